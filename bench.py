@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — MPC solves/s of the batched TinyMPC ADMM solver on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     (N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 Workload (BASELINE.json configs[2], the configuration the metric is quoted on):
@@ -16,10 +16,14 @@ predictor sweep and bucket sort that let the launch start its longest instance g
 part of the timed step, not of `roofline.kernel_ms`).  Inputs are resident in HBM before the timed region.  The batch shards embarrassingly across ranks (weak scaling: 65536 instances per GPU); there is no
 data-path collective — torch.distributed is used only for the barriers and the max-over-ranks of the time.
 
-Prints ONE JSON line (rank 0).  `roofline` and `cpu_baseline` are described in DESIGN.md §Measurement.  At N=1 the line
-also carries extras that never enter `value`: `fast_arithmetic` (the fma variant of the kernel), `closed_loop` (warm-started
-MPC steps in one launch), `pipelined_batches` (consecutive batches double-buffered on two streams), `fp64_tinytype` (the
-same workload through the `typedef double tinytype` library).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the headline (`value`,
+`ms_per_step`, `config`); it measures and checks nothing else.  With --full the line also carries what takes runs of its
+own: `roofline` (per-step kernel times) and `cpu_baseline` with the `parity` sample, with more than
+one rank the `final_gather` check, and at N=1 extras that never enter `value`: `fixed10`, `transfers`, `fast_arithmetic`
+(the fma variant of the kernel), `closed_loop` (warm-started MPC steps in one launch), `pipelined_batches` (consecutive
+batches double-buffered on two streams), `fp64_tinytype` (the same workload through the `typedef double tinytype` library).
+--dump-outputs DIR writes what the last timed step computed as .npy files (dump_outputs); the inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -79,6 +83,27 @@ def kernel_isa_sha(kernel_name: str):
     goes stale exactly when the kernel's code changes."""
     import accelerated_tinympc_amd as T
     return T.build.kernel_isa_sha(kernel_name)
+
+
+DUMP_BYTES = 48 << 20   # --dump-outputs: at most this many bytes of arrays in all
+
+
+def dump_outputs(out_dir: str, sol, suffix: str = "") -> None:
+    """--dump-outputs: what a caller of the timed path receives from its last step — the solution x (B, N, nx) and u (B, N-1, nu)
+    of every instance, its iteration count, status and four residuals — as float32 `<name><suffix>.npy` under out_dir.  Up to
+    DUMP_BYTES all instances are written; beyond that a fixed, seeded sample of them (the same for the same batch and class),
+    whose instance indices are `sample_index<suffix>.npy` (float64)."""
+    B, nx, nu, N = sol.B, sol.nx, sol.nu, sol.N
+    per_instance = (N * nx + (N - 1) * nu + 6) * 4 + 8
+    n = min(B, DUMP_BYTES // per_instance)
+    idx = np.arange(B) if n == B else np.sort(np.random.default_rng(20240607).choice(B, n, replace=False))
+    it, st, res = sol.get_status()
+    out = {"x": sol.get_x()[idx], "u": sol.get_u()[idx], "iter": it[idx].astype(np.float32), "status": st[idx].astype(np.float32),
+           "residuals": res[idx].astype(np.float32), "sample_index": idx.astype(np.float64)}
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, a in out.items():
+        np.save(d / f"{name}{suffix}.npy", np.ascontiguousarray(a))
 
 
 def cpu_all_cores(config: str, total: int, settings: dict, seconds: float = 5.0):
@@ -255,9 +280,14 @@ def main():
                          "(tiny_batch_set_dispatch; the predictor sweep and the sort run inside the timed region), 2 longest first by the previous "
                          "solve's iteration counts (warm-started launches), -1 the library's default: 1 for the cold-start step timed here, 2 for the "
                          "warm-started launches of the closed_loop extra")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg (and with it the parity sample)")
-    ap.add_argument("--no-closed-loop", action="store_true", help="skip the fixed10 / transfers legs and the warm-started closed-loop and pipelined-batches extras (profiling runs: "
+    ap.add_argument("--full", action="store_true", help="besides the headline, measure and check everything else: the cpu_baseline legs and the parity "
+                    "sample, per-step kernel times and the roofline, the final gather of a multi-rank run and the extras of rank 0 "
+                    "(fixed10, transfers, fast_arithmetic, closed_loop, pipelined_batches, fp64_tinytype)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline leg (and with it the parity sample)")
+    ap.add_argument("--no-closed-loop", action="store_true", help="with --full: skip the fixed10 / transfers legs and the warm-started closed-loop and pipelined-batches extras (profiling runs: "
                     "its launches of the same kernel would be averaged into the per-kernel statistics)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed (x, u, iter, status, "
+                    "residuals; a seeded sample of the instances beyond 48 MiB) as DIR/<name>.npy, DIR/<name>_rank<r>.npy with more than one rank")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -284,7 +314,7 @@ def main():
     # the all-core CPU baseline runs first: it starts one reference process per core, which this process may only do while it has
     # not yet initialised the GPU
     all_cores = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         cfg0 = CONFIGS[args.config]
         try:
             all_cores = cpu_all_cores(args.config, (args.batch or cfg0.get("per_gpu") or cfg0["total"]),
@@ -378,30 +408,34 @@ def main():
         # the library keeps ONE hipEvent pair per handle: of the pairs recorded in this loop only the last can be read afterwards, so only the last step
         # records one (a pair costs ~12 us of command-processor time around the solve launch: 6.3 us in front of and 5.9 us behind the kernel in the
         # rocprofv3 trace; the first nineteen pairs used to be recorded and overwritten)
-        if k == args.steps - 1:
+        if args.full and k == args.steps - 1:
             sol.enable_timing(True)
         step()
     sol.synchronize()
     barrier()
     dt = time.perf_counter() - t0
-    kernel_ms = [sol.last_solve_ms()]  # events of the last timed step (recorded by the library on its launch stream)
-    # per-step kernel durations: a second, untimed pass with an event read after every step
-    for _ in range(min(args.steps, 10)):
-        step()
-        kernel_ms.append(sol.last_solve_ms())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, sol, f"_rank{rank}" if world > 1 else "")
+    kernel_ms = []
+    if args.full:
+        kernel_ms = [sol.last_solve_ms()]  # events of the last timed step (recorded by the library on its launch stream)
+        # per-step kernel durations: a second, untimed pass with an event read after every step
+        for _ in range(min(args.steps, 10)):
+            step()
+            kernel_ms.append(sol.last_solve_ms())
     n_unsolved = sol.wait()
     # reported by the library for the launches just timed (tiny_batch_dispatch_applied), not re-derived here
     dispatch_used = {0: "index order", 1: "longest first by predicted iteration count (predictor sweep + sort inside the timed region)",
                      2: "caller-supplied order", 3: "longest first by the previous solve's iteration counts"}[sol.dispatch_applied()]
     iters, status, _ = sol.get_status()
     npar = min(B, 2048)
-    gpu_u = sol.get_u()[:npar].copy() if (rank == 0 and world == 1 and not args.no_cpu) else None  # parity sample, before the extras touch the workspace
+    gpu_u = sol.get_u()[:npar].copy() if (args.full and rank == 0 and world == 1 and not args.no_cpu) else None  # parity sample, before the extras touch the workspace
     agg = T.sharding.reduce_stats(dist, "cuda" if backend == "nccl" else "cpu", iters, status, cost.flops_of(iters, status), dt)
     dt = agg["wall_s"]  # max over ranks
     # optional epilogue of SURVEY.md §8(e), outside the timed region: every rank obtains u.col(0) of all instances with
     # one all-gather (nu floats per instance; RCCL over xGMI on the real runs).  Never allowed to break the bench line.
     gather = None
-    if dist is not None:
+    if args.full and dist is not None:
         try:
             cap = max(T.sharding.block_partition(total, world, r)[1] - T.sharding.block_partition(total, world, r)[0] for r in range(world))
             d_u0 = torch.zeros((cap, NU), dtype=torch.float32, device="cuda")
@@ -423,12 +457,12 @@ def main():
             gather = {"error": f"{type(e).__name__}: {e}"}  # reported in the line AND, with more than one rank, as exit code 3 below
     total_solves = total * args.steps
     value = total_solves / dt
-    extras_ok = rank == 0 and world == 1 and not args.kernel and args.config == "tracking"
+    extras_ok = args.full and rank == 0 and world == 1 and not args.kernel and args.config == "tracking"
     # "report both fixed-iteration (tol = 0, max_iter = 10) and early-exit throughput" — the same kernel, exact
     # arithmetic, same inputs, ten iterations for every instance; and the H2D / D2H legs of a host-driven step (x0 up, u.col(0) down),
     # hipEvent-timed on pinned buffers.  Extras of rank 0: neither enters `value`.
     fixed10 = transfers = None
-    if rank == 0 and world == 1 and args.mode == "early_exit" and not args.no_closed_loop:   # (profiling runs skip it: the same kernel on another workload)
+    if args.full and rank == 0 and world == 1 and args.mode == "early_exit" and not args.no_closed_loop:   # (profiling runs skip it: the same kernel on another workload)
         try:
             sol.set_settings(**dict(settings, abs_pri_tol=0.0, abs_dua_tol=0.0, max_iter=10))
             k10 = cold_name()   # (before the steps: it resets the workspace)
@@ -497,7 +531,7 @@ def main():
             fast["_u_fixed10"] = sol.get_u()[:npar].copy()
             sol.set_settings(**settings)
         sol.select_kernel(0)
-    elif rank == 0 and world == 1 and not args.kernel and args.config == "random32" and kname.startswith(("tile48", "waveres")):
+    elif args.full and rank == 0 and world == 1 and not args.kernel and args.config == "random32" and kname.startswith(("tile48", "waveres")):
         sol.select_kernel(3)   # the nx = 32 class: kernel time of the fma instantiation only (its parity bar is held by the GPU tests)
         step()
         ms = []
@@ -624,7 +658,8 @@ def main():
         except Exception as e:  # noqa: BLE001
             fp64 = {"error": f"{type(e).__name__}: {e}"}
 
-    if rank == 0:
+    roof = None
+    if rank == 0 and args.full:
         k_ms = float(np.mean(kernel_ms))
         fl = cost.flops_of(iters, status)  # this rank's launch
         t_mem = B * cost.b_solve / (PEAK_HBM_GBS * 1e9)
@@ -677,6 +712,7 @@ def main():
                     alg_flops_per_iteration={"forward_sweep_and_updates": cost.f_fwd, "backward_sweep": cost.f_bwd},
                     alg_flops_per_launch=fl, note="fp32 vector/MFMA peak 157.3 TFLOP/s; the path is not a dense "
                     "GEMM, 'mfma' here means the fp32 FMA roof (vector == f32-MFMA peak on gfx950)")
+    if rank == 0:
         what = "quadrotor_tracking" if args.config == "tracking" else "codegen_random (seeded marginally stable system, SURVEY.md §8(d) config 4)"
         line = {
             "metric": cfg["metric"], "value": value, "unit": "solves/s",
@@ -690,8 +726,9 @@ def main():
                        "dispatch": dispatch_used,
                        "mean_iters": agg["sum_iters"] / agg["n_instances"],
                        "max_iters": agg["max_iters"], "frac_converged": agg["n_converged"] / agg["n_instances"]},
-            "roofline": roof,
         }
+        if roof is not None:
+            line["roofline"] = roof
         if fixed10 is not None:
             line["fixed10"] = fixed10
         if transfers is not None:
@@ -706,7 +743,7 @@ def main():
             line["pipelined_batches"] = pipelined
         if fp64 is not None:
             line["fp64_tinytype"] = fp64
-        if not args.no_cpu and world == 1:  # rank 0 at N=1 only: the other ranks of a multi-GPU run would sit in the barrier
+        if args.full and not args.no_cpu and world == 1:  # rank 0 at N=1 only: the other ranks of a multi-GPU run would sit in the barrier
             cb, ref_first, kind = cpu_baseline(prob, make_batch, settings, fixed10_n=(npar if (fast is not None and "_u_fixed10" in fast) else 0))
             if all_cores is not None:
                 cb["all_cores"] = all_cores

@@ -21,7 +21,7 @@ def oracle_mod():
     from oracle import oracle as O
     lib = ROOT / "oracle" / "libtinympc_oracle.so"
     if shutil.which("make") and shutil.which("gcc"):
-        O.build(ref=(Path("/root/reference/src/tinympc").is_dir()))
+        O.build(ref=True)  # oracle/Makefile builds oracle/_ref only where it can read the reference tree
     elif not lib.exists():
         pytest.skip("the CPU checker (oracle/libtinympc_oracle.so) is neither prebuilt nor buildable here: no make / gcc on this box")
     return O

@@ -19,6 +19,9 @@ Scenarios:
                        u_min > u_max — infeasible boxes, per-row values), gains from the reference's tiny_codegen(); 24 instances,
                        three chained solves, bounds stored as full arrays (bnd_*)
   riccati_*            reference tiny_codegen() cache for cartpole and the random system
+  reference_headers    numbers and names out of the reference's headers (trajectory, quadrotor problem data, interface
+                       names), for the host tests that compare the package with them; generated on its own, from the
+                       reference tree given as the argument: make_golden.py reference_headers <reference tree>
   closed_loop_traces   whole closed loops of the compiled reference (tiny_solve + the examples' Eigen plant step) over
                        batches of 64 (20) instances: u.col(0), iter, status of EVERY step and the final x0 — hovering 70
                        steps, tracking 110 steps with sliding per-instance windows, cartpole 100 steps, (8,3,7) 25 steps
@@ -291,6 +294,32 @@ def closed_loop_traces():
     np.savez_compressed(OUT / "closed_loop_traces.npz", **d)
     print(f"wrote closed_loop_traces.npz ({(OUT / 'closed_loop_traces.npz').stat().st_size / 1024:.1f} KiB)")
 
+
+def reference_headers(ref: Path):
+    """reference_headers.npz: the numbers and names tests/test_host.py holds the package to, parsed out of the reference's
+    headers exactly as those tests once parsed them in place — the y_axis_line trajectory (301 x 12), the 20 Hz quadrotor's
+    problem data, the function names of tiny_wrapper.hpp and admm.hpp and TinyWorkspace's member names (types.hpp).
+    Values and identifiers only; no code."""
+    traj = (ref / "examples" / "trajectory_data" / "quadrotor_20hz_y_axis_line.hpp").read_text()
+    body = traj.split("{", 1)[1].rsplit("}", 1)[0]
+    d = {"y_axis_line": np.array([float(v) for v in body.replace("\n", " ").split(",") if v.strip()]).reshape(301, 12)}
+    params = (ref / "examples" / "problem_data" / "quadrotor_20hz_params.hpp").read_text()
+    for name in ("Adyn", "Bdyn", "Kinf", "Pinf", "Quu_inv", "AmBKt", "Q", "R"):
+        m = re.search(name + r"_data\s*\[[^\]]*\]\s*=\s*\{([^}]*)\}", params, re.S)
+        d["quadrotor_20hz_" + name] = np.array([float(v) for v in m.group(1).replace("\n", " ").split(",") if v.strip()])
+    src = ref / "src" / "tinympc"
+    types_body = (src / "types.hpp").read_text().split("Problem variables")[1].split("} TinyWorkspace")[0]
+    names = {"tiny_wrapper_functions": re.findall(r"void\s+(\w+)\s*\(", (src / "tiny_wrapper.hpp").read_text()),
+             "admm_functions": re.findall(r"^\s*(?:int|void|bool)\s+(\w+)\s*\(TinySolver", (src / "admm.hpp").read_text(), re.M),
+             "workspace_members": re.findall(r"^\s*(?:tiny_\w+|tinytype|int)\s+(\w+);", types_body, re.M)}
+    d["names"] = np.frombuffer(json.dumps(names).encode(), dtype=np.uint8)
+    np.savez_compressed(OUT / "reference_headers.npz", **d)
+    print(f"wrote reference_headers.npz ({(OUT / 'reference_headers.npz').stat().st_size / 1024:.1f} KiB)")
+
+
+if __name__ == "__main__" and len(sys.argv) > 2 and sys.argv[1] == "reference_headers":
+    reference_headers(Path(sys.argv[2]))   # python tests/golden/make_golden.py reference_headers <reference tree>
+    sys.exit(0)
 
 if __name__ == "__main__" and len(sys.argv) > 1 and sys.argv[1] == "codegen_random":
     O.build(ref=True)

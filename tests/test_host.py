@@ -76,24 +76,18 @@ def test_riccati_rejects_bad_arguments(tinympc):
 def test_trajectory_matches_reference_header(tinympc):
     X = tinympc.problems.y_axis_line()
     assert X.shape == (301, 12) and X[300, 7] == 0.0 and X[0, 7] == 0.2666667 and X[300, 1] == 4.0
-    hdr = Path("/root/reference/examples/trajectory_data/quadrotor_20hz_y_axis_line.hpp")
-    if not hdr.exists():
-        pytest.skip("reference tree not present")
-    body = hdr.read_text().split("{", 1)[1].rsplit("}", 1)[0]
-    vals = np.array([float(v) for v in body.replace("\n", " ").split(",") if v.strip()])
+    # the numbers of the reference's quadrotor_20hz_y_axis_line.hpp (tests/golden/make_golden.py reference_headers)
+    vals = np.load(GOLDEN / "reference_headers.npz")["y_axis_line"]
     assert vals.size == 301 * 12
     assert np.array_equal(vals.reshape(301, 12), X)
 
 
 def test_problem_data_matches_reference_headers(tinympc):
-    hdr = Path("/root/reference/examples/problem_data/quadrotor_20hz_params.hpp")
-    if not hdr.exists():
-        pytest.skip("reference tree not present")
-    txt = hdr.read_text()
+    # the <name>_data arrays of the reference's quadrotor_20hz_params.hpp (tests/golden/make_golden.py reference_headers)
+    z = np.load(GOLDEN / "reference_headers.npz")
     q = tinympc.problems.quadrotor(20, 30)
     for name in ("Adyn", "Bdyn", "Kinf", "Pinf", "Quu_inv", "AmBKt", "Q", "R"):
-        m = re.search(name + r"_data\s*\[[^\]]*\]\s*=\s*\{([^}]*)\}", txt, re.S)
-        vals = np.array([float(v) for v in m.group(1).replace("\n", " ").split(",") if v.strip()])
+        vals = z["quadrotor_20hz_" + name]
         assert np.array_equal(vals, np.asarray(q[name]).ravel()), name
     assert q["rho"] == 5.0
 
@@ -140,6 +134,12 @@ def test_cpp_example_compiles_and_links_against_the_c_abi(tinympc, tmp_path):
     assert r.returncode == 0, r.stderr
 
 
+def reference_names():
+    """Function and member names of the reference's headers, recorded in tests/golden/reference_headers.npz."""
+    import json
+    return json.loads(bytes(np.load(GOLDEN / "reference_headers.npz")["names"]).decode())
+
+
 WRAPPER_SYMBOLS = ["set_x0", "set_xref", "set_umin", "set_umax", "set_xmin", "set_xmax", "reset_dual_variables",
                    "call_tiny_solve", "get_x", "get_u"]  # src/tinympc/tiny_wrapper.hpp:14-23
 
@@ -149,10 +149,8 @@ def test_wrapper_library_exports_the_reference_wrapper_names(tinympc):
     lib = C.CDLL(str(ROOT / "accelerated-tinympc_amd" / "lib" / "libtinympc_wrapper.so"))
     for s in WRAPPER_SYMBOLS + ["tiny_wrapper_setup", "tiny_wrapper_teardown", "tiny_wrapper_last_status"]:
         assert hasattr(lib, s), s
-    hdr = Path("/root/reference/src/tinympc/tiny_wrapper.hpp")
-    if hdr.exists():  # the ten names are exactly the reference's
-        names = re.findall(r"void\s+(\w+)\s*\(", hdr.read_text())
-        assert sorted(names) == sorted(WRAPPER_SYMBOLS)
+    # the ten names are exactly the functions of the reference's tiny_wrapper.hpp
+    assert sorted(reference_names()["tiny_wrapper_functions"]) == sorted(WRAPPER_SYMBOLS)
     # before setup every call is a reported no-op, never a crash
     lib.reset_dual_variables(0)
     assert lib.tiny_wrapper_last_status(None, None) < 0
@@ -213,10 +211,7 @@ def test_native_names_header_is_plain_c_and_matches_the_binding(tinympc, tmp_pat
     lib = C.CDLL(str(ROOT / "accelerated-tinympc_amd" / "lib" / "libtinympc_wrapper.so"))
     for s in NATIVE_SYMBOLS:
         assert hasattr(lib, s), s
-    hdr = Path("/root/reference/src/tinympc/admm.hpp")
-    if hdr.exists():
-        names = re.findall(r"^\s*(?:int|void|bool)\s+(\w+)\s*\(TinySolver", hdr.read_text(), re.M)
-        assert sorted(names) == sorted(NATIVE_SYMBOLS)
+    assert sorted(reference_names()["admm_functions"]) == sorted(NATIVE_SYMBOLS)   # the functions of the reference's admm.hpp
     members = ["nx", "x", "y", "primal_residual_state", "iter", "Q", "Bdyn", "u_min", "Xref", "Qu"]
     src = tmp_path / "layout.c"
     src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "tinympc_admm.h"\nint main(void){\n'
@@ -229,11 +224,7 @@ def test_native_names_header_is_plain_c_and_matches_the_binding(tinympc, tmp_pat
                                          C.sizeof(native.TinyWorkspace), C.sizeof(native.TinySolver)]
     assert [int(v) for v in out[4:]] == [getattr(native.TinyWorkspace, m).offset for m in members]
     # member names and order are the reference's (types.hpp:52-97), with nx,nu,N in front and pointers for matrices
-    ref_types = Path("/root/reference/src/tinympc/types.hpp")
-    if ref_types.exists():
-        body = ref_types.read_text().split("Problem variables")[1].split("} TinyWorkspace")[0]
-        ref_members = re.findall(r"^\s*(?:tiny_\w+|tinytype|int)\s+(\w+);", body, re.M)
-        assert [f[0] for f in native.TinyWorkspace._fields_[3:]] == ref_members
+    assert [f[0] for f in native.TinyWorkspace._fields_[3:]] == reference_names()["workspace_members"]
 
 
 @pytest.mark.parametrize("name", ["r01_bench_default_line.json", "r02_bench_default_line_d.json", "r02_bench_random32_line_b.json",

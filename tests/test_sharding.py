@@ -80,7 +80,7 @@ def test_bench_two_rank_rehearsal(tmp_path):
     for config, extra in (("tracking", ["--batch", "4096"]), ("random32", ["--batch", "512"])):
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                "--master-port", str(_free_port()), str(ROOT / "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-               "--config", config, *extra]
+               "--config", config, "--full", *extra]   # --full: the final gather runs only there
         r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]
         lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -119,7 +119,7 @@ def test_bench_rccl_branch_single_rank(tmp_path):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), str(ROOT / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "8192",
-           "--no-cpu", "--no-closed-loop"]
+           "--full", "--no-cpu", "--no-closed-loop"]   # --full: the final gather runs only there
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
