@@ -57,6 +57,13 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 #ifndef TINY_T16_SCHED
 #define TINY_T16_SCHED 1 // the scheduling fences pay in exact arithmetic only (measured: exact 2.01 -> 1.88 ms, fma 1.02 -> 1.08)
 #endif
+#ifndef TINY_T16_LINES
+#define TINY_T16_LINES 1 // live-out steps 2j, 2j + 1 stored together as whole 128-byte lines of eight instances (DPP row_ror:8 pairing)
+#endif
+#ifndef TINY_T16_STAMP
+#define TINY_T16_STAMP 0 // measurement build only (tools/t16_epilogue_stamps.py): per wave and tile, s_memrealtime at the claim, at the end of the
+                         // iteration loop and after the live-out stores are issued, into the buffer tiny_t16_stamp_begin() allocates
+#endif
 
 #if TINY_T16_ABLATE == 1 // timing experiment: no matrix-core work (results are wrong)
 __device__ __forceinline__ f32x4 t16_fake4(float a, float b, f32x4 c) { c[0] += a; c[1] += b; c[2] += a; c[3] += b; return c; }
@@ -390,6 +397,35 @@ __device__ __forceinline__ f32x4 t16_transpose4(const f32x4 &r)
 constexpr int TILE16_WAVES = 4;         // waves per workgroup = one per SIMD of a CU; they share the bounds and reference tables
 constexpr int TILE16_MAX_TABLE_ROWS = 512;
 
+// Pairs the live-out rows of steps 2j (e) and 2j + 1 (o) after t16_transpose4 — lane (g, c) holds 16-byte piece g of instance c's row — into two
+// registers of WHOLE 128-byte lines: an instance's array is N x 64 bytes, so rows 2j and 2j + 1 are one line wherever N is even.  A rotation by
+// half a 16-lane row (row_ror:8) with a bank mask writes only one half of each row: lo8 keeps e in lanes c < 8 and takes o of instance c - 8 in
+// lanes c >= 8 (line of instance c & 7, piece g + 4 (c >> 3)); hi8 the same for instances 8 .. 15.  One store instruction then writes eight whole
+// lines instead of sixteen half lines: the same number of store instructions, half the line requests, and no partial line reaches the caches.
+__device__ __forceinline__ void t16_pair_lines(const f32x4 &e, const f32x4 &o, f32x4 &lo8, f32x4 &hi8)
+{
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+    {
+        lo8[k] = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(e[k]), __float_as_int(o[k]), 0x128, 0xf, 0xc, false)); // banks 2, 3 <- lane - 8
+        hi8[k] = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(o[k]), __float_as_int(e[k]), 0x128, 0xf, 0x3, false)); // banks 0, 1 <- lane + 8
+    }
+}
+
+#if TINY_T16_STAMP && !defined(TINY_T16_PI_UNIT)
+constexpr int T16_STAMP_TILES = 32; // records per wave slot: [tile claimed, iteration loop left, live-out stores issued, tile (-1: the failed claim)]
+__device__ unsigned long long *t16_stamp_buf; // null until tiny_t16_stamp_begin(): nothing is written then
+__device__ int t16_stamp_slots;                 // wave slots the buffer holds: a wave beyond them records nothing
+__device__ __forceinline__ void t16_stamp(int wslot, int k, int field, unsigned long long v)
+{
+    unsigned long long *const buf = t16_stamp_buf;
+    if (buf && wslot < t16_stamp_slots && k < T16_STAMP_TILES && (threadIdx.x & 63) == 0) buf[((size_t)wslot * T16_STAMP_TILES + k) * 4 + field] = v;
+}
+#define T16_STAMP(k, field, v) t16_stamp((int)blockIdx.x * TILE16_WAVES + (int)(threadIdx.x >> 6), (k), (field), (v))
+#else
+#define T16_STAMP(k, field, v) ((void)0)
+#endif
+
 // ---- BR / XR = true (round 4, the "pi" instantiations): box bounds (BR) and / or the reference (XR) PER INSTANCE (types.hpp:88-92: every
 // reference workspace owns its u_min .. x_max and its Xref).  The kernel has no register to prefetch them into (512 of 512 in use) and the
 // 61 KB + 30 KB a tile would need do not fit LDS beside the slack, so the rows travel HBM/L2 -> LDS by LDS-DMA (`global_load_lds_dwordx4`: no
@@ -555,11 +591,18 @@ __global__ __launch_bounds__(WAVE * TILE16_WAVES, 1) void admm_tile16_kernel(con
         if (tail_stride && (((unsigned)blockIdx.x * TILE16_WAVES + (unsigned)wv) % tail_stride) == 0u) qinc = 0x10000;
         qinc = __builtin_amdgcn_readfirstlane(qinc);
     }
+#if TINY_T16_STAMP
+    int stamp_k = 0;
+#else
+    constexpr int stamp_k = 0;
+#endif
     for (;;)
     {
     int slot = 0;
     if (lane == 0) slot = atomicAdd(P.n_unsolved + 1, qinc);
     slot = __builtin_amdgcn_readfirstlane(slot);
+    T16_STAMP(stamp_k, 0, __builtin_amdgcn_s_memrealtime());
+    T16_STAMP(stamp_k, 3, ~0ull);
     if (DQ && ntiles <= 32768)
     {
         const int qh = slot & 0xffff, qt = (int)((unsigned)slot >> 16);
@@ -576,6 +619,7 @@ __global__ __launch_bounds__(WAVE * TILE16_WAVES, 1) void admm_tile16_kernel(con
     int tile = slot;
     if (P.order) tile = P.order[slot];
     const bool tile_ok = tile >= 0 && tile < ntiles; // also rejects a bad entry of a caller-supplied order: such a wave stores nothing
+    T16_STAMP(stamp_k, 3, (unsigned long long)(unsigned)tile);
     const int inst = tile * 16 + c;
     const bool valid = tile_ok && inst < P.batch;
     const int inst_a = valid ? inst : P.batch - 1; // padding columns of the last tile load a valid instance and store nothing
@@ -1018,6 +1062,7 @@ __global__ __launch_bounds__(WAVE * TILE16_WAVES, 1) void admm_tile16_kernel(con
         for (int i = 0; i < N; i++) a[i][0] = a[i][1] = a[i][2] = a[i][3] = 0.f; // y = g = 0 (:106-107)
     }
     } // MPC steps
+    T16_STAMP(stamp_k, 1, __builtin_amdgcn_s_memrealtime());
 
     if (P.max_iter <= 0) // tiny_solve only sets status and iter (admm.cpp:114-117,151)
     {
@@ -1027,6 +1072,10 @@ __global__ __launch_bounds__(WAVE * TILE16_WAVES, 1) void admm_tile16_kernel(con
             P.iter[inst] = 1;
             atomicAdd(P.n_unsolved, 1);
         }
+        T16_STAMP(stamp_k, 2, __builtin_amdgcn_s_memrealtime());
+#if TINY_T16_STAMP
+        ++stamp_k;
+#endif
         continue;
     }
 
@@ -1067,6 +1116,76 @@ __global__ __launch_bounds__(WAVE * TILE16_WAVES, 1) void admm_tile16_kernel(con
             if (valid2) *reinterpret_cast<f32x4 *>(dst + obase2 + i * 16) = o;
         };
         float s[3] = {x0[0], x0[1], x0[2]};
+        // (whole lines in the shared-table launches from a reset workspace only, exact and fma, the instantiations whose kernel times were
+        //  measured with it: the warm-start and closed-loop instantiations sit at the allocator's cliff, and the paired form sends them to
+        //  scratch — the closed-loop ones from 280 to 796 bytes per lane —; the pi ones keep the row-wise stores)
+        if constexpr (XPOSE && TINY_T16_LINES && COLD && !MPC && !BR && !XR)
+        {
+            // the live-out of step i that the state holds as it stands (everything but x, u)
+            auto slack_of = [&](int i) { return reinterpret_cast<const f32x4_ma *>(stage_w + i * (WAVE * 4))[lane]; };
+            auto lin_of = [&](int i, const f32x4 &sni) {
+                const f32x4 xr = load_xref(tab, wstart, i);
+                f32x4 lin = lin_cost4<EXACT>(cost_of(xr), rho4, sni - dual4(i));
+                if (i == N - 1) lin[3] = 0.f;
+                return lin;
+            };
+            // p.col(N-1) is rewritten by every forward sweep (admm.cpp:83-84); the other columns and d come from the
+            // last backward sweep this instance executed (an instance that never ran one keeps its live-in p, d)
+            auto pd_of = [&](int i) { return i == N - 1 ? f32x4{pN[0], pN[1], pN[2], 0.f} : f32x4{acc_get(pl[i][0]), acc_get(pl[i][1]), acc_get(pl[i][2]), dr[i]}; };
+            // a converged instance returned before v = vnew (admm.cpp:135-142): its v, z are the slack the last sweep replaced
+            auto vz_of = [&](int i, const f32x4 &sni) {
+                f32x4 vzv;
+    #pragma unroll
+                for (int v = 0; v < 4; v++)
+                {
+                    const float bov = acc_get(bo[i][v]);
+                    vzv[v] = solved ? bov : sni[v];
+                }
+                return vzv;
+            };
+            // Steps in pairs, each array's two rows as whole 128-byte lines (t16_pair_lines): the lane stores piece g + 4 (c >> 3) of the line of
+            // instance tile 16 + (c & 7) (lo8) and of that + 8 (hi8).  The arrays the state holds go first; x, u last, behind the regeneration chain,
+            // whose products are in flight while the other stores issue.  (An odd N leaves its last step to the row-wise store.)
+            const int instL = tile * 16 + (c & 7);
+            const bool validL = tile_ok && instL < P.batch, validH = tile_ok && instL + 8 < P.batch;
+            const int obaseL = (validL ? instL : 0) * (N * 16) + ((c >> 3) << 4) + 4 * g, offH = 8 * N * 16;
+            auto put2 = [&](float *dst, int i, const f32x4 &ve, const f32x4 &vo) {
+                f32x4 lo8, hi8;
+                t16_pair_lines(t16_transpose4(ve), t16_transpose4(vo), lo8, hi8);
+                if (validL) *reinterpret_cast<f32x4 *>(dst + obaseL + i * 16) = lo8;
+                if (validH) *reinterpret_cast<f32x4 *>(dst + obaseL + offH + i * 16) = hi8;
+            };
+#pragma unroll
+            for (int i = 0; i + 1 < N; i += 2)
+            {
+                const f32x4 sne = slack_of(i), sno = slack_of(i + 1);
+                put2(P.gy, i, dual4(i), dual4(i + 1));
+                put2(P.vzn, i, sne, sno);
+                put2(P.vz, i, vz_of(i, sne), vz_of(i + 1, sno));
+                put2(P.pd, i, pd_of(i), pd_of(i + 1));
+                put2(P.qr, i, lin_of(i, sne), lin_of(i + 1, sno));
+                // x,u: regenerated from the d of the last executed forward sweep by the same instruction sequence
+                float ue = 0.f, xe[3];
+                M.lqr(s, dr[i], ue, xe);
+                const f32x4 sve = {s[0], s[1], s[2], ue};
+                float uo = 0.f, xo[3] = {0.f, 0.f, 0.f};
+                if (i + 1 < N - 1) M.lqr(xe, dr[i + 1], uo, xo);
+                put2(P.xu, i, sve, f32x4{xe[0], xe[1], xe[2], uo});
+                s[0] = xo[0]; s[1] = xo[1]; s[2] = xo[2];
+            }
+            if constexpr (N % 2 == 1)
+            {
+                const f32x4 sni = slack_of(N - 1);
+                put(P.xu, N - 1, f32x4{s[0], s[1], s[2], 0.f});
+                put(P.qr, N - 1, lin_of(N - 1, sni));
+                put(P.pd, N - 1, pd_of(N - 1));
+                put(P.vz, N - 1, vz_of(N - 1, sni));
+                put(P.vzn, N - 1, sni);
+                put(P.gy, N - 1, dual4(N - 1));
+            }
+        }
+        else
+        {
 #pragma unroll
         for (int i = 0; i < N; i++)
         {
@@ -1099,8 +1218,11 @@ __global__ __launch_bounds__(WAVE * TILE16_WAVES, 1) void admm_tile16_kernel(con
             if constexpr (!XPOSE) reinterpret_cast<f32x4_ma *>(stage_w + i * (WAVE * 4))[lane] = sni; // the slot gets its slack back: the deferred sweep below reads it
             s[0] = xn[0]; s[1] = xn[1]; s[2] = xn[2];
         }
+        }
         // The deferred backward sweep of the last permitted iteration (admm.cpp:141-144 with iter = max_iter): instances that
-        // exhausted max_iter get p, d from it; the others keep what pass 1 stored (the same lanes store again, in program order).
+        // exhausted max_iter get p, d from it; the others keep what pass 1 stored.  (Row-wise pass 1: the same lanes store again, in program
+        // order.  Paired pass 1: OTHER lanes of the same wave wrote these rows; the later store wins because the stores of one wave to one
+        // address complete in issue order — the bitwise tile16 tests at max_iter 1 / 2 cover it.)
         const unsigned long long umask = __ballot(valid && !solved);
         if (umask != 0ull)
         {
@@ -1147,6 +1269,10 @@ __global__ __launch_bounds__(WAVE * TILE16_WAVES, 1) void admm_tile16_kernel(con
             if (g == 0 && P.xref_mode == 1) P.xref_start[inst] = wstart;
         }
     }
+    T16_STAMP(stamp_k, 2, __builtin_amdgcn_s_memrealtime());
+#if TINY_T16_STAMP
+    ++stamp_k;
+#endif
     } // tile queue
 }
 
@@ -1236,6 +1362,36 @@ bool tile16_supported(int nx, int nu, int N)
 }
 
 int tile16_max_table_rows() { return TILE16_MAX_TABLE_ROWS; }
+
+#if TINY_T16_STAMP
+// measurement build only: a zeroed stamp buffer with one record set per wave slot of the current device (one persistent workgroup of
+// TILE16_WAVES waves per CU: the launches that follow write into it; a wave beyond the slots records nothing) and its copy to the host
+static int t16_stamp_nslots = 0;
+extern "C" int tiny_t16_stamp_begin()
+{
+    static unsigned long long *buf = nullptr;
+    int dev = 0, ncu = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) return 1;
+    const int nslots = ncu * TILE16_WAVES;
+    const size_t bytes = (size_t)nslots * T16_STAMP_TILES * 4 * sizeof(unsigned long long);
+    if (buf) (void)hipFree(buf);
+    buf = nullptr;
+    if (hipMalloc(&buf, bytes) != hipSuccess || hipMemset(buf, 0, bytes) != hipSuccess) return 1;
+    if (hipMemcpyToSymbol(HIP_SYMBOL(t16_stamp_slots), &nslots, sizeof(nslots)) != hipSuccess) return 1;
+    if (hipMemcpyToSymbol(HIP_SYMBOL(t16_stamp_buf), &buf, sizeof(buf)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return 1;
+    t16_stamp_nslots = nslots;
+    return 0;
+}
+extern "C" int tiny_t16_stamp_slots() { return t16_stamp_nslots; }
+extern "C" int tiny_t16_stamp_read(unsigned long long *host, int nslots)
+{
+    if (nslots > t16_stamp_nslots) return 1;
+    unsigned long long *buf = nullptr;
+    if (hipMemcpyFromSymbol(&buf, HIP_SYMBOL(t16_stamp_buf), sizeof(buf)) != hipSuccess || !buf) return 1;
+    return hipMemcpy(host, buf, (size_t)nslots * T16_STAMP_TILES * 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess;
+}
+extern "C" int tiny_t16_stamp_tiles() { return T16_STAMP_TILES; }
+#endif
 
 hipError_t launch_admm_tile16(int N, bool exact, const RowParams &P, hipStream_t stream, int n_cu, int tail)
 {
