@@ -112,12 +112,10 @@ struct GenIdx
     __device__ size_t u(int step, int row) const { return (((size_t)tile * (N - 1) + step) * WAVE + ((row & 3) * 16 + c)) * NUC + (row >> 2); }
 };
 
-__global__ __launch_bounds__(64) void admm_generic_kernel(const SolveParams P, const float *__restrict__ G, int NXC, int NUC)
+// the body of both kernels below: G = the gains of this instance, rho its rho
+__device__ __forceinline__ void generic_body(const SolveParams &P, const float *__restrict__ G, const float rho, int NXC, int NUC, const int inst)
 {
-    const int inst = blockIdx.x * blockDim.x + threadIdx.x;
-    if (inst >= P.batch) return;
     const int nx = P.nx, nu = P.nu, N = P.N;
-    const float rho = P.rho;
     const float *Kinf = G, *Pinf = Kinf + nu * nx, *Quu = Pinf + nx * nx, *AmBKt = Quu + nu * nu, *Adyn = AmBKt + nx * nx, *Bdyn = Adyn + nx * nx,
                 *Qd = Bdyn + nx * nu;
     GenIdx I{inst / TILE, inst % TILE, N, NXC, NUC};
@@ -298,6 +296,21 @@ __global__ __launch_bounds__(64) void admm_generic_kernel(const SolveParams P, c
     P.iter[inst] = itn;
     if (st != TINY_STATUS_SOLVED_) atomicAdd(P.n_unsolved, 1);
 }
+
+__global__ __launch_bounds__(64) void admm_generic_kernel(const SolveParams P, const float *__restrict__ G, int NXC, int NUC)
+{
+    const int inst = blockIdx.x * blockDim.x + threadIdx.x;
+    if (inst >= P.batch) return;
+    generic_body(P, G, P.rho, NXC, NUC, inst);
+}
+
+// per-instance models (tiny_batch_set_models): the instance's own record Kinf | Pinf | Quu_inv | AmBKt | Adyn | Bdyn | Q and rho
+__global__ __launch_bounds__(64) void admm_generic_pm_kernel(const SolveParams P, const ModelParams M, int NXC, int NUC)
+{
+    const int inst = blockIdx.x * blockDim.x + threadIdx.x;
+    if (inst >= P.batch) return;
+    generic_body(P, M.mats + (size_t)inst * M.mats_stride, M.rho[inst], NXC, NUC, inst);
+}
 } // namespace
 
 // exact arithmetic is defined for these dimensions (see the header comment)
@@ -307,6 +320,13 @@ hipError_t launch_admm_generic(const SolveParams &P, const float *gains, int nxc
 {
     if (!generic_exact_supported(P.nx, P.nu)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(admm_generic_kernel, dim3((P.batch + 63) / 64), dim3(64), 0, stream, P, gains, nxc, nuc);
+    return hipGetLastError();
+}
+
+hipError_t launch_admm_generic_pm(const SolveParams &P, const ModelParams &M, int nxc, int nuc, hipStream_t stream)
+{
+    if (!generic_exact_supported(P.nx, P.nu) || !M.mats || !M.rho || M.mats_stride != (unsigned)pm_gen_floats(P.nx, P.nu)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(admm_generic_pm_kernel, dim3((P.batch + 63) / 64), dim3(64), 0, stream, P, M, nxc, nuc);
     return hipGetLastError();
 }
 

@@ -43,10 +43,14 @@ constexpr int BPI_AHEAD = TINY_BPI_AHEAD;
 // one more DPP product group behind the Riccati step (rowlane_math.h d2p_term: added to the STORED p_i, in sequential order, as Eigen does).
 // fp32 storage, batch-shared bounds, one solve per launch.
 constexpr int OPT_AHEAD = 4;
-template <int NX, int NU, int N, bool EXACT, bool H16, bool MPC = false, bool BPI = false, bool D32 = false, bool OPT = false>
-__global__ __launch_bounds__(WAVE, (N > 32 && EXACT && !H16) ? 1 : 2) void admm_rowlane_kernel(const RowParams P)
+// The body of both kernels below.  PM = true (per-instance models, tiny_batch_set_models): the gain rows and rho of a row come from
+// that instance's record, mats = M.mats + inst * M.mats_stride and M.rho[inst], instead of the one table the batch shares; the
+// plant step of the on-chip loop then uses the instance's own Adyn / Bdyn (the M1 / M2 rows) with no further change.
+template <int NX, int NU, int N, bool EXACT, bool H16, bool MPC, bool BPI, bool D32, bool OPT, bool PM>
+__device__ __forceinline__ void rowlane_body(const RowParams &P, const ModelParams &M)
 {
     static_assert(!OPT || (!H16 && !MPC && !BPI && !D32), "the optional terms are instantiated for fp32 storage, shared bounds, one solve per launch");
+    static_assert(!PM || (!H16 && !D32 && !OPT), "per-instance models are instantiated for fp32 storage without the optional terms");
     constexpr bool HD = H16 && !D32; // storage precision of the duals (gy)
     const int lane = threadIdx.x;
     const int r16 = lane & 15;
@@ -59,7 +63,7 @@ __global__ __launch_bounds__(WAVE, (N > 32 && EXACT && !H16) ? 1 : 2) void admm_
     const int inst_a = valid ? inst : P.batch - 1;
     const bool is_x = r16 < NX;
     const bool is_u = (r16 >= NX) && (r16 < NX + NU);
-    const float rho = P.rho;
+    const float rho = PM ? M.rho[inst_a] : P.rho;
 
     // ---- box bounds of the whole horizon, shared by the batch: LDS table [N][16] of {lo, hi} ----
     __shared__ float2 bnd[BPI ? 1 : N * 16];
@@ -77,17 +81,18 @@ __global__ __launch_bounds__(WAVE, (N > 32 && EXACT && !H16) ? 1 : 2) void admm_
     float *b = b_lds + lane;     // b[i * WAVE]
 
     // ---- gain rows of this lane -----------------------------------------------------------------
+    const float *mats = PM ? M.mats + (size_t)inst_a * M.mats_stride : P.mats;
     RowGains<NX, NU> G;
-    G.load(P.mats, r16);
+    G.load(mats, r16);
     // optional terms (OPT): R(r) on the input rows, coeff_d2p(r, m) on the state rows (pack_gains), this lane's Uref column
     [[maybe_unused]] float rrow = 0.f, CD[NU];
     [[maybe_unused]] const bool uref_on = OPT && P.uref != nullptr, d2p_on = OPT && P.en_d2p != 0;
     [[maybe_unused]] const int uref_off = inst_a * (int)P.uref_inst_stride + r16;
     if constexpr (OPT)
     {
-        rrow = P.mats[(3 * NX + 2 * NU + 1) * 16 + r16];
+        rrow = mats[(3 * NX + 2 * NU + 1) * 16 + r16];
 #pragma unroll
-        for (int m = 0; m < NU; m++) CD[m] = P.mats[(3 * NX + 2 * NU + 2 + m) * 16 + r16];
+        for (int m = 0; m < NU; m++) CD[m] = mats[(3 * NX + 2 * NU + 2 + m) * 16 + r16];
     }
     // cost term of step i as lin_cost() wants it: -(Xref_i .* Q) on the state rows; on the input rows -0 (so that r = -rho (znew - y) keeps the
     // sign of a zero difference) or, with the Uref term on, -(Uref_i .* R)   (admm.cpp:79-82)
@@ -115,7 +120,7 @@ __global__ __launch_bounds__(WAVE, (N > 32 && EXACT && !H16) ? 1 : 2) void admm_
     const bool zdual = cold || (P.duals_zero != 0);
     float xrN = 0.f; // Xref_{N-1}(r)
     {
-        const float qrow = P.mats[(2 * NX + 2 * NU) * 16 + r16]; // Q(r) on x rows, 0 elsewhere
+        const float qrow = mats[(2 * NX + 2 * NU) * 16 + r16]; // Q(r) on x rows, 0 elsewhere
 #pragma unroll
         for (int i = 0; i < N; i++)
         {
@@ -139,7 +144,7 @@ __global__ __launch_bounds__(WAVE, (N > 32 && EXACT && !H16) ? 1 : 2) void admm_
     float x0 = ldw<H16>(P.xu, rowbase); // x.col(0) on x rows (u rows hold stale u_0, never used as x)
 
     // -(Xref_{N-1}^T Pinf): constant during a solve (admm.cpp:83)
-    float pterm = terminal_term<NX, NU, EXACT, H16>(P.mats, r16, xrN);
+    float pterm = terminal_term<NX, NU, EXACT, H16>(mats, r16, xrN);
 
     int st = TINY_STATUS_UNSOLVED_, itn = 1; // admm.cpp:114-115
     float r_ps = 0.f, r_pi = 0.f, r_ds = 0.f, r_di = 0.f;
@@ -273,7 +278,7 @@ __global__ __launch_bounds__(WAVE, (N > 32 && EXACT && !H16) ? 1 : 2) void admm_
         if (P.u0_traj && valid && is_u) P.u0_traj[((long long)ms * P.batch + inst) * NU + (r16 - NX)] = sv0;
         if constexpr (MPC) x0 = plant_step<NX, NU>(G, sv0); // x_1 = Adyn x0 + Bdyn u_0 (:110), the plant kernel's arithmetic
         wstart += P.window_advance;
-        const float qrow = P.mats[(2 * NX + 2 * NU) * 16 + r16];
+        const float qrow = mats[(2 * NX + 2 * NU) * 16 + r16];
 #pragma unroll
         for (int i = 0; i < N; i++)
         {
@@ -289,7 +294,7 @@ __global__ __launch_bounds__(WAVE, (N > 32 && EXACT && !H16) ? 1 : 2) void admm_
             c[i] = is_x ? cqn : pd[i]; // d of the workspace = d of the last executed backward sweep
             a[i] = 0.f;                // y = g = 0 (:106-107)
         }
-        if (P.xref_mode == 1) pterm = terminal_term<NX, NU, EXACT, H16>(P.mats, r16, xrN);
+        if (P.xref_mode == 1) pterm = terminal_term<NX, NU, EXACT, H16>(mats, r16, xrN);
     }
     }
 
@@ -350,6 +355,19 @@ __global__ __launch_bounds__(WAVE, (N > 32 && EXACT && !H16) ? 1 : 2) void admm_
             if (!solved) atomicAdd(P.n_unsolved, 1);
         }
     }
+}
+
+template <int NX, int NU, int N, bool EXACT, bool H16, bool MPC = false, bool BPI = false, bool D32 = false, bool OPT = false>
+__global__ __launch_bounds__(WAVE, (N > 32 && EXACT && !H16) ? 1 : 2) void admm_rowlane_kernel(const RowParams P)
+{
+    rowlane_body<NX, NU, N, EXACT, H16, MPC, BPI, D32, OPT, false>(P, ModelParams{});
+}
+
+// per-instance models (tiny_batch_set_models): fp32 storage, shared or per-instance bounds, one solve or the on-chip closed loop
+template <int NX, int NU, int N, bool EXACT, bool MPC, bool BPI>
+__global__ __launch_bounds__(WAVE, (N > 32 && EXACT) ? 1 : 2) void admm_rowlane_pm_kernel(const RowParams P, const ModelParams M)
+{
+    rowlane_body<NX, NU, N, EXACT, false, MPC, BPI, false, false, true>(P, M);
 }
 
 bool rowlane_supported(int nx, int nu, int N)
@@ -427,6 +445,25 @@ hipError_t launch_admm_rowlane(int nx, int nu, int N, bool exact, bool h16, cons
         return hipGetLastError();                                                                           \
     }
     TINY_FOR_EACH_ROWLANE(TINY_ROWLANE_DISPATCH)
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_admm_rowlane_pm(int nx, int nu, int N, bool exact, const RowParams &P, const ModelParams &M, hipStream_t stream)
+{
+    const int nblocks = (P.batch + 3) / 4;
+    const bool mpc = P.mpc_steps > 1, bpi = P.bounds_inst_stride != 0;
+    if (P.dual32 || (mpc && bpi) || P.uref != nullptr || P.en_d2p || !M.mats || !M.rho) return hipErrorInvalidValue;
+#define TINY_ROWLANE_PM_LAUNCH(NX, NU, NN, EX, MP, BP) \
+    hipLaunchKernelGGL((admm_rowlane_pm_kernel<NX, NU, NN, EX, MP, BP>), dim3(nblocks), dim3(WAVE), 0, stream, P, M)
+#define TINY_ROWLANE_PM_DISPATCH(NX, NU, NN)                                                                \
+    if (nx == NX && nu == NU && N == NN)                                                                    \
+    {                                                                                                       \
+        if (mpc) { if (exact) TINY_ROWLANE_PM_LAUNCH(NX, NU, NN, true, true, false); else TINY_ROWLANE_PM_LAUNCH(NX, NU, NN, false, true, false); } \
+        else if (bpi) { if (exact) TINY_ROWLANE_PM_LAUNCH(NX, NU, NN, true, false, true); else TINY_ROWLANE_PM_LAUNCH(NX, NU, NN, false, false, true); } \
+        else { if (exact) TINY_ROWLANE_PM_LAUNCH(NX, NU, NN, true, false, false); else TINY_ROWLANE_PM_LAUNCH(NX, NU, NN, false, false, false); } \
+        return hipGetLastError();                                                                           \
+    }
+    TINY_FOR_EACH_ROWLANE(TINY_ROWLANE_PM_DISPATCH)
     return hipErrorInvalidValue;
 }
 

@@ -213,12 +213,10 @@ __global__ void dual_width_kernel(const float *__restrict__ src, float *__restri
 // test_plant_step_bit_exact_vs_compiled_reference): dst = Adyn*x0, then dst += Bdyn*u0; a product whose rows and depth are both >= 8 takes the column-major
 // GEMV kernel (row accumulator starting at +0, products added in ascending column order), a smaller one the lazy product
 // (sequential from the first product for the nx % 4 == 0 classes this library serves).
-__global__ void plant_step_kernel(float *__restrict__ x0buf, float *__restrict__ xarr, const float *__restrict__ uarr,
-                                  const float *__restrict__ A, const float *__restrict__ Bm, int *__restrict__ wstart,
-                                  int window_advance, int batch, int layout, Geo g, int h16)
+__device__ __forceinline__ void plant_step_one(int b, float *__restrict__ x0buf, float *__restrict__ xarr, const float *__restrict__ uarr,
+                                               const float *__restrict__ A, const float *__restrict__ Bm, int *__restrict__ wstart,
+                                               int window_advance, int layout, Geo g, int h16)
 {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= batch) return;
     const int nx = g.nx, nu = g.nu;
     const float *x0 = x0buf + (long long)b * nx;
     const bool gemv_a = nx >= 8, gemv_b = nx >= 8 && nu >= 8;
@@ -239,6 +237,101 @@ __global__ void plant_step_kernel(float *__restrict__ x0buf, float *__restrict__
         put_elem(xarr, idx_of(layout, g, 0, b, 0, i), xn[i], h16);
     }
     if (wstart && window_advance) wstart[b] += window_advance;
+}
+
+__global__ void plant_step_kernel(float *__restrict__ x0buf, float *__restrict__ xarr, const float *__restrict__ uarr,
+                                  const float *__restrict__ A, const float *__restrict__ Bm, int *__restrict__ wstart,
+                                  int window_advance, int batch, int layout, Geo g, int h16)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= batch) return;
+    plant_step_one(b, x0buf, xarr, uarr, A, Bm, wstart, window_advance, layout, g, h16);
+}
+
+// ... with per-instance models: the instance's own Adyn / Bdyn from its record (Kinf | Pinf | Quu_inv | AmBKt | Adyn | Bdyn | Q, pm_gen_floats apart)
+__global__ void plant_step_pm_kernel(float *__restrict__ x0buf, float *__restrict__ xarr, const float *__restrict__ uarr,
+                                     const float *__restrict__ recs, int *__restrict__ wstart, int window_advance, int batch, int layout, Geo g, int h16)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= batch) return;
+    const int nx = g.nx, nu = g.nu;
+    const float *r = recs + (size_t)b * pm_gen_floats(nx, nu) + nu * nx + nx * nx + nu * nu + nx * nx;
+    plant_step_one(b, x0buf, xarr, uarr, r, r + nx * nx, wstart, window_advance, layout, g, h16);
+}
+
+// Per-instance models (tiny_batch_set_models_device): the caller's eight [B] arrays into one record per instance in the run-time-dimension kernel's
+// order Kinf | Pinf | Quu_inv | AmBKt | Adyn | Bdyn | Q (plain copies), rho into its own array
+__global__ void models_gather_kernel(const float *__restrict__ rho, const float *__restrict__ K, const float *__restrict__ Pf, const float *__restrict__ Qi,
+                                     const float *__restrict__ Am, const float *__restrict__ A, const float *__restrict__ Bm, const float *__restrict__ Q,
+                                     float *__restrict__ dst, float *__restrict__ dst_rho, int batch, int nx, int nu)
+{
+    const int G = pm_gen_floats(nx, nu);
+    const long long total = (long long)batch * G;
+    const int sz[7] = {nu * nx, nx * nx, nu * nu, nx * nx, nx * nx, nx * nu, nx};
+    const float *src[7] = {K, Pf, Qi, Am, A, Bm, Q};
+    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x)
+    {
+        const long long b = e / G;
+        int o = (int)(e % G), k = 0;
+        while (o >= sz[k]) o -= sz[k++];
+        dst[e] = src[k][b * sz[k] + o];
+        if (o == 0 && k == 0) dst_rho[b] = rho[b];
+    }
+}
+
+// ... and from those records the gain rows of the 16-lane kernel, element for element what pack_gains writes for one shared model (rows 0 .. 3nx + 2nu:
+// M1, M2, M3, M45, Q, PT; the optional-term rows are not instantiated with per-instance models).  fast = 1: the fma form (u rows of M1 and x rows of M45
+// hold -K; the exact form holds +K and the kernel negates the sum)
+__global__ void models_pack_row_kernel(const float *__restrict__ recs, float *__restrict__ dst, int batch, int nx, int nu, int fast)
+{
+    const int G = pm_gen_floats(nx, nu), R = pm_row_floats(nx, nu);
+    const long long total = (long long)batch * R;
+    const float sg = fast ? -1.f : 1.f;
+    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x)
+    {
+        const long long b = e / R;
+        const int o = (int)(e % R), reg = o / 16, r = o % 16;
+        const float *K = recs + b * G, *Pf = K + nu * nx, *Qi = Pf + nx * nx, *Am = Qi + nu * nu, *A = Am + nx * nx, *Bm = A + nx * nx, *Q = Bm + nx * nu;
+        const bool isx = r < nx, isu = r >= nx && r < nx + nu;
+        const int mr = r - nx;
+        float v = 0.f;
+        if (reg < nx) v = isx ? A[reg * nx + r] : (isu ? sg * K[reg * nu + mr] : 0.f); // M1: A(r,k) | K(m,k) (exact), -K(m,k) (fast)
+        else if (reg < nx + nu) v = isx ? Bm[(reg - nx) * nx + r] : 0.f;                // M2: B(r,m)
+        else if (reg < 2 * nx + nu)
+        {
+            const int k = reg - nx - nu;                                                // M3: AmBKt(r,k) | B(k,m)
+            v = isx ? Am[k * nx + r] : (isu ? Bm[mr * nx + k] : 0.f);
+        }
+        else if (reg < 2 * nx + 2 * nu)
+        {
+            const int mm = reg - 2 * nx - nu;                                           // M45: K(m,r) (exact), -K(m,r) (fast) | Quu_inv(mr,m)
+            v = isx ? sg * K[r * nu + mm] : (isu ? Qi[mm * nu + mr] : 0.f);
+        }
+        else if (reg == 2 * nx + 2 * nu) v = isx ? Q[r] : 0.f;                          // Q(r)
+        else v = isx ? Pf[r * nx + (reg - 2 * nx - 2 * nu - 1)] : 0.f;                  // PT[k]: Pinf(k,r)
+        dst[e] = v;
+    }
+}
+
+// tiny_batch_set_systems: fp64 systems and their Riccati caches into the fp32 arrays of tiny_batch_set_models_device, with the conventions of
+// problems.with_cache(): rho, Kinf ..., Adyn, Bdyn cast, Q = (float)(Q + rho) formed in fp64
+__global__ void systems_to_models_kernel(const double *__restrict__ rho, const double *__restrict__ K, const double *__restrict__ Pf, const double *__restrict__ Qi,
+                                         const double *__restrict__ Am, const double *__restrict__ A, const double *__restrict__ Bm, const double *__restrict__ Q,
+                                         float *__restrict__ dst, int batch, int nx, int nu)
+{
+    // dst: rho [B] | Kinf | Pinf | Quu_inv | AmBKt | Adyn | Bdyn | Q, each [B][...]
+    const int sz[8] = {1, nu * nx, nx * nx, nu * nu, nx * nx, nx * nx, nx * nu, nx};
+    const double *src[8] = {rho, K, Pf, Qi, Am, A, Bm, Q};
+    const long long total = (long long)batch * (1 + pm_gen_floats(nx, nu));
+    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x)
+    {
+        long long o = e;
+        int k = 0;
+        while (o >= (long long)batch * sz[k]) o -= (long long)batch * sz[k++];
+        double v = src[k][o];
+        if (k == 7) v = v + rho[o / nx];
+        dst[e] = (float)v;
+    }
 }
 
 // per-instance bounds table of the ROW layout: dst[b][step][r] = {min(lo, hi), hi}, +-inf where a bound is disabled or the
@@ -418,6 +511,12 @@ struct TinyBatch
     int last_dispatch = 0;        // what the most recent solve launch did: 0 index order, 1 predicted longest first, 2 the caller's order, 3 longest first by the previous solve's counts
     bool iter_history = false;    // iter[] holds the counts of a solve of THIS workspace's instances (not a reset, not an upload): the history order's key
     bool closed_loop_run = false; // inside tiny_batch_mpc_run_*(steps > 1): the auto choice keeps the kernel with the on-chip loop
+    // per-instance models (tiny_batch_set_models): one record per instance in the run-time-dimension kernel's form ([batch][pm_gen_floats]: Kinf | Pinf |
+    // Quu_inv | AmBKt | Adyn | Bdyn | Q, which is also what the plant step reads), rho [batch]; the 16-lane kernel's two forms of the gain rows
+    // ([batch][pm_row_floats], [0] exact, [1] fma) are packed from the records on the device when a launch first needs one
+    bool pm = false;
+    float *pm_src = nullptr, *pm_rho = nullptr, *pm_row[2] = {};
+    bool pm_row_dirty[2] = {true, true};
     bool h16 = false; // ROW-layout arrays, Xref and bounds stored as IEEE binary16 (tiny_batch_set_storage)
     bool dual32 = false; // with h16: the duals pair gy IS fp32 right now (the state of the array)
     bool dual32_pref = false;   // tiny_batch_set_storage(tb, 16): fp32 duals wherever the kernel a call resolves to implements them, 16-bit duals elsewhere
@@ -947,8 +1046,43 @@ int settle_dual_width(TinyBatch *tb, bool kernel_keeps_fp32_duals)
 }
 bool family_keeps_fp32_duals(int fam) { return fam == 0 || fam == 4; }
 
+// per-instance models: the unrolled 16-lane kernel where (nx, nu, N) is instantiated, the run-time-dimension kernel otherwise (both read a gain
+// record per instance).  Every other kernel keeps ONE gain table for the whole launch — tile16's MFMA A operand is one gain matrix for all sixteen
+// columns, the streaming and wave kernels stage theirs once per workgroup — and is never chosen.
+int resolve_variant_pm(TinyBatch *tb, int *out)
+{
+    int v = tb->variant;
+    if (tb->h16)
+        return fail(TINY_BATCH_EUNSUPPORTED, "per-instance models (tiny_batch_set_models) are implemented for fp32 storage only: tiny_batch_set_storage(tb, 32) or tiny_batch_clear_models()");
+    if (tb->en_uref || tb->en_d2p)
+        return fail(TINY_BATCH_EUNSUPPORTED, "the optional Uref / coeff_d2p terms are not implemented with per-instance models (tiny_batch_set_optional_terms(tb, 0, 0) or tiny_batch_clear_models())");
+    if (v == VAR_STREAM)
+        return fail(TINY_BATCH_EUNSUPPORTED, "the streaming MFMA kernel (variant 1) holds one gain matrix for the whole launch and cannot serve per-instance models");
+    if (v == VAR_AUTO)
+    {
+        if (!tb->row_dims_ok && !tb->generic_ok)
+            return fail(TINY_BATCH_EUNSUPPORTED, "per-instance models need the unrolled 16-lane kernel (an instantiated nx, nu, N) or the run-time-dimension exact kernel "
+                                                 "(nx, nu each <= 4 or a multiple of 4); nx=%d nu=%d N=%d has neither", tb->nx, tb->nu, tb->N);
+        v = tb->row_dims_ok ? VAR_ROW_EXACT : VAR_GENERIC;
+    }
+    if (v == VAR_ROW_EXACT || v == VAR_ROW_FAST)
+    {
+        if (!tb->row_dims_ok)
+            return fail(TINY_BATCH_EUNSUPPORTED, "with per-instance models the row variants run on the unrolled 16-lane kernel only, which has no instantiation for nx=%d nu=%d N=%d "
+                                                 "(variant 4, the run-time-dimension exact kernel, serves it)", tb->nx, tb->nu, tb->N);
+        if (tb->row_family_forced >= 0 && tb->row_family_forced != 0)
+            return fail(TINY_BATCH_EUNSUPPORTED, "the forced row kernel (tiny_batch_set_row_kernel) keeps one gain table for the whole launch and cannot serve per-instance models "
+                                                 "(tile16: its MFMA A operand is one gain matrix for all 16 columns); only the 16-lane kernel (1) or auto (0) can");
+    }
+    if (v == VAR_GENERIC && !tb->generic_ok)
+        return fail(TINY_BATCH_EUNSUPPORTED, "the run-time-dimension exact kernel (variant 4) needs nx, nu each <= 4 or a multiple of 4 (nx=%d nu=%d)", tb->nx, tb->nu);
+    *out = v;
+    return 0;
+}
+
 int resolve_variant(TinyBatch *tb, int *out)
 {
+    if (tb->pm) return resolve_variant_pm(tb, out);
     int v = tb->variant;
     // row variants: register-resident kernel when (nx,nu,N) is instantiated, else the any-N row kernel with the state in HBM
     // per-instance bounds: the streaming row kernel and the wave kernel read them per instance; the register-resident
@@ -1038,6 +1172,7 @@ bool tile48_pays(int batch, int n_cu)
 
 int row_family(const TinyBatch *tb)
 {
+    if (tb->pm) return 0; // per-instance models: the unrolled 16-lane kernel (resolve_variant_pm refuses every other row kernel)
     // one wavefront per instance: state on chip where the horizon fits (admm_waveres.hip, 6), else streamed through HBM (admm_wave.hip, 3)
     // (7: sixteen instances per workgroup on the matrix cores, admm_tile48.hip: fp32 storage)
     if (tb->wave_ok)
@@ -1109,7 +1244,12 @@ void update_kname(TinyBatch *tb)
     if (resolve_variant(tb, &v)) { tb->kname = "unsupported"; g_err = keep; return; }
     const bool d32 = tb->h16 && (tb->dual32_forced ? tb->dual32 : (tb->dual32_pref && !tile_variant(v) && family_keeps_fp32_duals(row_family(tb))));
     const char *ar = v == VAR_ROW_EXACT ? "exact" : "fast", *sto = tb->h16 ? (d32 ? ",h16d" : ",h16") : "";
-    if (v == VAR_STREAM) snprintf(nm, sizeof nm, "stream<%d,%d>", tb->NXC, tb->NUC);
+    if (tb->pm) // per-instance models: the kernels that read a gain record per instance, marked ",pm"
+    {
+        if (v == VAR_GENERIC) snprintf(nm, sizeof nm, "generic<%d,%d,exact,pm>", tb->nx, tb->nu);
+        else snprintf(nm, sizeof nm, "rowlane<%d,%d,%d,%s,pm>", tb->nx, tb->nu, tb->N, ar);
+    }
+    else if (v == VAR_STREAM) snprintf(nm, sizeof nm, "stream<%d,%d>", tb->NXC, tb->NUC);
     else if (v == VAR_GENERIC) snprintf(nm, sizeof nm, "generic<%d,%d,exact>", tb->nx, tb->nu);
     else if (row_family(tb) == 0) snprintf(nm, sizeof nm, "rowlane<%d,%d,%d,%s%s>", tb->nx, tb->nu, tb->N, ar, sto);
     else if (row_family(tb) == 1) snprintf(nm, sizeof nm, "rowloop<%d,%d,%s%s>", tb->nx, tb->nu, ar, sto);
@@ -1159,6 +1299,8 @@ int check_optional_terms(const TinyBatch *tb)
 // One of the six step functions of admm.hpp:10-18 over the whole batch (admm_steps.hip).
 int run_step(TinyBatch *tb, int fn, int *converged_host, int *n_true)
 {
+    if (tb->pm)
+        return fail(TINY_BATCH_EUNSUPPORTED, "the six single-function step kernels read one shared model: not available with per-instance models (tiny_batch_clear_models())");
     if (!tb->have_cache || !tb->have_dyn || !tb->have_settings)
         return fail(TINY_BATCH_ENOTREADY, "set_cache, set_dynamics and set_settings must be called first");
     if (!tb->rowmath_ok)
@@ -1189,11 +1331,35 @@ int run_step(TinyBatch *tb, int fn, int *converged_host, int *n_true)
     return 0;
 }
 
+// per-instance models: the 16-lane kernel's gain rows in the form variant v computes in, packed from the records when they changed (the run-time-dimension
+// kernel reads the records themselves)
+int pack_models(TinyBatch *tb, int v)
+{
+    if (v != VAR_ROW_EXACT && v != VAR_ROW_FAST) return 0;
+    const int f = v == VAR_ROW_FAST ? 1 : 0;
+    if (!tb->pm_row_dirty[f]) return 0;
+    const long long n = (long long)tb->batch * pm_row_floats(tb->nx, tb->nu);
+    if (!tb->pm_row[f]) HIP_TRY(guarded_malloc((void **)&tb->pm_row[f], (size_t)n * sizeof(float)));
+    hipLaunchKernelGGL(models_pack_row_kernel, dim3(grid_for(n)), dim3(256), 0, tb->stream, tb->pm_src, tb->pm_row[f], tb->batch, tb->nx, tb->nu, f);
+    HIP_TRY(hipGetLastError());
+    tb->pm_row_dirty[f] = false;
+    return 0;
+}
+
+ModelParams model_params(const TinyBatch *tb, int v)
+{
+    ModelParams M;
+    M.rho = tb->pm_rho;
+    if (v == VAR_GENERIC) { M.mats = tb->pm_src; M.mats_stride = (unsigned)pm_gen_floats(tb->nx, tb->nu); }
+    else { M.mats = tb->pm_row[v == VAR_ROW_FAST ? 1 : 0]; M.mats_stride = (unsigned)pm_row_floats(tb->nx, tb->nu); }
+    return M;
+}
+
 // everything a solve needs that may allocate, copy or synchronise (not capturable in a hipGraph)
 int prepare_solve(TinyBatch *tb, int *variant)
 {
-    if (!tb->have_cache || !tb->have_dyn || !tb->have_settings)
-        return fail(TINY_BATCH_ENOTREADY, "tiny_batch_solve: set_cache, set_dynamics and set_settings must be called first");
+    if (!(tb->pm || (tb->have_cache && tb->have_dyn)) || !tb->have_settings)
+        return fail(TINY_BATCH_ENOTREADY, "tiny_batch_solve: set_cache, set_dynamics (or set_models) and set_settings must be called first");
     for (int k = 0; k < 4; k += 2)
     {
         const InputArr &lo = tb->in_bnd[k], &hi = tb->in_bnd[k + 1];
@@ -1205,7 +1371,8 @@ int prepare_solve(TinyBatch *tb, int *variant)
     TRY(set_device(tb));
     int v = 0;
     TRY(resolve_variant(tb, &v));
-    if (tb->gains_dirty) TRY(pack_gains(tb));
+    if (tb->pm) TRY(pack_models(tb, v));
+    else if (tb->gains_dirty) TRY(pack_gains(tb));
     // (whatever the mode says NOW: a launch sequence enqueued after one prepare_solve — the captured graph of tiny_batch_mpc_run_async — gains a history with its
     //  first solve, and its second one is then dispatched by it)
     if (!tb->order_buf && tb->bpad4 / 4 >= kDispatchMinGroups)
@@ -1238,7 +1405,8 @@ int enqueue_solve(TinyBatch *tb, int v, bool record_events)
     // longest-first dispatch (dispatch_order.hip): predictor sweep + bucket sort ahead of the register-resident 16-lane kernels;
     // pays off only when the launch is several rounds of waves deep
     const int fam_l = layout == LAYOUT_ROW ? row_family(tb) : -1;
-    const bool predicted_order = layout == LAYOUT_ROW && dispatch_effective(tb) == 1 && !tb->order_dev && (fam_l == 0 || fam_l == 1 || fam_l == 5) && !tb->dual32 &&
+    // (per-instance models: the predictor sweep reads the shared fma gains, which are unset or stale there — such a launch keeps index order)
+    const bool predicted_order = layout == LAYOUT_ROW && dispatch_effective(tb) == 1 && !tb->pm && !tb->order_dev && (fam_l == 0 || fam_l == 1 || fam_l == 5) && !tb->dual32 &&
                                  tb->bpad4 / 4 >= kDispatchMinGroups && tb->max_iter > 1 && tb->order_buf;
     // [0] unsolved count, [1] tile queue of admm_tile16.hip: zeroed by the sort kernel of the predicted order where that runs (one stream node less)
     const bool history_order = layout == LAYOUT_ROW && dispatch_effective(tb) == 2 && !tb->order_dev && (fam_l == 0 || fam_l == 1 || fam_l == 5) &&
@@ -1280,7 +1448,9 @@ int enqueue_solve(TinyBatch *tb, int v, bool record_events)
         P.xref_table = tb->tab_tile; P.xref_start = tb->xref_start; P.table_rows = tb->table_rows;
         P.res = tb->res; P.status = tb->status; P.iter = tb->iter; P.n_unsolved = tb->n_unsolved;
         P.opnd = tb->opnd; P.qvec = tb->qvec;
-        e = v == VAR_GENERIC ? launch_admm_generic(P, tb->gen_mats, tb->NXC, tb->NUC, tb->stream) : launch_admm_stream(tb->NXC, tb->NUC, P, tb->stream);
+        e = v == VAR_GENERIC ? (tb->pm ? launch_admm_generic_pm(P, model_params(tb, v), tb->NXC, tb->NUC, tb->stream)
+                                       : launch_admm_generic(P, tb->gen_mats, tb->NXC, tb->NUC, tb->stream))
+                             : launch_admm_stream(tb->NXC, tb->NUC, P, tb->stream);
     }
     else
     {
@@ -1293,7 +1463,8 @@ int enqueue_solve(TinyBatch *tb, int v, bool record_events)
         if (P.dual32 && fam != 0 && fam != 4)
             return fail(TINY_BATCH_EUNSUPPORTED, "fp16 storage with fp32 duals runs on the register-resident 16-lane and quad kernels only "
                                                  "(batch-shared bounds, no optional terms, no forced row kernel)");
-        e = fam == 0   ? launch_admm_rowlane(tb->nx, tb->nu, tb->N, v == VAR_ROW_EXACT, tb->h16, P, tb->stream)
+        e = fam == 0   ? (tb->pm ? launch_admm_rowlane_pm(tb->nx, tb->nu, tb->N, v == VAR_ROW_EXACT, P, model_params(tb, v), tb->stream)
+                                 : launch_admm_rowlane(tb->nx, tb->nu, tb->N, v == VAR_ROW_EXACT, tb->h16, P, tb->stream))
             : fam == 1 ? launch_admm_rowloop(tb->nx, tb->nu, v == VAR_ROW_EXACT, tb->h16, P, tb->stream)
             : fam == 3 ? launch_admm_wavestream(tb->nx, tb->nu, P, tb->stream)
             : fam == 4 ? launch_admm_quadlane(tb->N, v == VAR_ROW_EXACT, tb->h16, P, tb->stream)
@@ -1323,6 +1494,13 @@ int launch_solve(TinyBatch *tb)
 
 int enqueue_plant_step(TinyBatch *tb, int window_advance)
 {
+    if (tb->pm)
+    {
+        hipLaunchKernelGGL(plant_step_pm_kernel, dim3((tb->batch + 127) / 128), dim3(128), 0, tb->stream, tb->x0buf, work_ptr(tb, TINY_ARR_X), work_ptr(tb, TINY_ARR_U),
+                           tb->pm_src, tb->xref_mode == 1 ? tb->xref_start : nullptr, window_advance, tb->batch, tb->layout, geo(tb), h16_of(tb, tb->layout));
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
     hipLaunchKernelGGL(plant_step_kernel, dim3((tb->batch + 127) / 128), dim3(128), 0, tb->stream, tb->x0buf,
                        work_ptr(tb, TINY_ARR_X), work_ptr(tb, TINY_ARR_U), tb->dA, tb->dB,
                        tb->xref_mode == 1 ? tb->xref_start : nullptr, window_advance, tb->batch, tb->layout, geo(tb),
@@ -1436,6 +1614,7 @@ void tiny_batch_destroy(TinyBatch *tb)
     (void)guarded_free(tb->tab_tile); (void)guarded_free(tb->tab_row); (void)guarded_free(tb->tab_row_h); (void)guarded_free(tb->xref_start);
     (void)guarded_free(tb->res); (void)guarded_free(tb->status); (void)guarded_free(tb->iter); (void)guarded_free(tb->n_unsolved);
     (void)guarded_free(tb->opnd); (void)guarded_free(tb->qvec); (void)guarded_free(tb->gen_mats); (void)guarded_free(tb->mats_exact); (void)guarded_free(tb->mats_fast);
+    (void)guarded_free(tb->pm_src); (void)guarded_free(tb->pm_rho); (void)guarded_free(tb->pm_row[0]); (void)guarded_free(tb->pm_row[1]);
     (void)guarded_free(tb->dA); (void)guarded_free(tb->dB); (void)guarded_free(tb->x0buf); (void)guarded_free(tb->staging); (void)guarded_free(tb->conv_dev);
     if (tb->graph_exec) (void)hipGraphExecDestroy(tb->graph_exec);
     if (tb->own_stream) (void)hipStreamDestroy(tb->own_stream);
@@ -1487,6 +1666,172 @@ int tiny_batch_set_dynamics(TinyBatch *tb, const float *Adyn, const float *Bdyn,
     tb->gains_dirty = true;
     invalidate_graph(tb);
     return 0;
+}
+
+// ---- per-instance models ----------------------------------------------------------------------------------------------------
+int tiny_batch_set_models_device(TinyBatch *tb, const float *d_rho, const float *d_Kinf, const float *d_Pinf, const float *d_Quu_inv,
+                                 const float *d_AmBKt, const float *d_Adyn, const float *d_Bdyn, const float *d_Q)
+{
+    CHECK_TB(tb); CHECK_PTR(d_rho); CHECK_PTR(d_Kinf); CHECK_PTR(d_Pinf); CHECK_PTR(d_Quu_inv); CHECK_PTR(d_AmBKt); CHECK_PTR(d_Adyn); CHECK_PTR(d_Bdyn); CHECK_PTR(d_Q);
+    TRY(set_device(tb));
+    invalidate_graph(tb); // the record pointers and the kernel choice are baked into a captured graph
+    const long long n = (long long)tb->batch * pm_gen_floats(tb->nx, tb->nu);
+    if (!tb->pm_src) HIP_TRY(guarded_malloc((void **)&tb->pm_src, (size_t)n * sizeof(float)));
+    if (!tb->pm_rho) HIP_TRY(guarded_malloc((void **)&tb->pm_rho, (size_t)tb->batch * sizeof(float)));
+    hipLaunchKernelGGL(models_gather_kernel, dim3(grid_for(n)), dim3(256), 0, tb->stream, d_rho, d_Kinf, d_Pinf, d_Quu_inv, d_AmBKt, d_Adyn, d_Bdyn, d_Q,
+                       tb->pm_src, tb->pm_rho, tb->batch, tb->nx, tb->nu);
+    HIP_TRY(hipGetLastError());
+    tb->pm = true;
+    tb->pm_row_dirty[0] = tb->pm_row_dirty[1] = true; // the packed rows follow the records
+    update_kname(tb);
+    return 0;
+}
+
+namespace
+{
+// the [B] arrays of tiny_batch_set_models, one after the other in one buffer of floats: rho | Kinf | Pinf | Quu_inv | AmBKt | Adyn | Bdyn | Q
+int set_models_packed(TinyBatch *tb, const float *d)
+{
+    const size_t B = tb->batch, nx = tb->nx, nu = tb->nu;
+    const float *p = d;
+    const float *rho = p; p += B;
+    const float *K = p; p += B * nu * nx;
+    const float *Pf = p; p += B * nx * nx;
+    const float *Qi = p; p += B * nu * nu;
+    const float *Am = p; p += B * nx * nx;
+    const float *A = p; p += B * nx * nx;
+    const float *Bm = p; p += B * nx * nu;
+    return tiny_batch_set_models_device(tb, rho, K, Pf, Qi, Am, A, Bm, p);
+}
+} // namespace
+
+int tiny_batch_set_models(TinyBatch *tb, const float *rho, const float *Kinf, const float *Pinf, const float *Quu_inv, const float *AmBKt,
+                          const float *Adyn, const float *Bdyn, const float *Q)
+{
+    CHECK_TB(tb); CHECK_PTR(rho); CHECK_PTR(Kinf); CHECK_PTR(Pinf); CHECK_PTR(Quu_inv); CHECK_PTR(AmBKt); CHECK_PTR(Adyn); CHECK_PTR(Bdyn); CHECK_PTR(Q);
+    TRY(set_device(tb));
+    const size_t B = tb->batch, nx = tb->nx, nu = tb->nu;
+    const float *src[8] = {rho, Kinf, Pinf, Quu_inv, AmBKt, Adyn, Bdyn, Q};
+    const size_t sz[8] = {B, B * nu * nx, B * nx * nx, B * nu * nu, B * nx * nx, B * nx * nx, B * nx * nu, B * nx};
+    size_t total = 0;
+    for (size_t z : sz) total += z;
+    float *d = nullptr;
+    HIP_TRY(guarded_malloc((void **)&d, total * sizeof(float)));
+    int rc = 0;
+    size_t o = 0;
+    for (int k = 0; k < 8 && rc == 0; k++)
+    {
+        if (hipMemcpyAsync(d + o, src[k], sz[k] * sizeof(float), hipMemcpyHostToDevice, tb->stream) != hipSuccess) rc = fail(TINY_BATCH_EHIP, "hipMemcpyAsync failed");
+        o += sz[k];
+    }
+    if (rc == 0) rc = set_models_packed(tb, d);
+    if (hipStreamSynchronize(tb->stream) != hipSuccess && rc == 0) rc = fail(TINY_BATCH_EHIP, "hipStreamSynchronize failed");
+    (void)guarded_free(d);
+    return rc;
+}
+
+int tiny_batch_clear_models(TinyBatch *tb)
+{
+    CHECK_TB(tb);
+    if (!tb->pm) return 0;
+    TRY(set_device(tb));
+    invalidate_graph(tb);
+    HIP_TRY(hipStreamSynchronize(tb->stream)); // a launch still reading the records may be in flight
+    // the records and the packed rows are released (about 8 KB per quadrotor instance); a later set_models allocates them again
+    for (float **p : {&tb->pm_src, &tb->pm_rho, &tb->pm_row[0], &tb->pm_row[1]})
+    {
+        (void)guarded_free(*p);
+        *p = nullptr;
+    }
+    tb->pm_row_dirty[0] = tb->pm_row_dirty[1] = true;
+    tb->pm = false;
+    update_kname(tb);
+    return 0;
+}
+
+int tiny_batch_models_per_instance(TinyBatch *tb)
+{
+    CHECK_TB(tb);
+    return tb->pm ? 1 : 0;
+}
+
+int tiny_batch_riccati_device(int nx, int nu, int count, const double *d_A, const double *d_B, const double *d_Q, const double *d_R, const double *d_rho,
+                              double *d_Kinf, double *d_Pinf, double *d_Quu_inv, double *d_AmBKt, double *d_coeff_d2p, int *d_iters, void *hip_stream)
+{
+    if (nx < 1 || nx > 64 || nu < 1 || nu > 32) return fail(TINY_BATCH_EINVAL, "tiny_batch_riccati_device: need 1 <= nx <= 64 and 1 <= nu <= 32 (got %d, %d)", nx, nu);
+    if (count < 1) return fail(TINY_BATCH_EINVAL, "tiny_batch_riccati_device: count must be >= 1 (got %d)", count);
+    CHECK_PTR(d_A); CHECK_PTR(d_B); CHECK_PTR(d_Q); CHECK_PTR(d_R); CHECK_PTR(d_rho); CHECK_PTR(d_Kinf); CHECK_PTR(d_Pinf); CHECK_PTR(d_Quu_inv);
+    CHECK_PTR(d_AmBKt); CHECK_PTR(d_iters);
+    hipStream_t st = (hipStream_t)hip_stream;
+    // scratch for at most ~1 GiB of systems at a time, whole waves
+    const size_t per = (size_t)riccati_batch_doubles(nx, nu) * sizeof(double);
+    long long chunk = (long long)((1ull << 30) / per) / 64 * 64;
+    if (chunk < 64) chunk = 64;
+    if (chunk > (long long)(count + 63) / 64 * 64) chunk = (long long)(count + 63) / 64 * 64;
+    double *scratch = nullptr;
+    int *nfail = nullptr;
+    HIP_TRY(guarded_malloc((void **)&scratch, (size_t)chunk * per));
+    int rc = 0;
+    if (guarded_malloc((void **)&nfail, sizeof(int)) != hipSuccess || hipMemsetAsync(nfail, 0, sizeof(int), st) != hipSuccess)
+        rc = fail(TINY_BATCH_EHIP, "tiny_batch_riccati_device: allocation failed");
+    for (long long s0 = 0; s0 < count && rc == 0; s0 += chunk)
+    {
+        hipError_t e = launch_riccati_batch(nx, nu, (int)s0, (int)chunk, count, d_A, d_B, d_Q, d_R, d_rho, d_Kinf, d_Pinf, d_Quu_inv, d_AmBKt, d_coeff_d2p, d_iters,
+                                            scratch, nfail, st);
+        if (e != hipSuccess) rc = fail(TINY_BATCH_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
+    }
+    int h = 0;
+    if (rc == 0 && hipMemcpyAsync(&h, nfail, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess) rc = fail(TINY_BATCH_EHIP, "hipMemcpyAsync failed");
+    if (hipStreamSynchronize(st) != hipSuccess && rc == 0) rc = fail(TINY_BATCH_EHIP, "hipStreamSynchronize failed");
+    (void)guarded_free(scratch);
+    (void)guarded_free(nfail);
+    return rc ? rc : h;
+}
+
+int tiny_batch_set_systems(TinyBatch *tb, const double *A, const double *B, const double *Q, const double *R, const double *rho, int *iters)
+{
+    CHECK_TB(tb); CHECK_PTR(A); CHECK_PTR(B); CHECK_PTR(Q); CHECK_PTR(R); CHECK_PTR(rho);
+    TRY(set_device(tb));
+    const size_t Bn = tb->batch, nx = tb->nx, nu = tb->nu;
+    // inputs A | B | Q | R | rho, outputs Kinf | Pinf | Quu_inv | AmBKt, fp64; then the fp32 arrays of tiny_batch_set_models
+    const size_t in_sz[5] = {Bn * nx * nx, Bn * nx * nu, Bn * nx, Bn * nu, Bn};
+    const size_t out_sz[4] = {Bn * nu * nx, Bn * nx * nx, Bn * nu * nu, Bn * nx * nx};
+    const double *in[5] = {A, B, Q, R, rho};
+    size_t nd = 0;
+    for (size_t z : in_sz) nd += z;
+    for (size_t z : out_sz) nd += z;
+    const size_t nf = Bn * (1 + pm_gen_floats(tb->nx, tb->nu));
+    double *d = nullptr;
+    float *f = nullptr;
+    int *it = nullptr;
+    int rc = 0;
+    if (guarded_malloc((void **)&d, nd * sizeof(double)) != hipSuccess || guarded_malloc((void **)&f, nf * sizeof(float)) != hipSuccess ||
+        guarded_malloc((void **)&it, Bn * sizeof(int)) != hipSuccess)
+        rc = fail(TINY_BATCH_EHIP, "tiny_batch_set_systems: allocation failed");
+    double *dp[9];
+    size_t o = 0;
+    for (int k = 0; k < 5; k++) { dp[k] = d + o; o += in_sz[k]; }
+    for (int k = 0; k < 4; k++) { dp[5 + k] = d + o; o += out_sz[k]; }
+    for (int k = 0; k < 5 && rc == 0; k++)
+        if (hipMemcpyAsync(dp[k], in[k], in_sz[k] * sizeof(double), hipMemcpyHostToDevice, tb->stream) != hipSuccess) rc = fail(TINY_BATCH_EHIP, "hipMemcpyAsync failed");
+    int nfail = 0;
+    if (rc == 0)
+    {
+        nfail = tiny_batch_riccati_device(tb->nx, tb->nu, tb->batch, dp[0], dp[1], dp[2], dp[3], dp[4], dp[5], dp[6], dp[7], dp[8], nullptr, it, tb->stream);
+        if (nfail < 0) rc = nfail;
+    }
+    if (rc == 0 && iters && hipMemcpy(iters, it, Bn * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(TINY_BATCH_EHIP, "hipMemcpy failed");
+    if (rc == 0 && nfail > 0) rc = fail(TINY_BATCH_EINVAL, "tiny_batch_set_systems: the Riccati recursion is singular for %d of %zu systems (iters = -1); models unchanged", nfail, Bn);
+    if (rc == 0)
+    {
+        hipLaunchKernelGGL(systems_to_models_kernel, dim3(grid_for((long long)nf)), dim3(256), 0, tb->stream, dp[4], dp[5], dp[6], dp[7], dp[8], dp[0], dp[1], dp[2], f,
+                           tb->batch, tb->nx, tb->nu);
+        if (hipGetLastError() != hipSuccess) rc = fail(TINY_BATCH_EHIP, "kernel launch failed");
+    }
+    if (rc == 0) rc = set_models_packed(tb, f);
+    if (hipStreamSynchronize(tb->stream) != hipSuccess && rc == 0) rc = fail(TINY_BATCH_EHIP, "hipStreamSynchronize failed");
+    (void)guarded_free(d); (void)guarded_free(f); (void)guarded_free(it);
+    return rc;
 }
 
 // ---- the two terms the reference ships commented out (admm.cpp:20 and :79), off by default ------------------------------
@@ -1942,7 +2287,7 @@ int tiny_batch_mpc_run_traj_async(TinyBatch *tb, int steps, int window_advance, 
         const bool history_order = dispatch_effective(tb) == 2 && !tb->order_dev && (fam == 0 || fam == 5) && tb->bpad4 / 4 >= kDispatchMinGroups && tb->order_buf;
         // ... and a run that starts from a reset workspace by the predictor of its first, cold solve (which is also its longest: 22 iterations against 11): steps 0 - 19
         // of the tracking loop, makespan 1 522 iterations in index order, 1 299 by the predictor (by the true first-step counts 1 291; 16-lane kernel 2 336 -> 2 175)
-        const bool predicted_order = (tb->dispatch_mode == 1 || (tb->dispatch_mode == -1 && from_reset)) && !history_order && !tb->order_dev && (fam == 0 || fam == 5) && !tb->dual32 && tb->bpad4 / 4 >= kDispatchMinGroups &&
+        const bool predicted_order = (tb->dispatch_mode == 1 || (tb->dispatch_mode == -1 && from_reset)) && !history_order && !tb->pm && !tb->order_dev && (fam == 0 || fam == 5) && !tb->dual32 && tb->bpad4 / 4 >= kDispatchMinGroups &&
                                      tb->order_buf && tb->max_iter > 1;
         if (history_order)
         {
@@ -1960,7 +2305,8 @@ int tiny_batch_mpc_run_traj_async(TinyBatch *tb, int steps, int window_advance, 
         }
         else HIP_TRY(hipMemsetAsync(tb->n_unsolved, 0, 2 * sizeof(int), tb->stream)); // [0] unsolved count, [1] tile queue of admm_tile16.hip
         tb->last_dispatch = history_order ? 3 : predicted_order ? 1 : (P.order ? 2 : 0);
-        hipError_t e = fam == 0   ? launch_admm_rowlane(tb->nx, tb->nu, tb->N, v == VAR_ROW_EXACT, false, P, tb->stream)
+        hipError_t e = fam == 0   ? (tb->pm ? launch_admm_rowlane_pm(tb->nx, tb->nu, tb->N, v == VAR_ROW_EXACT, P, model_params(tb, v), tb->stream)
+                                            : launch_admm_rowlane(tb->nx, tb->nu, tb->N, v == VAR_ROW_EXACT, false, P, tb->stream))
                        : fam == 5 ? launch_admm_tile16(tb->N, v == VAR_ROW_EXACT, P, tb->stream, tb->n_cu)
                                   : launch_admm_quadlane(tb->N, v == VAR_ROW_EXACT, false, P, tb->stream);
         if (e != hipSuccess) return fail(TINY_BATCH_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
@@ -1981,8 +2327,9 @@ int tiny_batch_mpc_run_traj_async(TinyBatch *tb, int steps, int window_advance, 
     // (round 3: the signature is complete — rho, the shared / per-instance modes that set the strides, the bound flags and the
     // dispatch order are in it — so setters that only change buffer CONTENTS no longer drop the graph: `set_xref; mpc_run(k)`
     // in a loop replays one captured graph instead of re-capturing it every step)
-    char sig[480];
-    snprintf(sig, sizeof sig, "%d|%d|%d|%s|%d|%d|%g|%g|%d|%d|%p|%p|%p|%d|%p|%p|%p|%p|%d%d|%a|%d%d%d|%d%d|%d|%p|%p|%p", steps, window_advance, v, tb->kname.c_str(), tb->max_iter,
+    char sig[560];
+    snprintf(sig, sizeof sig, "%p|%p|%p|%d|%d|%d|%s|%d|%d|%g|%g|%d|%d|%p|%p|%p|%d|%p|%p|%p|%p|%d%d|%a|%d%d%d|%d%d|%d|%p|%p|%p", (void *)tb->pm_src, (void *)tb->pm_row[0],
+             (void *)tb->pm_row[1], steps, window_advance, v, tb->kname.c_str(), tb->max_iter,
              tb->check_termination, (double)tb->abs_pri_tol, (double)tb->abs_dua_tol, tb->xref_mode, tb->table_rows, (void *)tb->pair[0],
              (void *)tb->arr[0], (void *)tb->r_bounds, (int)tb->h16, (void *)tb->stream, (void *)d_u0_traj, (void *)tb->r_xref,
              (void *)tb->r_uref, (int)tb->en_uref, (int)tb->en_d2p, (double)tb->rho, (int)bounds_all_shared(tb),

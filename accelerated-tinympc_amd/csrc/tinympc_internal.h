@@ -117,6 +117,26 @@ struct RowParams
     int dual32;                  // with fp16 storage: gy (the duals g, y) stays fp32 in HBM and is not rounded (rowlane and quadlane kernels only)
 };
 
+// Per-instance models (tiny_batch_set_models): a kernel argument of its own beside RowParams / SolveParams, whose layouts stay as they are.
+//   mats: [batch][mats_stride] — the rowlane kernel: pack_gains' rows 0 .. 3nx + 2nu (M1, M2, M3, M45, Q, PT; no optional-term rows) of
+//         each instance, in the exact or the fma form; the run-time-dimension kernel: Kinf | Pinf | Quu_inv | AmBKt | Adyn | Bdyn | Q
+//   rho:  [batch]
+struct ModelParams
+{
+    const float *mats = nullptr;
+    unsigned mats_stride = 0; // floats between instances
+    const float *rho = nullptr;
+};
+// floats of one instance's record in the two forms
+__host__ __device__ inline int pm_row_floats(int nx, int nu) { return (3 * nx + 2 * nu + 1) * 16; }
+__host__ __device__ inline int pm_gen_floats(int nx, int nu) { return nu * nx + nx * nx + nu * nu + nx * nx + nx * nx + nx * nu + nx; }
+
+// batched fp64 Riccati (riccati_batch.hip): doubles of scratch per system, and the launch over systems [s0, min(s0 + n, count)) with scratch for n systems
+__host__ __device__ inline int riccati_batch_doubles(int nx, int nu) { return 4 * nx * nx + 3 * nu * nx + nu * (nx > nu ? nx : nu) + 2 * nu * nu; }
+hipError_t launch_riccati_batch(int nx, int nu, int s0, int n, int count, const double *A, const double *B, const double *Q, const double *R, const double *rho,
+                                double *Kinf, double *Pinf, double *Quu_inv, double *AmBKt, double *coeff_d2p, int *iters, double *scratch, int *nfail,
+                                hipStream_t stream);
+
 // (nx, nu) pairs with single-function kernels (admm_steps.hip), any N
 // (2, 2): the reference's own examples/codegen_random.cpp:19-31 (n = 2, m = 2, N = 3, min > max bounds)
 #define TINY_FOR_EACH_ROWDIMS(X) X(12, 4) X(4, 1) X(8, 3) X(8, 4) X(12, 2) X(4, 2) X(4, 4) X(2, 2)
@@ -128,6 +148,9 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 bool rowlane_supported(int nx, int nu, int N);
 // h16: the row-layout arrays, Xref and the bounds table are IEEE binary16 (see rowlane_math.h: rnd/ldw/stw)
 hipError_t launch_admm_rowlane(int nx, int nu, int N, bool exact, bool h16, const RowParams &P, hipStream_t stream);
+// the same kernel with per-instance models (admm_rowlane_pm_kernel): fp32 storage, no optional terms; shared or per-instance bounds for one solve,
+// shared bounds for the on-chip closed loop (P.mpc_steps > 1)
+hipError_t launch_admm_rowlane_pm(int nx, int nu, int N, bool exact, const RowParams &P, const ModelParams &M, hipStream_t stream);
 bool rowdims_supported(int nx, int nu);
 hipError_t launch_admm_rowstream(int nx, int nu, bool exact, bool h16, const RowParams &P, hipStream_t stream);
 hipError_t launch_admm_step(int nx, int nu, bool exact, bool h16, int fn, const RowParams &P, int *conv_out, hipStream_t stream);
@@ -169,6 +192,8 @@ hipError_t launch_admm_stream(int nxc, int nuc, const SolveParams &P, hipStream_
 // multiple of 4; gains = Kinf | Pinf | Quu_inv | AmBKt | Adyn | Bdyn | Q (column-major)
 bool generic_exact_supported(int nx, int nu);
 hipError_t launch_admm_generic(const SolveParams &P, const float *gains, int nxc, int nuc, hipStream_t stream);
+// ... with per-instance models: M.mats in the run-time-dimension form, M.mats_stride = pm_gen_floats(nx, nu)
+hipError_t launch_admm_generic_pm(const SolveParams &P, const ModelParams &M, int nxc, int nuc, hipStream_t stream);
 
 // longest-first dispatch order of the instance groups for the register-resident row kernel (dispatch_order.hip);
 // P.mats must be the fma gains

@@ -97,6 +97,66 @@ def with_cache(prob: dict, riccati=None) -> dict:
     return out
 
 
+def model_family(kind: str, n_models: int, batch: int, seed: int = 7) -> dict:
+    """Seeded family of `n_models` distinct models of one class, assigned to `batch` instances by a shuffled index.
+
+    kind = "quadrotor": the 20 Hz quadrotor with per-model scaled Bdyn columns (mass / inertia, 0.8 ... 1.25) and rho (4 ... 6.5, around the shipped 5);
+    "cartpole": the cartpole with A perturbed by 1 % relative noise on its non-zero entries and rho (1 ... 4); "random83": seeded random (8, 3) systems.
+    Returns per-instance A [B][nx][nx], B [B][nx][nu], Q [B][nx], R [B][nu] (without rho), rho [B] (float64), the per-instance model index
+    `model` [B] and the distinct models' own arrays under "models" (the same keys, leading axis n_models)."""
+    rng = np.random.default_rng(seed)
+    if kind == "quadrotor":
+        base = quadrotor(20, 30)
+        A0, B0, Q0, R0 = base["Adyn"], base["Bdyn"], np.asarray(base["Q"], np.float64), np.asarray(base["R"], np.float64).ravel()
+        As, Bs, rhos = [], [], []
+        for _ in range(n_models):
+            As.append(A0.copy())
+            Bs.append(B0 * rng.uniform(0.8, 1.25, size=B0.shape[1])[None, :])
+            rhos.append(rng.uniform(4.0, 6.5))
+        Qs, Rs = [Q0.copy() for _ in range(n_models)], [R0.copy() for _ in range(n_models)]
+    elif kind == "cartpole":
+        base = cartpole()
+        A0, B0 = base["Adyn"], base["Bdyn"]
+        As = [A0 * (1.0 + 0.01 * rng.standard_normal(A0.shape) * (A0 != 0)) for _ in range(n_models)]
+        Bs = [B0.copy() for _ in range(n_models)]
+        Qs, Rs = [np.array([10.0, 1.0, 10.0, 1.0]) for _ in range(n_models)], [np.array([1.0]) for _ in range(n_models)]
+        rhos = [float(rng.uniform(5.0, 20.0)) for _ in range(n_models)]
+    elif kind == "random83":
+        As, Bs, Qs, Rs, rhos = [], [], [], [], []
+        for _ in range(n_models):
+            A = np.eye(8) + 0.05 * rng.standard_normal((8, 8)) / np.sqrt(8)
+            As.append(A / np.max(np.abs(np.linalg.eigvals(A))))
+            Bs.append(0.1 * rng.standard_normal((8, 3)))
+            Qs.append(np.full(8, 10.0)); Rs.append(np.full(3, 1.0)); rhos.append(float(rng.uniform(0.5, 2.0)))
+    else:
+        raise ValueError(kind)
+    model = rng.permutation(np.arange(batch) % n_models)
+    models = dict(A=np.array(As), B=np.array(Bs), Q=np.array(Qs), R=np.array(Rs), rho=np.array(rhos, np.float64))
+    out = {k: v[model] for k, v in models.items()}
+    out["model"] = model
+    out["models"] = models
+    return out
+
+
+def family_caches(fam: dict, riccati=None) -> dict:
+    """The per-instance models of a model_family() batch with host Riccati caches (one tiny_riccati per distinct model), in the keys and
+    conventions of with_cache / TinyBatchSolver.set_models (Q = Q + rho).  Also returns the distinct models' prob-style dicts under "probs"."""
+    if riccati is None:
+        from . import riccati as _r
+        riccati = _r
+    ms = fam["models"]
+    nx, nu = ms["A"].shape[1], ms["B"].shape[2]
+    probs = []
+    for i in range(len(ms["rho"])):
+        p = dict(nx=nx, nu=nu, rho=float(ms["rho"][i]), Adyn=ms["A"][i], Bdyn=ms["B"][i], Q=ms["Q"][i], R=ms["R"][i])
+        probs.append(with_cache(p, riccati))
+    idx = fam["model"]
+    out = {k: np.array([probs[m][k] for m in range(len(probs))])[idx] for k in ("Kinf", "Pinf", "Quu_inv", "AmBKt", "Adyn", "Bdyn", "Q")}
+    out["rho"] = ms["rho"][idx]
+    out["probs"] = probs
+    return out
+
+
 def y_axis_line() -> np.ndarray:
     """(301, 12) reference trajectory: z = 1 m, y from 0 to 4 m, dy = 0.2666667 m/s (0 in the last row).
 

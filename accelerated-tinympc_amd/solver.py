@@ -84,6 +84,10 @@ def load_library(build_if_missing: bool = False) -> C.CDLL:
         "tiny_batch_set_array_device": [P, C.c_int, P], "tiny_batch_get_array_device": [P, C.c_int, P],
         "tiny_batch_set_xref_device": [P, P, C.c_int],
         "tiny_riccati": [C.c_int, C.c_int, D, D, D, D, C.c_double, D, D, D, D, D, I],
+        "tiny_batch_set_models": [P, F, F, F, F, F, F, F, F], "tiny_batch_set_models_device": [P, P, P, P, P, P, P, P, P],
+        "tiny_batch_clear_models": [P], "tiny_batch_models_per_instance": [P],
+        "tiny_batch_riccati_device": [C.c_int, C.c_int, C.c_int, P, P, P, P, P, P, P, P, P, P, P, P],
+        "tiny_batch_set_systems": [P, D, D, D, D, D, I],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)
@@ -169,6 +173,56 @@ def riccati(nx, nu, A, B, Q, R, rho):
                 AmBKt=Am.reshape(nx, nx).T.copy(), coeff_d2p=cd.reshape(nu, nx).T.copy(), iters=it.value)
 
 
+def _colmajor_batch(m, dtype=np.float32):
+    """[B][rows][cols] logical matrices -> [B][rows*cols] column-major each."""
+    a = np.asarray(m, dtype=dtype)
+    return np.ascontiguousarray(np.swapaxes(a, 1, 2)).reshape(a.shape[0], -1)
+
+
+def _hip():
+    """The HIP runtime the library is linked against (device buffers for riccati_batch without a framework in between)."""
+    hip = C.CDLL(os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib", "libamdhip64.so"))
+    hip.hipMalloc.argtypes, hip.hipMalloc.restype = [C.POINTER(C.c_void_p), C.c_size_t], C.c_int
+    hip.hipFree.argtypes, hip.hipFree.restype = [C.c_void_p], C.c_int
+    hip.hipMemcpy.argtypes, hip.hipMemcpy.restype = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int], C.c_int
+    return hip
+
+
+def riccati_batch(nx, nu, A, B, Q, R, rho) -> dict:
+    """tiny_riccati for many systems on the GPU (tiny_batch_riccati_device, current HIP device), fp64, bitwise equal to `riccati` per system.
+    A [S][nx][nx], B [S][nx][nu], Q [S][nx], R [S][nu], rho [S] (Q, R without rho).  Returns Kinf [S][nu][nx], Pinf, Quu_inv, AmBKt, coeff_d2p
+    (logical orientation, float64) and iters [S] (-1 where the recursion is singular: that system's matrices are then NaN)."""
+    lib, hip = load_library(), _hip()
+    S = int(np.asarray(rho).shape[0])
+    ins = [_colmajor_batch(A, np.float64), _colmajor_batch(B, np.float64), np.asarray(Q, np.float64).reshape(S, nx),
+           np.asarray(R, np.float64).reshape(S, nu), np.asarray(rho, np.float64).reshape(S)]
+    shp = {"Kinf": (nx, nu), "Pinf": (nx, nx), "Quu_inv": (nu, nu), "AmBKt": (nx, nx), "coeff_d2p": (nu, nx)}
+    outs = {k: np.full((S, a * b), np.nan) for k, (a, b) in shp.items()}
+    it = np.zeros(S, np.int32)
+    host = [np.ascontiguousarray(a) for a in ins] + list(outs.values()) + [it]
+    dev = []
+    try:
+        for a in host:
+            p = C.c_void_p()
+            if hip.hipMalloc(C.byref(p), a.nbytes) != 0:
+                raise TinyBatchError("hipMalloc failed")
+            dev.append(p)
+            if hip.hipMemcpy(p, a.ctypes.data, a.nbytes, 1) != 0:  # hipMemcpyHostToDevice
+                raise TinyBatchError("hipMemcpy failed")
+        rc = lib.tiny_batch_riccati_device(nx, nu, S, *dev, None)
+        if rc < 0:
+            raise TinyBatchError(f"rc={rc}: {lib.tiny_batch_last_error().decode()}")
+        for a, p in zip(host[5:], dev[5:]):
+            if hip.hipMemcpy(a.ctypes.data, p, a.nbytes, 2) != 0:  # hipMemcpyDeviceToHost
+                raise TinyBatchError("hipMemcpy failed")
+    finally:
+        for p in dev:
+            hip.hipFree(p)
+    res = {k: np.swapaxes(v.reshape(S, *shp[k]), 1, 2).copy() for k, v in outs.items()}
+    res["iters"] = it
+    return res
+
+
 def solve_group(solvers) -> int:
     """tiny_batch_group_solve: several problem classes (one TinyBatchSolver each) solved as one overlapping group.
     Returns the number of instances, over all classes, that hit max_iter."""
@@ -202,6 +256,38 @@ class TinyBatchSolver:
         """TinyCache (types.hpp:26-34): rho, Kinf, Pinf, Quu_inv, AmBKt of `prob` (logical row/col numpy matrices)."""
         k, p, qi, am = (_colmajor(prob[n]) for n in ("Kinf", "Pinf", "Quu_inv", "AmBKt"))
         self._check(self.lib.tiny_batch_set_cache(self._h, float(prob["rho"]), _fp(k), _fp(p), _fp(qi), _fp(am)))
+
+    # -- per-instance models (tiny_batch_set_models) ----------------------------------------------
+    def set_models(self, models: dict):
+        """Every instance its own model: `models` holds rho [B] and Kinf, Pinf, Quu_inv, AmBKt, Adyn, Bdyn [B][rows][cols], Q [B][nx], the keys and
+        the logical orientation of set_cache / the prob dicts (Q as stored in work.Q)."""
+        B = self.B
+        rho = _f32(np.asarray(models["rho"]).reshape(B))
+        arrs = [_colmajor_batch(models[k]) for k in ("Kinf", "Pinf", "Quu_inv", "AmBKt", "Adyn", "Bdyn")]
+        q = _f32(np.asarray(models["Q"]).reshape(B, self.nx))
+        for k, a in zip(("Kinf", "Pinf", "Quu_inv", "AmBKt", "Adyn", "Bdyn"), arrs):
+            assert a.shape[0] == B, (k, a.shape)
+        self._check(self.lib.tiny_batch_set_models(self._h, _fp(rho), *[_fp(a) for a in arrs], _fp(q)))
+
+    def set_systems(self, A, B, Q, R, rho) -> np.ndarray:
+        """Per-instance models from fp64 systems: the Riccati cache of every instance on the GPU (tiny_batch_set_systems), installed with the
+        conventions of problems.with_cache.  A [B][nx][nx], B [B][nx][nu], Q [B][nx], R [B][nu] (without rho), rho [B].  Returns iters [B]."""
+        n = self.B
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        a, b = _colmajor_batch(A, np.float64), _colmajor_batch(B, np.float64)
+        q = np.ascontiguousarray(np.asarray(Q, np.float64).reshape(n, self.nx))
+        r = np.ascontiguousarray(np.asarray(R, np.float64).reshape(n, self.nu))
+        rh = np.ascontiguousarray(np.asarray(rho, np.float64).reshape(n))
+        it = np.zeros(n, np.int32)
+        self._check(self.lib.tiny_batch_set_systems(self._h, dp(a), dp(b), dp(q), dp(r), dp(rh), it.ctypes.data_as(C.POINTER(C.c_int))))
+        return it
+
+    def clear_models(self):
+        """Back to the batch-shared cache and dynamics."""
+        self._check(self.lib.tiny_batch_clear_models(self._h))
+
+    def models_per_instance(self) -> bool:
+        return bool(self._check(self.lib.tiny_batch_models_per_instance(self._h)))
 
     # -- plumbing ---------------------------------------------------------------------------
     def _check(self, rc):

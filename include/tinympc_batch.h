@@ -313,6 +313,40 @@ extern "C"
     /* Uref: [N-1][nu] when shared != 0, else [batch][N-1][nu] (types.hpp:93) */
     int tiny_batch_set_uref(TinyBatch *tb, const float *uref, int shared);
 
+    /* ---- per-instance models: every instance its own problem class data --------------------------------------------------
+     * Every instance gets its own TinyCache{rho, Kinf, Pinf, Quu_inv, AmBKt} (types.hpp:26-34) and its own Adyn, Bdyn, Q (types.hpp:82-85),
+     * each array [B][...] with every instance's matrix column-major.  This satisfies the "cache and dynamics set" readiness check of a solve,
+     * replaces the batch-shared cache / dynamics until tiny_batch_clear_models(), and drops a captured closed-loop graph.  Settings stay per batch.
+     * Kernels: the unrolled 16-lane kernel where (nx, nu, N) is instantiated (exact or fma arithmetic, shared or per-instance bounds, any
+     * reference, the on-chip closed loop; kernel name "rowlane<nx,nu,N,exact,pm>"), the run-time-dimension exact kernel otherwise
+     * ("generic<nx,nu,exact,pm>").  Not available, TINY_BATCH_EUNSUPPORTED with a message: fp16 storage, the optional terms, a forced kernel
+     * that keeps one gain table per launch (streaming MFMA, tile16, quadlane, rowloop, rowstream, the wave kernels, tile48), the six
+     * single-function step calls.  The longest-first predictor (tiny_batch_set_dispatch mode 1) reads shared gains: such launches keep index
+     * order, history order (mode 2) applies; tiny_batch_dispatch_applied() says which. */
+    int tiny_batch_set_models(TinyBatch *tb, const float *rho /*[B]*/, const float *Kinf /*[B][nu*nx]*/, const float *Pinf /*[B][nx*nx]*/,
+                              const float *Quu_inv /*[B][nu*nu]*/, const float *AmBKt /*[B][nx*nx]*/, const float *Adyn /*[B][nx*nx]*/,
+                              const float *Bdyn /*[B][nx*nu]*/, const float *Q /*[B][nx]*/);
+    /* the same with DEVICE pointers on the handle's device: one gather kernel on the handle's stream, asynchronous */
+    int tiny_batch_set_models_device(TinyBatch *tb, const float *d_rho, const float *d_Kinf, const float *d_Pinf, const float *d_Quu_inv,
+                                     const float *d_AmBKt, const float *d_Adyn, const float *d_Bdyn, const float *d_Q);
+    /* back to the batch-shared cache / dynamics of tiny_batch_set_cache / tiny_batch_set_dynamics; the device memory of the per-instance
+     * records is released */
+    int tiny_batch_clear_models(TinyBatch *tb);
+    /* 1 while per-instance models are in force, 0 otherwise */
+    int tiny_batch_models_per_instance(TinyBatch *tb);
+    /* tiny_riccati for `count` independent systems on the device, fp64, bitwise equal per system.  Per system: A [nx*nx], B [nx*nu] column-major,
+     * Q [nx], R [nu], rho; outputs as tiny_riccati, [count][...] each; coeff_d2p may be NULL.  iters[i] = tiny_riccati's *iters, or -1 where
+     * tiny_riccati would return TINY_BATCH_EINVAL (singular); such a system's outputs are not written.  Device pointers; runs on hip_stream
+     * (NULL = the null stream) and waits for it.  Returns the number of failed systems (>= 0) or a negative error.  1 <= nx <= 64, 1 <= nu <= 32. */
+    int tiny_batch_riccati_device(int nx, int nu, int count, const double *d_A, const double *d_B, const double *d_Q, const double *d_R,
+                                  const double *d_rho, double *d_Kinf, double *d_Pinf, double *d_Quu_inv, double *d_AmBKt,
+                                  double *d_coeff_d2p, int *d_iters, void *hip_stream);
+    /* HOST fp64 systems in ([B][...] as above; Q, R without rho), the Riccati recursion on the handle's device, the result installed as the
+     * handle's per-instance models with the conventions of the code generator: Adyn = (float)A, Bdyn = (float)B, Q = (float)(Q + rho),
+     * rho = (float)rho, the cache = (float) of the fp64 result.  iters ([B], may be NULL) as tiny_batch_riccati_device.  Any failed system:
+     * TINY_BATCH_EINVAL and the handle's models are unchanged. */
+    int tiny_batch_set_systems(TinyBatch *tb, const double *A, const double *B, const double *Q, const double *R, const double *rho, int *iters);
+
     /* ---- offline setup: Riccati cache precompute (src/tinympc/codegen.cpp:254-292), fp64, host ---- */
     /* A (nx x nx), B (nx x nu) column-major; Q (nx), R (nu) diagonals WITHOUT rho (the routine adds it,
      * codegen.cpp:255-256).  Outputs column-major.  *iters = Riccati iterations run (1000 = not converged,
