@@ -5,6 +5,7 @@
 // There is deliberately NO CPU fallback in this library: every entry point that computes
 // launches a HIP kernel and reports HIP failures as TINY_BATCH_EHIP.
 #include "../../include/tinympc_batch.h"
+#include "eigen_orders.h"
 #include "tinympc_internal.h"
 
 #include <cmath>
@@ -211,8 +212,8 @@ __global__ void dual_width_kernel(const float *__restrict__ src, float *__restri
 // One thread per instance; matrices column-major in global memory (tiny, cache resident).
 // Summation order = Eigen's for that expression (pinned bit for bit against that expression compiled from the reference, tests/test_oracle.py:
 // test_plant_step_bit_exact_vs_compiled_reference): dst = Adyn*x0, then dst += Bdyn*u0; a product whose rows and depth are both >= 8 takes the column-major
-// GEMV kernel (row accumulator starting at +0, products added in ascending column order), a smaller one the lazy product
-// (sequential from the first product for the nx % 4 == 0 classes this library serves).
+// GEMV kernel (row accumulator starting at +0, products added in ascending column order), a smaller one the lazy product in the order of its
+// row count (eigen_orders.h: sequential for nx % 4 == 0, the halving tree for nx = 2, 3, the packet tree for nx = 1)
 __device__ __forceinline__ void plant_step_one(int b, float *__restrict__ x0buf, float *__restrict__ xarr, const float *__restrict__ uarr,
                                                const float *__restrict__ A, const float *__restrict__ Bm, int *__restrict__ wstart,
                                                int window_advance, int layout, Geo g, int h16)
@@ -220,15 +221,23 @@ __device__ __forceinline__ void plant_step_one(int b, float *__restrict__ x0buf,
     const int nx = g.nx, nu = g.nu;
     const float *x0 = x0buf + (long long)b * nx;
     const bool gemv_a = nx >= 8, gemv_b = nx >= 8 && nu >= 8;
-    float xn[64];
+    float xn[64], u0[64], t[64];
+    for (int m = 0; m < nu; m++) u0[m] = get_elem(uarr, idx_of(layout, g, 1, b, 0, m), h16);
     for (int i = 0; i < nx; i++)
     {
-        float acc = A[i] * x0[0];
-        if (gemv_a) acc = 0.f + acc;
-        for (int k = 1; k < nx; k++) acc += A[k * nx + i] * x0[k];
-        float acc2 = Bm[i] * get_elem(uarr, idx_of(layout, g, 1, b, 0, 0), h16);
-        if (gemv_b) acc2 = 0.f + acc2;
-        for (int m = 1; m < nu; m++) acc2 += Bm[m * nx + i] * get_elem(uarr, idx_of(layout, g, 1, b, 0, m), h16);
+        float acc, acc2;
+        if (gemv_a)
+        {
+            acc = 0.f + A[i] * x0[0];
+            for (int k = 1; k < nx; k++) acc += A[k * nx + i] * x0[k];
+        }
+        else acc = gen_row_dot(A, nx, nx, i, x0, t);
+        if (gemv_b)
+        {
+            acc2 = 0.f + Bm[i] * u0[0];
+            for (int m = 1; m < nu; m++) acc2 += Bm[m * nx + i] * u0[m];
+        }
+        else acc2 = gen_row_dot(Bm, nx, nu, i, u0, t);
         xn[i] = acc + acc2;
     }
     for (int i = 0; i < nx; i++)

@@ -97,13 +97,20 @@ def with_cache(prob: dict, riccati=None) -> dict:
     return out
 
 
-def model_family(kind: str, n_models: int, batch: int, seed: int = 7) -> dict:
+def model_family(kind: str, n_models: int, batch: int, seed: int = 7, vary: str = "some", dims: tuple | None = None) -> dict:
     """Seeded family of `n_models` distinct models of one class, assigned to `batch` instances by a shuffled index.
 
     kind = "quadrotor": the 20 Hz quadrotor with per-model scaled Bdyn columns (mass / inertia, 0.8 ... 1.25) and rho (4 ... 6.5, around the shipped 5);
-    "cartpole": the cartpole with A perturbed by 1 % relative noise on its non-zero entries and rho (1 ... 4); "random83": seeded random (8, 3) systems.
+    "cartpole": the cartpole with A perturbed by 1 % relative noise on its non-zero entries and rho (1 ... 4); "random83": seeded random (8, 3) systems;
+    "random": seeded random systems of any dims = (nx, nu) (each <= 4 or a multiple of 4 for the run-time-dimension kernel), spectral radius 0.9 ... 0.97,
+    every matrix their own.
+    vary = "all" gives every model its own A, B, Q and R as well: the quadrotor's non-zero Adyn entries get 1 ... 2 % relative noise, the cartpole's
+    Bdyn a per-model scale (0.8 ... 1.25), and every kind per-entry Q and R scales (0.5 ... 2).  Those extra draws come from a second stream seeded by `seed`, so
+    vary = "some" (the default) gives the same models for the same seed with or without it.
     Returns per-instance A [B][nx][nx], B [B][nx][nu], Q [B][nx], R [B][nu] (without rho), rho [B] (float64), the per-instance model index
     `model` [B] and the distinct models' own arrays under "models" (the same keys, leading axis n_models)."""
+    if vary not in ("some", "all"):
+        raise ValueError(vary)
     rng = np.random.default_rng(seed)
     if kind == "quadrotor":
         base = quadrotor(20, 30)
@@ -128,8 +135,26 @@ def model_family(kind: str, n_models: int, batch: int, seed: int = 7) -> dict:
             As.append(A / np.max(np.abs(np.linalg.eigvals(A))))
             Bs.append(0.1 * rng.standard_normal((8, 3)))
             Qs.append(np.full(8, 10.0)); Rs.append(np.full(3, 1.0)); rhos.append(float(rng.uniform(0.5, 2.0)))
+    elif kind == "random":
+        nx, nu = dims
+        As, Bs, Qs, Rs, rhos = [], [], [], [], []
+        for _ in range(n_models):
+            A = np.eye(nx) + 0.05 * rng.standard_normal((nx, nx)) / np.sqrt(nx)
+            As.append(rng.uniform(0.9, 0.97) * A / np.max(np.abs(np.linalg.eigvals(A))))  # strictly stable: the Riccati recursion converges in ~100 iterations
+            Bs.append(0.1 * rng.standard_normal((nx, nu)))
+            Qs.append(10.0 * rng.uniform(0.5, 2.0, size=nx)); Rs.append(rng.uniform(0.5, 2.0, size=nu)); rhos.append(float(rng.uniform(0.5, 2.0)))
     else:
         raise ValueError(kind)
+    if vary == "all" and kind != "random":
+        r2 = np.random.default_rng([seed, 1])
+        for i in range(n_models):
+            if kind == "quadrotor":
+                nz = As[i] != 0
+                As[i] = As[i] * (1.0 + r2.uniform(0.01, 0.02, size=nz.shape) * r2.choice([-1.0, 1.0], size=nz.shape) * nz)
+            elif kind == "cartpole":
+                Bs[i] = Bs[i] * r2.uniform(0.8, 1.25, size=Bs[i].shape[1])[None, :]
+            Qs[i] = Qs[i] * r2.uniform(0.5, 2.0, size=Qs[i].shape)
+            Rs[i] = Rs[i] * r2.uniform(0.5, 2.0, size=Rs[i].shape)
     model = rng.permutation(np.arange(batch) % n_models)
     models = dict(A=np.array(As), B=np.array(Bs), Q=np.array(Qs), R=np.array(Rs), rho=np.array(rhos, np.float64))
     out = {k: v[model] for k, v in models.items()}

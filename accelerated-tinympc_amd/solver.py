@@ -188,15 +188,18 @@ def _hip():
     return hip
 
 
-def riccati_batch(nx, nu, A, B, Q, R, rho) -> dict:
+def riccati_batch(nx, nu, A, B, Q, R, rho, coeff_d2p: bool = True) -> dict:
     """tiny_riccati for many systems on the GPU (tiny_batch_riccati_device, current HIP device), fp64, bitwise equal to `riccati` per system.
     A [S][nx][nx], B [S][nx][nu], Q [S][nx], R [S][nu], rho [S] (Q, R without rho).  Returns Kinf [S][nu][nx], Pinf, Quu_inv, AmBKt, coeff_d2p
-    (logical orientation, float64) and iters [S] (-1 where the recursion is singular: that system's matrices are then NaN)."""
+    (logical orientation, float64) and iters [S] (-1 where the recursion is singular: that system's matrices are then NaN).
+    coeff_d2p = False passes d_coeff_d2p = NULL (the library then skips that product) and returns no "coeff_d2p"."""
     lib, hip = load_library(), _hip()
     S = int(np.asarray(rho).shape[0])
     ins = [_colmajor_batch(A, np.float64), _colmajor_batch(B, np.float64), np.asarray(Q, np.float64).reshape(S, nx),
            np.asarray(R, np.float64).reshape(S, nu), np.asarray(rho, np.float64).reshape(S)]
     shp = {"Kinf": (nx, nu), "Pinf": (nx, nx), "Quu_inv": (nu, nu), "AmBKt": (nx, nx), "coeff_d2p": (nu, nx)}
+    if not coeff_d2p:
+        del shp["coeff_d2p"]
     outs = {k: np.full((S, a * b), np.nan) for k, (a, b) in shp.items()}
     it = np.zeros(S, np.int32)
     host = [np.ascontiguousarray(a) for a in ins] + list(outs.values()) + [it]
@@ -209,7 +212,7 @@ def riccati_batch(nx, nu, A, B, Q, R, rho) -> dict:
             dev.append(p)
             if hip.hipMemcpy(p, a.ctypes.data, a.nbytes, 1) != 0:  # hipMemcpyHostToDevice
                 raise TinyBatchError("hipMemcpy failed")
-        rc = lib.tiny_batch_riccati_device(nx, nu, S, *dev, None)
+        rc = lib.tiny_batch_riccati_device(nx, nu, S, *(dev if coeff_d2p else dev[:9] + [None] + dev[9:]), None)
         if rc < 0:
             raise TinyBatchError(f"rc={rc}: {lib.tiny_batch_last_error().decode()}")
         for a, p in zip(host[5:], dev[5:]):

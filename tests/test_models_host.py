@@ -72,3 +72,59 @@ def test_family_caches_follow_with_cache(tinympc):
         p = m["probs"][fam["model"][b]]
         assert np.array_equal(m["Kinf"][b], p["Kinf"]) and np.array_equal(m["Q"][b], fam["Q"][b] + fam["rho"][b])
         assert m["rho"][b] == fam["rho"][b]
+
+
+def test_default_families_are_unchanged(tinympc):
+    """vary="some" (the default) draws exactly what it drew before vary="all" and the "random" kind existed (tools/models_time.py and the GPU tests
+    depend on it): a fingerprint of the quadrotor and cartpole families (no eigenvalue routine in them, so no LAPACK build in the hash)."""
+    import hashlib
+    pr = tinympc.problems
+    for kind, want in (("quadrotor", "825bd11276045965"), ("cartpole", "5d6938f00f23a851")):
+        f = pr.model_family(kind, 8, 32, seed=4)
+        h = hashlib.sha256()
+        for k in ("A", "B", "Q", "R", "rho", "model"):
+            h.update(np.ascontiguousarray(f[k]).tobytes())
+        assert h.hexdigest()[:16] == want, kind
+        g = pr.model_family(kind, 8, 32, seed=4, vary="all")  # the extra draws come from a stream of their own
+        assert np.array_equal(g["model"], f["model"]) and np.array_equal(g["rho"], f["rho"])
+
+
+VARY_ALL = [("quadrotor", None), ("cartpole", None), ("random83", None)] + [("random", d) for d in ((12, 4), (4, 1), (8, 3), (20, 12), (3, 2), (8, 8), (4, 3),
+                                                                                                  (36, 4), (28, 16), (1, 1), (2, 5), (3, 8))]
+
+
+@pytest.mark.parametrize("kind,dims", VARY_ALL, ids=[k if d is None else f"{k}_{d[0]}_{d[1]}" for k, d in VARY_ALL])
+def test_model_family_vary_all(tinympc, kind, dims):
+    """The families the per-instance-model GPU tests use: deterministic, every pair of models differs in each of A, B, Q, R and rho, and the host
+    Riccati converges for every model."""
+    pr = tinympc.problems
+    n = 12
+    a = pr.model_family(kind, n, 3 * n, seed=6, vary="all", dims=dims)
+    b = pr.model_family(kind, n, 3 * n, seed=6, vary="all", dims=dims)
+    for k in ("A", "B", "Q", "R", "rho", "model"):
+        assert np.array_equal(a[k], b[k]), k
+    ms = a["models"]
+    for k in ("A", "B", "Q", "R", "rho"):
+        for i in range(n):
+            for j in range(i):
+                assert not np.array_equal(ms[k][i], ms[k][j]), (k, i, j)
+    if dims is not None:
+        assert ms["A"].shape[1:] == (dims[0], dims[0]) and ms["B"].shape[1:] == dims
+    for i in range(n):
+        r = tinympc.riccati(ms["A"].shape[1], ms["B"].shape[2], ms["A"][i], ms["B"][i], ms["Q"][i], ms["R"][i], ms["rho"][i])
+        assert 1 <= r["iters"] < 1000, (kind, dims, i, r["iters"])
+
+
+def test_every_rowlane_pm_instantiation_has_a_gpu_test():
+    """Coverage guard: every class of TINY_FOR_EACH_ROWLANE x {exact, fma} x {one solve, per-instance bounds, on-chip closed loop} (the 48
+    admm_rowlane_pm_kernel instantiations) is a case of tests/test_models_paths_gpu.py, so a new class cannot land untested."""
+    import re
+    from pathlib import Path
+    import test_models_paths_gpu as G
+    hdr = (Path(__file__).resolve().parents[1] / "accelerated-tinympc_amd" / "csrc" / "tinympc_internal.h").read_text()
+    line = re.search(r"#define TINY_FOR_EACH_ROWLANE\(X\)(.*)", hdr).group(1)
+    classes = {tuple(int(v) for v in m) for m in re.findall(r"X\((\d+),\s*(\d+),\s*(\d+)\)", line)}
+    assert len(classes) == 8, classes
+    want = {(c, a, w) for c in classes for a in ("exact", "fast") for w in ("solve", "bpi", "mpc")}
+    have = {(c, a, "bpi" if bpi else "solve") for c, a, bpi in G.SOLVE_CASES} | {(c, a, "mpc") for c, a in G.MPC_CASES}
+    assert have == want, sorted(want ^ have)

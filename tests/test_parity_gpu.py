@@ -1245,7 +1245,7 @@ def test_classes_without_an_instantiation_run_on_the_padded_mfma_kernel(tinympc,
         tinympc.TinyBatchSolver(pr.random_system(68, 4, 5, seed=1), 4)   # nx > 64: no kernel at all, refused at create
 
 
-@pytest.mark.parametrize("variant_name", ["row_exact", "row_fast", "loop_exact", "stream"])
+@pytest.mark.parametrize("variant_name", ["row_exact", "row_fast", "loop_exact", "stream", "generic"])
 def test_mpc_run_equals_step_by_step(tinympc, variant_name):
     """tiny_batch_mpc_run_async(steps) leaves exactly the state that `steps` calls of tiny_batch_mpc_step_async leave, in both
     implementations: the on-chip closed loop of the unrolled row kernel (row_* variants: one launch, the state stays in
@@ -1256,8 +1256,18 @@ def test_mpc_run_equals_step_by_step(tinympc, variant_name):
     B = 48
     x0, table, start = pr.tracking_batch(B, 30, seed=11)
     bnds = pr.bounds_arrays(prob)
-    a = make_solver(tinympc, prob, B, None, None, variant_name, bnds)
-    b = make_solver(tinympc, prob, B, None, None, variant_name, bnds)
+
+    def mk():
+        if variant_name != "generic":
+            return make_solver(tinympc, prob, B, None, None, variant_name, bnds)
+        # variant 4, the run-time-dimension kernel (not in VARIANTS: every test driven by the `variant` fixture iterates over that dict)
+        s = tinympc.TinyBatchSolver(prob, B)
+        s.select_kernel(4)
+        s.set_bounds(*bnds)
+        assert s.kernel_name() == "generic<12,4,exact>", s.kernel_name()
+        return s
+
+    a, b = mk(), mk()
     for s in (a, b):
         s.set_xref_window(table, start)
         s.set_x0(x0)
