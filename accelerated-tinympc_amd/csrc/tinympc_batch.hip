@@ -15,6 +15,7 @@
 #include <limits>
 #include <map>
 #include <mutex>
+#include <optional>
 #include <string>
 #include <vector>
 
@@ -110,7 +111,9 @@ hipError_t guarded_free(void *p)
 
 enum { LAYOUT_TILE = 0, LAYOUT_ROW = 1 };
 enum { VAR_AUTO = 0, VAR_STREAM = 1, VAR_ROW_EXACT = 2, VAR_ROW_FAST = 3, VAR_GENERIC = 4 }; // 4: admm_generic.hip, exact arithmetic for any eligible class
-inline bool tile_variant(int v) { return v == VAR_STREAM || v == VAR_GENERIC; } // the variants that work on the TILE layout
+
+// The solve kernels; kKernelTraits below says everything the host code needs to know about each of them.
+enum class Kernel { Rowlane, Rowloop, Rowstream, Wavestream, Quadlane, Tile16, Waveres, Tile48, Stream, Generic };
 
 // ---------------------------------------------------------------------------------------------
 // Element addressing of the two device layouts.  `fam` 0 = state-type (nx rows, N steps),
@@ -516,10 +519,9 @@ struct TinyBatch
     bool cold_pending = false;
     bool x0_zero_pending = false; // reset_workspace(): x.col(0) and x0buf read as zero until a set_x0 overwrites them
     int variant = VAR_AUTO;
-    int row_family_forced = -1; // tiny_batch_set_row_kernel
+    std::optional<Kernel> row_family_forced; // tiny_batch_set_row_kernel (empty: automatic)
     int last_dispatch = 0;        // what the most recent solve launch did: 0 index order, 1 predicted longest first, 2 the caller's order, 3 longest first by the previous solve's counts
     bool iter_history = false;    // iter[] holds the counts of a solve of THIS workspace's instances (not a reset, not an upload): the history order's key
-    bool closed_loop_run = false; // inside tiny_batch_mpc_run_*(steps > 1): the auto choice keeps the kernel with the on-chip loop
     // per-instance models (tiny_batch_set_models): one record per instance in the run-time-dimension kernel's form ([batch][pm_gen_floats]: Kinf | Pinf |
     // Quu_inv | AmBKt | Adyn | Bdyn | Q, which is also what the plant step reads), rho [batch]; the 16-lane kernel's two forms of the gain rows
     // ([batch][pm_row_floats], [0] exact, [1] fma) are packed from the records on the device when a launch first needs one
@@ -533,11 +535,39 @@ struct TinyBatch
     bool timing = false;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool ev_valid = false;
-    std::string kname;
+    std::string name_buf[2]; // what tiny_batch_kernel_name() [0] / tiny_batch_closed_loop_kernel_name() [1] last returned; nothing else reads or writes them
 };
 
 namespace
 {
+
+// In ONE table, everything the host code needs to know about each solve kernel (enum class Kernel, in its order).
+struct KernelTraits
+{
+    const char *name;      // what tiny_batch_kernel_name() prints up to the '<' ...
+    bool name_has_N;       // ... whether N follows nx, nu (one instantiation per horizon) ...
+    bool name_has_storage; // ... and ",h16" / ",h16d" the arithmetic (the kernels that implement fp16 storage)
+    int layout;            // device layout of the work arrays
+    bool fp32_duals;       // keeps the duals pair fp32 under fp16 storage (register-resident 16-lane and quad kernels)
+    int order_unit_solve;  // what a longest-first dispatch order lists for a lone solve: 4 groups of four instances, 16 tiles of sixteen, 0 takes no order
+    int order_unit_run;    // ... and for the on-chip closed-loop run
+    bool onchip_mpc;       // runs all the MPC steps of tiny_batch_mpc_run_async inside one launch
+    int row_kernel_number; // tiny_batch_set_row_kernel's public number (0: not a row kernel)
+    bool TinyBatch::*has;  // the handle's flag "this class has an instantiation of it" (set by tiny_batch_create)
+};
+constexpr KernelTraits kKernelTraits[] = {
+    /* Rowlane    */ {"rowlane", true, true, LAYOUT_ROW, true, 4, 4, true, 1, &TinyBatch::row_dims_ok},
+    /* Rowloop    */ {"rowloop", false, true, LAYOUT_ROW, false, 4, 0, false, 2, &TinyBatch::rowloop_ok},
+    /* Rowstream  */ {"rowstream", false, true, LAYOUT_ROW, false, 0, 0, false, 3, &TinyBatch::rowmath_ok},
+    /* Wavestream */ {"wavestream", false, false, LAYOUT_ROW, false, 0, 0, false, 6, &TinyBatch::wave_ok},
+    /* Quadlane   */ {"quadlane", true, true, LAYOUT_ROW, true, 0, 0, true, 4, &TinyBatch::quad_ok},
+    /* Tile16     */ {"tile16", true, false, LAYOUT_ROW, false, 16, 16, true, 5, &TinyBatch::tile16_ok},
+    /* Waveres    */ {"waveres", false, false, LAYOUT_ROW, false, 0, 0, false, 7, &TinyBatch::waveres_ok},
+    /* Tile48     */ {"tile48", true, false, LAYOUT_ROW, false, 0, 0, false, 8, &TinyBatch::tile48_ok},
+    /* Stream     */ {"stream", false, false, LAYOUT_TILE, false, 0, 0, false, 0, &TinyBatch::tile_dims_ok},
+    /* Generic    */ {"generic", false, false, LAYOUT_TILE, false, 0, 0, false, 0, &TinyBatch::generic_ok},
+};
+constexpr const KernelTraits &traits(Kernel k) { return kKernelTraits[(int)k]; }
 
 Geo geo(const TinyBatch *tb) { return Geo{tb->nx, tb->nu, tb->N, tb->NXC, tb->NUC, tb->rw}; }
 
@@ -721,16 +751,19 @@ int download_work(TinyBatch *tb, int id, float *host, int step0, int nsteps)
     return 0;
 }
 
-int store_input(TinyBatch *tb, InputArr &in, const float *host, bool shared, int steps, int dim)
+// `kind` = hipMemcpyDeviceToDevice: `src` is resident on the handle's device; no host copy is kept (only the bounds are ever read on the host) and the
+// call does not wait for the stream
+int store_input(TinyBatch *tb, InputArr &in, const float *src, bool shared, int steps, int dim, hipMemcpyKind kind = hipMemcpyHostToDevice)
 {
     const size_t n = (size_t)(shared ? 1 : tb->batch) * steps * dim;
+    const bool from_host = kind == hipMemcpyHostToDevice;
     if (in.dev && in.shared != shared) { (void)guarded_free(in.dev); in.dev = nullptr; }
     if (!in.dev) HIP_TRY(guarded_malloc((void **)&in.dev, n * sizeof(float)));
-    HIP_TRY(hipMemcpyAsync(in.dev, host, n * sizeof(float), hipMemcpyHostToDevice, tb->stream));
-    HIP_TRY(hipStreamSynchronize(tb->stream));
+    HIP_TRY(hipMemcpyAsync(in.dev, src, n * sizeof(float), kind, tb->stream));
+    if (from_host) HIP_TRY(hipStreamSynchronize(tb->stream));
     in.shared = shared;
     in.set = true;
-    if (shared) in.host.assign(host, host + n);
+    if (shared && from_host) in.host.assign(src, src + n);
     else in.host.clear();
     tb->derived_dirty[0] = tb->derived_dirty[1] = true; // (a captured closed-loop graph carries the mode in its signature)
     return 0;
@@ -1015,12 +1048,10 @@ int prepare_inputs(TinyBatch *tb, int layout)
     return 0;
 }
 
-int row_family(const TinyBatch *tb);
 // Automatic choice of the sixteen-instances-per-wave kernel (round 4, re-measured on the final binaries, 65 536-instance tracking workload cut to size, kernel ms,
 // tile16 / 16-lane kernel, both longest first): 32 768: 1.03 / 0.97, 36 864: 1.11 / 1.08, 40 960: 1.09 / 1.19, 49 152: 1.24 / 1.40, 65 536: 1.54 / 1.83 — from 160
 // instances per CU on; in index order the 16-lane kernel wins or ties at every size (65 536: 2.00 / 1.99), so the choice also asks for the longest-first dispatch
 constexpr int kTile16AutoPerCu = 160;
-int dispatch_effective(const TinyBatch *tb);
 bool tile16_auto_size(const TinyBatch *tb) { return dispatch_effective(tb) == 1 && tb->batch >= kTile16AutoPerCu * tb->n_cu; }
 // ... and for a closed-loop run (tiny_batch_mpc_run_async: all MPC steps of a tile inside one launch).  Since the tiles of a run are dispatched by the iteration
 // counts of the solve before it (history order, dispatch_order.hip: a tile's total over the steps of a run spreads widely, and four tiles per wave slot in index
@@ -1031,8 +1062,8 @@ constexpr int kTile16ClosedLoopPerCu = 160;
 bool tile16_closed_loop_size(const TinyBatch *tb) { return tb->batch >= kTile16ClosedLoopPerCu * tb->n_cu; }
 
 // fp16 storage: bring the duals pair to the width the coming launch implements.  Under tiny_batch_set_storage(tb, 16) fp32 duals are a
-// PREFERENCE (the register-resident 16-lane and quad kernels keep them, every other kernel — streamed state, per-instance bounds under
-// fp16, the optional terms, the six single-function kernels — stores binary16 duals): the array is converted in place of being refused.
+// PREFERENCE (the register-resident 16-lane and quad kernels keep them — KernelTraits::fp32_duals — every other kernel — streamed state, per-instance
+// bounds under fp16, the optional terms, the six single-function kernels — stores binary16 duals): the array is converted in place of being refused.
 // An explicit tiny_batch_set_storage_ex(tb, 16, 32) stays a requirement (the caller is told when a kernel cannot honour it).
 int settle_dual_width(TinyBatch *tb, bool kernel_keeps_fp32_duals)
 {
@@ -1053,83 +1084,7 @@ int settle_dual_width(TinyBatch *tb, bool kernel_keeps_fp32_duals)
     invalidate_graph(tb); // the array pointer is a kernel argument
     return 0;
 }
-bool family_keeps_fp32_duals(int fam) { return fam == 0 || fam == 4; }
 
-// per-instance models: the unrolled 16-lane kernel where (nx, nu, N) is instantiated, the run-time-dimension kernel otherwise (both read a gain
-// record per instance).  Every other kernel keeps ONE gain table for the whole launch — tile16's MFMA A operand is one gain matrix for all sixteen
-// columns, the streaming and wave kernels stage theirs once per workgroup — and is never chosen.
-int resolve_variant_pm(TinyBatch *tb, int *out)
-{
-    int v = tb->variant;
-    if (tb->h16)
-        return fail(TINY_BATCH_EUNSUPPORTED, "per-instance models (tiny_batch_set_models) are implemented for fp32 storage only: tiny_batch_set_storage(tb, 32) or tiny_batch_clear_models()");
-    if (tb->en_uref || tb->en_d2p)
-        return fail(TINY_BATCH_EUNSUPPORTED, "the optional Uref / coeff_d2p terms are not implemented with per-instance models (tiny_batch_set_optional_terms(tb, 0, 0) or tiny_batch_clear_models())");
-    if (v == VAR_STREAM)
-        return fail(TINY_BATCH_EUNSUPPORTED, "the streaming MFMA kernel (variant 1) holds one gain matrix for the whole launch and cannot serve per-instance models");
-    if (v == VAR_AUTO)
-    {
-        if (!tb->row_dims_ok && !tb->generic_ok)
-            return fail(TINY_BATCH_EUNSUPPORTED, "per-instance models need the unrolled 16-lane kernel (an instantiated nx, nu, N) or the run-time-dimension exact kernel "
-                                                 "(nx, nu each <= 4 or a multiple of 4); nx=%d nu=%d N=%d has neither", tb->nx, tb->nu, tb->N);
-        v = tb->row_dims_ok ? VAR_ROW_EXACT : VAR_GENERIC;
-    }
-    if (v == VAR_ROW_EXACT || v == VAR_ROW_FAST)
-    {
-        if (!tb->row_dims_ok)
-            return fail(TINY_BATCH_EUNSUPPORTED, "with per-instance models the row variants run on the unrolled 16-lane kernel only, which has no instantiation for nx=%d nu=%d N=%d "
-                                                 "(variant 4, the run-time-dimension exact kernel, serves it)", tb->nx, tb->nu, tb->N);
-        if (tb->row_family_forced >= 0 && tb->row_family_forced != 0)
-            return fail(TINY_BATCH_EUNSUPPORTED, "the forced row kernel (tiny_batch_set_row_kernel) keeps one gain table for the whole launch and cannot serve per-instance models "
-                                                 "(tile16: its MFMA A operand is one gain matrix for all 16 columns); only the 16-lane kernel (1) or auto (0) can");
-    }
-    if (v == VAR_GENERIC && !tb->generic_ok)
-        return fail(TINY_BATCH_EUNSUPPORTED, "the run-time-dimension exact kernel (variant 4) needs nx, nu each <= 4 or a multiple of 4 (nx=%d nu=%d)", tb->nx, tb->nu);
-    *out = v;
-    return 0;
-}
-
-int resolve_variant(TinyBatch *tb, int *out)
-{
-    if (tb->pm) return resolve_variant_pm(tb, out);
-    int v = tb->variant;
-    // row variants: register-resident kernel when (nx,nu,N) is instantiated, else the any-N row kernel with the state in HBM
-    // per-instance bounds: the streaming row kernel and the wave kernel read them per instance; the register-resident
-    // kernels stage ONE table in LDS and need batch-shared bounds
-    const bool row_ok = tb->row_dims_ok || tb->rowmath_ok || tb->wave_ok;
-    if (tb->variant == VAR_ROW_FAST && tb->wave_ok && row_family(tb) != 6 && row_family(tb) != 7)
-        return fail(TINY_BATCH_EUNSUPPORTED, "fma arithmetic for 16 < nx + nu <= 64 needs the state-on-chip wave kernel (N <= 50); beyond that it is the streaming MFMA kernel (variant 1)");
-    if (v == VAR_AUTO)
-    {
-        // the automatic choice is exact arithmetic or nothing: a class without a compiled exact kernel runs in fma arithmetic on the padded
-        // MFMA kernel only when the caller has asked for it by name (round 4: it used to be selected silently)
-        if (!row_ok && !tb->generic_ok)
-            return fail(TINY_BATCH_EUNSUPPORTED, "nx=%d nu=%d has no exact-arithmetic kernel (the reference's own summation order depends on column alignment "
-                                                 "unless nx and nu are each <= 4 or a multiple of 4); tiny_batch_select_kernel(tb, 1) opts into fma arithmetic "
-                                                 "on the MFMA streaming kernel", tb->nx, tb->nu);
-        v = row_ok ? VAR_ROW_EXACT : VAR_GENERIC; // a class outside the compiled lists: exact arithmetic with run-time dimensions (admm_generic.hip)
-    }
-    if (v == VAR_GENERIC && (!tb->generic_ok || tb->h16 || tb->en_uref || tb->en_d2p))
-        return fail(TINY_BATCH_EUNSUPPORTED, "the run-time-dimension exact kernel (variant 4) needs nx, nu each <= 4 or a multiple of 4 (nx <= 64, nu <= 32), "
-                                             "fp32 storage and no optional terms (nx=%d nu=%d)", tb->nx, tb->nu);
-    if ((tb->en_uref || tb->en_d2p) && (!tb->rowmath_ok || tile_variant(v)))
-        return fail(TINY_BATCH_EUNSUPPORTED, "the optional Uref / coeff_d2p terms (tiny_batch_set_optional_terms) are implemented by the row "
-                                             "kernels for nx + nu <= 16 only (nx=%d nu=%d, variant %d)", tb->nx, tb->nu, v);
-    if ((v == VAR_ROW_EXACT || v == VAR_ROW_FAST) && !row_ok)
-    {
-        return fail(TINY_BATCH_EUNSUPPORTED, "no row kernel instantiation for nx=%d nu=%d (needs nx + nu <= 16)", tb->nx, tb->nu);
-    }
-    if (v == VAR_STREAM && !tb->tile_dims_ok)
-        return fail(TINY_BATCH_EUNSUPPORTED, "no streaming kernel instantiation for nx=%d nu=%d", tb->nx, tb->nu);
-    if (v == VAR_STREAM && tb->h16)
-        return fail(TINY_BATCH_EUNSUPPORTED, "fp16 storage is implemented by the row kernels only (nx + nu <= 16)");
-    *out = v;
-    return 0;
-}
-
-// which of the three row kernels a row variant launches: 0 = unrolled register-resident (rowlane, fastest, one
-// instantiation per (nx, nu, N)), 1 = rolled-loop register-resident (rowloop, any N <= 64), 2 = any N with the state in
-// HBM (rowstream).  tiny_batch_set_row_kernel() can force one of them.
 // admm_tile16.hip needs fp32 storage, a reference it does not have to keep resident (a window of a trajectory table that
 // fits its LDS share, or one shared reference) and — checked by the caller — batch-shared bounds and no optional terms
 // Round 4: per-instance bounds and a per-instance reference are served by the PI instantiations (rows fetched by LDS-DMA into per-wave rings,
@@ -1152,14 +1107,11 @@ Tile16Pi tile16_pi_plan(const TinyBatch *tb)
 }
 // automatic choice with per-instance tables: the same rule as with shared ones (65 536 tracking instances, longest first, kernel ms, tile16 pi against the 16-lane
 // kernel: bounds constant along the horizon 1.75 / 2.13, reference per step 1.81 / 1.96, both per step 1.95 / 2.15; in index order the rings lose, 2.45 / 2.22)
-bool tile16_pi_auto(const TinyBatch *tb)
-{
-    return !tb->order_dev && tile16_auto_size(tb);
-}
-bool tile16_applies(const TinyBatch *tb)
+bool tile16_pi_auto(const TinyBatch *tb) { return !tb->order_dev && tile16_auto_size(tb); }
+bool tile16_applies(const TinyBatch *tb, bool closed_loop)
 {
     if (!tb->tile16_ok || tb->h16) return false;
-    if (tile16_per_instance(tb)) return !tb->closed_loop_run && tile16_pi_plan(tb).fits;
+    if (tile16_per_instance(tb)) return !closed_loop && tile16_pi_plan(tb).fits;
     if (tb->xref_mode == 1) return tb->table_rows <= tile16_max_table_rows();
     return true;
 }
@@ -1179,40 +1131,51 @@ bool tile48_pays(int batch, int n_cu)
     return rounds_t * kTileRoundInWaveRounds <= rounds_w * 0.93;
 }
 
-int row_family(const TinyBatch *tb)
+// What one solve launches: resolved ONCE per call by resolve_plan(), read by everything that names, prepares, orders or launches the kernel.
+struct KernelPlan
 {
-    if (tb->pm) return 0; // per-instance models: the unrolled 16-lane kernel (resolve_variant_pm refuses every other row kernel)
-    // one wavefront per instance: state on chip where the horizon fits (admm_waveres.hip, 6), else streamed through HBM (admm_wave.hip, 3)
-    // (7: sixteen instances per workgroup on the matrix cores, admm_tile48.hip: fp32 storage)
+    Kernel kernel = Kernel::Rowlane;
+    bool exact = true;   // arithmetic: the reference's summation order, or fma
+    bool pm = false;     // per-instance models (the ",pm" instantiations of the 16-lane and the run-time-dimension kernel)
+    bool pi = false;     // tile16 with per-instance bounds / reference (admm_tile16_pi.hip)
+    Tile16Pi pi_tables{}; // ... and which of its tables go through the rings
+};
+
+// the row / wave kernel a row variant launches for this handle (resolve_plan's second half; `forced`: tiny_batch_set_row_kernel)
+Kernel row_kernel_for(const TinyBatch *tb, bool closed_loop)
+{
+    const std::optional<Kernel> forced = tb->row_family_forced;
+    // one wavefront per instance: state on chip where the horizon fits (admm_waveres.hip), else streamed through HBM (admm_wave.hip)
+    // (tile48: sixteen instances per workgroup on the matrix cores, admm_tile48.hip: fp32 storage)
     if (tb->wave_ok)
     {
-        if (tb->row_family_forced == 3) return 3;
-        if (tb->tile48_ok && !tb->h16 && (tb->row_family_forced == 7 || (tb->row_family_forced < 0 && tile48_pays(tb->batch, tb->n_cu)))) return 7;
-        return tb->waveres_ok ? 6 : 3;
+        if (forced == Kernel::Wavestream) return Kernel::Wavestream;
+        if (tb->tile48_ok && !tb->h16 && (forced == Kernel::Tile48 || (!forced && tile48_pays(tb->batch, tb->n_cu)))) return Kernel::Tile48;
+        return tb->waveres_ok ? Kernel::Waveres : Kernel::Wavestream;
     }
     // per-instance bounds: the unrolled register-resident kernel (fp32 storage) and the rolled-loop ones (N <= 64, either storage)
     // read them from the [B][N][16] table, the streaming row kernel serves every other case; the quad kernel stages one shared table
     // the optional terms (Uref, coeff_d2p): on the unrolled register-resident kernel since round 4 (fp32 storage, batch-shared bounds, one solve per
     // launch); every other combination — fp16 storage, per-instance bounds, a closed-loop run, another forced family — on the streaming row kernel
-    if ((tb->en_uref || tb->en_d2p) && tb->row_dims_ok && !tb->h16 && bounds_all_shared(tb) && !tb->closed_loop_run &&
-        (tb->row_family_forced < 0 || tb->row_family_forced == 0))
-        return 0;
+    const bool optional_terms = tb->en_uref || tb->en_d2p;
+    if (optional_terms && tb->row_dims_ok && !tb->h16 && bounds_all_shared(tb) && !closed_loop && (!forced || forced == Kernel::Rowlane))
+        return Kernel::Rowlane;
     if (!bounds_all_shared(tb))
     {
-        if (tb->en_uref || tb->en_d2p) return 2;
-        if (tile16_applies(tb) && (tb->row_family_forced == 5 || (tb->row_family_forced < 0 && tile16_pi_auto(tb)))) return 5;
-        const int ff = tb->row_family_forced == 5 ? -1 : tb->row_family_forced; // tile16 asked for but not applicable (closed-loop run): like auto
-        if (tb->row_dims_ok && !tb->h16 && (ff < 0 || ff == 0)) return 0;
-        if (tb->rowloop_ok && (ff < 0 || ff == 1)) return 1; // one step ahead from global memory
-        return 2;
+        if (optional_terms) return Kernel::Rowstream;
+        if (tile16_applies(tb, closed_loop) && (forced == Kernel::Tile16 || (!forced && tile16_pi_auto(tb)))) return Kernel::Tile16;
+        const std::optional<Kernel> ff = forced == Kernel::Tile16 ? std::nullopt : forced; // tile16 asked for but not applicable (closed-loop run): like auto
+        if (tb->row_dims_ok && !tb->h16 && (!ff || ff == Kernel::Rowlane)) return Kernel::Rowlane;
+        if (tb->rowloop_ok && (!ff || ff == Kernel::Rowloop)) return Kernel::Rowloop; // one step ahead from global memory
+        return Kernel::Rowstream;
     }
-    if (tb->en_uref || tb->en_d2p) return 2; // the optional terms live in the streaming row kernel (c's u rows hold d elsewhere)
-    // 5 = sixteen instances per wave, products on the matrix cores (admm_tile16.hip): on request only; needs fp32 storage and
+    if (optional_terms) return Kernel::Rowstream; // the optional terms live in the streaming row kernel (c's u rows hold d elsewhere)
+    // sixteen instances per wave, products on the matrix cores (admm_tile16.hip): on request only; needs fp32 storage and
     // a reference it does not have to keep resident (window of a table, or one shared reference)
-    if (tb->row_family_forced == 5)
-        return tile16_applies(tb) ? 5 : (tb->row_dims_ok ? 0 : (tb->rowloop_ok ? 1 : 2));
-    if (tb->row_family_forced >= 0) return tb->row_family_forced;
-    if (tb->quad_ok) return 4; // four lanes per instance (admm_quadlane.hip): nx = 4, nu = 1
+    if (forced == Kernel::Tile16)
+        return tile16_applies(tb, closed_loop) ? Kernel::Tile16 : (tb->row_dims_ok ? Kernel::Rowlane : (tb->rowloop_ok ? Kernel::Rowloop : Kernel::Rowstream));
+    if (forced) return *forced;
+    if (tb->quad_ok) return Kernel::Quadlane; // four lanes per instance (admm_quadlane.hip): nx = 4, nu = 1
     // auto (round 3): sixteen instances per wave on the matrix cores where the launch is at least two rounds deep for its one
     // wave per SIMD (2 048 tiles) — measured 1.79 against 1.91 ms on 65 536 tracking instances; smaller launches fill the chip
     // better with four instances per wave, and a closed-loop run keeps the kernel whose MPC loop stays on chip
@@ -1221,54 +1184,120 @@ int row_family(const TinyBatch *tb)
     // (round 4: tile16's MPC loop stays on chip too — tiny_batch_set_row_kernel(tb, 5) — but the warm-started solves of a closed loop are short and
     //  uneven, and sixteen instances in lock step lose more there than the matrix cores gain: measured 1.02 ms per MPC step of 65 536 tracking
     //  instances against 0.97 ms on the 16-lane kernel, so the automatic choice of a closed-loop run stays with the latter)
-    if (tile16_applies(tb) && !tb->order_dev && (tb->closed_loop_run ? tile16_closed_loop_size(tb) : tile16_auto_size(tb))) return 5;
-    if (tb->row_dims_ok) return 0;
-    if (tb->rowloop_ok) return 1;
-    return 2;
+    if (tile16_applies(tb, closed_loop) && !tb->order_dev && (closed_loop ? tile16_closed_loop_size(tb) : tile16_auto_size(tb))) return Kernel::Tile16;
+    if (tb->row_dims_ok) return Kernel::Rowlane; // unrolled register-resident (fastest, one instantiation per (nx, nu, N))
+    if (tb->rowloop_ok) return Kernel::Rowloop;  // rolled-loop register-resident (any N <= 64)
+    return Kernel::Rowstream;                    // any N with the state in HBM
 }
 
-hipError_t launch_tile16_pi(const TinyBatch *tb, bool exact, RowParams &P)
+// the plan of a resolved variant v (not VAR_AUTO) whose row variants launch `row`
+int plan_of(const TinyBatch *tb, int v, Kernel row, KernelPlan *out)
 {
-    const Tile16Pi pl = tile16_pi_plan(tb);
-    P.pi_flags = pl.flags;
-    // ring tables are read from their tile images (a window of the trajectory table through the ring: from the table's rows)
-    if (pl.bounds_ring && (pl.flags & 1u))
-    {
-        if (!tb->r_bounds_img) return hipErrorInvalidValue;
-        P.bounds = tb->r_bounds_img;
-    }
-    if (pl.xref_ring && (pl.flags & 2u))
-    {
-        if (!tb->r_xref_img) return hipErrorInvalidValue;
-        P.xref = tb->r_xref_img;
-    }
-    return launch_admm_tile16_pi(tb->N, exact, pl.bounds_ring, pl.xref_ring, P, tb->stream, tb->n_cu, tb->tile_queue);
+    out->kernel = v == VAR_STREAM ? Kernel::Stream : (v == VAR_GENERIC ? Kernel::Generic : row);
+    out->exact = v == VAR_ROW_EXACT || v == VAR_GENERIC;
+    out->pm = tb->pm;
+    out->pi = out->kernel == Kernel::Tile16 && tile16_per_instance(tb);
+    if (out->pi) out->pi_tables = tile16_pi_plan(tb);
+    return 0;
 }
 
-void update_kname(TinyBatch *tb)
+// THE policy: which kernel serves this handle, in which arithmetic.  `closed_loop`: the call is a tiny_batch_mpc_run_*(steps > 1) — the automatic choice
+// then keeps the kernel with the on-chip MPC loop.  Reads the handle and changes nothing; the answer depends on rows_vary, which prepare_inputs() fills.
+int resolve_plan(const TinyBatch *tb, bool closed_loop, KernelPlan *out)
 {
-    int v = 0;
+    int v = tb->variant;
+    if (tb->pm)
+    {
+        // per-instance models: the unrolled 16-lane kernel where (nx, nu, N) is instantiated, the run-time-dimension kernel otherwise (both read a gain
+        // record per instance).  Every other kernel keeps ONE gain table for the whole launch — tile16's MFMA A operand is one gain matrix for all sixteen
+        // columns, the streaming and wave kernels stage theirs once per workgroup — and is never chosen.
+        if (tb->h16)
+            return fail(TINY_BATCH_EUNSUPPORTED, "per-instance models (tiny_batch_set_models) are implemented for fp32 storage only: tiny_batch_set_storage(tb, 32) or tiny_batch_clear_models()");
+        if (tb->en_uref || tb->en_d2p)
+            return fail(TINY_BATCH_EUNSUPPORTED, "the optional Uref / coeff_d2p terms are not implemented with per-instance models (tiny_batch_set_optional_terms(tb, 0, 0) or tiny_batch_clear_models())");
+        if (v == VAR_STREAM)
+            return fail(TINY_BATCH_EUNSUPPORTED, "the streaming MFMA kernel (variant 1) holds one gain matrix for the whole launch and cannot serve per-instance models");
+        if (v == VAR_AUTO)
+        {
+            if (!tb->row_dims_ok && !tb->generic_ok)
+                return fail(TINY_BATCH_EUNSUPPORTED, "per-instance models need the unrolled 16-lane kernel (an instantiated nx, nu, N) or the run-time-dimension exact kernel "
+                                                     "(nx, nu each <= 4 or a multiple of 4); nx=%d nu=%d N=%d has neither", tb->nx, tb->nu, tb->N);
+            v = tb->row_dims_ok ? VAR_ROW_EXACT : VAR_GENERIC;
+        }
+        if (v == VAR_ROW_EXACT || v == VAR_ROW_FAST)
+        {
+            if (!tb->row_dims_ok)
+                return fail(TINY_BATCH_EUNSUPPORTED, "with per-instance models the row variants run on the unrolled 16-lane kernel only, which has no instantiation for nx=%d nu=%d N=%d "
+                                                     "(variant 4, the run-time-dimension exact kernel, serves it)", tb->nx, tb->nu, tb->N);
+            if (tb->row_family_forced && tb->row_family_forced != Kernel::Rowlane)
+                return fail(TINY_BATCH_EUNSUPPORTED, "the forced row kernel (tiny_batch_set_row_kernel) keeps one gain table for the whole launch and cannot serve per-instance models "
+                                                     "(tile16: its MFMA A operand is one gain matrix for all 16 columns); only the 16-lane kernel (1) or auto (0) can");
+        }
+        if (v == VAR_GENERIC && !tb->generic_ok)
+            return fail(TINY_BATCH_EUNSUPPORTED, "the run-time-dimension exact kernel (variant 4) needs nx, nu each <= 4 or a multiple of 4 (nx=%d nu=%d)", tb->nx, tb->nu);
+        return plan_of(tb, v, Kernel::Rowlane, out);
+    }
+    // row variants: register-resident kernel when (nx,nu,N) is instantiated, else the any-N row kernel with the state in HBM
+    // per-instance bounds: the streaming row kernel and the wave kernel read them per instance; the register-resident
+    // kernels stage ONE table in LDS and need batch-shared bounds
+    const bool row_ok = tb->row_dims_ok || tb->rowmath_ok || tb->wave_ok;
+    const Kernel row = row_kernel_for(tb, closed_loop);
+    if (v == VAR_ROW_FAST && tb->wave_ok && row != Kernel::Waveres && row != Kernel::Tile48)
+        return fail(TINY_BATCH_EUNSUPPORTED, "fma arithmetic for 16 < nx + nu <= 64 needs the state-on-chip wave kernel (N <= 50); beyond that it is the streaming MFMA kernel (variant 1)");
+    if (v == VAR_AUTO)
+    {
+        // the automatic choice is exact arithmetic or nothing: a class without a compiled exact kernel runs in fma arithmetic on the padded
+        // MFMA kernel only when the caller has asked for it by name (round 4: it used to be selected silently)
+        if (!row_ok && !tb->generic_ok)
+            return fail(TINY_BATCH_EUNSUPPORTED, "nx=%d nu=%d has no exact-arithmetic kernel (the reference's own summation order depends on column alignment "
+                                                 "unless nx and nu are each <= 4 or a multiple of 4); tiny_batch_select_kernel(tb, 1) opts into fma arithmetic "
+                                                 "on the MFMA streaming kernel", tb->nx, tb->nu);
+        v = row_ok ? VAR_ROW_EXACT : VAR_GENERIC; // a class outside the compiled lists: exact arithmetic with run-time dimensions (admm_generic.hip)
+    }
+    if (v == VAR_GENERIC && (!tb->generic_ok || tb->h16 || tb->en_uref || tb->en_d2p))
+        return fail(TINY_BATCH_EUNSUPPORTED, "the run-time-dimension exact kernel (variant 4) needs nx, nu each <= 4 or a multiple of 4 (nx <= 64, nu <= 32), "
+                                             "fp32 storage and no optional terms (nx=%d nu=%d)", tb->nx, tb->nu);
+    const bool row_variant = v == VAR_ROW_EXACT || v == VAR_ROW_FAST;
+    if ((tb->en_uref || tb->en_d2p) && (!tb->rowmath_ok || !row_variant))
+        return fail(TINY_BATCH_EUNSUPPORTED, "the optional Uref / coeff_d2p terms (tiny_batch_set_optional_terms) are implemented by the row "
+                                             "kernels for nx + nu <= 16 only (nx=%d nu=%d, variant %d)", tb->nx, tb->nu, v);
+    if (row_variant && !row_ok)
+        return fail(TINY_BATCH_EUNSUPPORTED, "no row kernel instantiation for nx=%d nu=%d (needs nx + nu <= 16)", tb->nx, tb->nu);
+    if (v == VAR_STREAM && !tb->tile_dims_ok)
+        return fail(TINY_BATCH_EUNSUPPORTED, "no streaming kernel instantiation for nx=%d nu=%d", tb->nx, tb->nu);
+    if (v == VAR_STREAM && tb->h16)
+        return fail(TINY_BATCH_EUNSUPPORTED, "fp16 storage is implemented by the row kernels only (nx + nu <= 16)");
+    return plan_of(tb, v, row, out);
+}
+
+// the name tiny_batch_kernel_name() reports: "<family><nx,nu[,N],arithmetic[,h16 | ,h16d | ,pi | ,pm]>"; the streaming kernel is named by its chunk counts
+std::string kernel_name(const TinyBatch *tb, const KernelPlan &pl)
+{
+    const KernelTraits &t = traits(pl.kernel);
     char nm[96];
-    const std::string keep = g_err;
-    if (resolve_variant(tb, &v)) { tb->kname = "unsupported"; g_err = keep; return; }
-    const bool d32 = tb->h16 && (tb->dual32_forced ? tb->dual32 : (tb->dual32_pref && !tile_variant(v) && family_keeps_fp32_duals(row_family(tb))));
-    const char *ar = v == VAR_ROW_EXACT ? "exact" : "fast", *sto = tb->h16 ? (d32 ? ",h16d" : ",h16") : "";
-    if (tb->pm) // per-instance models: the kernels that read a gain record per instance, marked ",pm"
+    if (pl.kernel == Kernel::Stream)
     {
-        if (v == VAR_GENERIC) snprintf(nm, sizeof nm, "generic<%d,%d,exact,pm>", tb->nx, tb->nu);
-        else snprintf(nm, sizeof nm, "rowlane<%d,%d,%d,%s,pm>", tb->nx, tb->nu, tb->N, ar);
+        snprintf(nm, sizeof nm, "stream<%d,%d>", tb->NXC, tb->NUC);
+        return nm;
     }
-    else if (v == VAR_STREAM) snprintf(nm, sizeof nm, "stream<%d,%d>", tb->NXC, tb->NUC);
-    else if (v == VAR_GENERIC) snprintf(nm, sizeof nm, "generic<%d,%d,exact>", tb->nx, tb->nu);
-    else if (row_family(tb) == 0) snprintf(nm, sizeof nm, "rowlane<%d,%d,%d,%s%s>", tb->nx, tb->nu, tb->N, ar, sto);
-    else if (row_family(tb) == 1) snprintf(nm, sizeof nm, "rowloop<%d,%d,%s%s>", tb->nx, tb->nu, ar, sto);
-    else if (row_family(tb) == 3) snprintf(nm, sizeof nm, "wavestream<%d,%d,%s>", tb->nx, tb->nu, ar);
-    else if (row_family(tb) == 6) snprintf(nm, sizeof nm, "waveres<%d,%d,%s>", tb->nx, tb->nu, ar);
-    else if (row_family(tb) == 7) snprintf(nm, sizeof nm, "tile48<%d,%d,%d,%s>", tb->nx, tb->nu, tb->N, ar);
-    else if (row_family(tb) == 4) snprintf(nm, sizeof nm, "quadlane<%d,%d,%d,%s%s>", tb->nx, tb->nu, tb->N, ar, sto);
-    else if (row_family(tb) == 5) snprintf(nm, sizeof nm, "tile16<%d,%d,%d,%s%s>", tb->nx, tb->nu, tb->N, ar, tile16_per_instance(tb) ? ",pi" : "");
-    else snprintf(nm, sizeof nm, "rowstream<%d,%d,%s%s>", tb->nx, tb->nu, ar, sto);
-    tb->kname = nm;
+    int n = snprintf(nm, sizeof nm, "%s<%d,%d", t.name, tb->nx, tb->nu);
+    if (t.name_has_N) n += snprintf(nm + n, sizeof nm - n, ",%d", tb->N);
+    const bool d32 = tb->dual32_forced ? tb->dual32 : (tb->dual32_pref && t.fp32_duals);
+    const char *suffix = pl.pm ? ",pm" : pl.pi ? ",pi" : (t.name_has_storage && tb->h16) ? (d32 ? ",h16d" : ",h16") : "";
+    snprintf(nm + n, sizeof nm - n, ",%s%s>", pl.exact ? "exact" : "fast", suffix);
+    return nm;
+}
+
+// the name of the kernel a lone solve (closed_loop = false) or a closed-loop run of several steps launches; "unsupported" where no kernel would run.
+// One buffer per question and handle: the pointer holds until the same question is asked of the same handle again
+const char *plan_name(TinyBatch *tb, bool closed_loop)
+{
+    std::string &name = tb->name_buf[closed_loop ? 1 : 0];
+    const std::string keep = g_err;
+    KernelPlan pl;
+    name = resolve_plan(tb, closed_loop, &pl) ? "unsupported" : kernel_name(tb, pl);
+    g_err = keep;
+    return name.c_str();
 }
 
 void fill_row_params(TinyBatch *tb, RowParams &P, bool exact)
@@ -1340,12 +1369,12 @@ int run_step(TinyBatch *tb, int fn, int *converged_host, int *n_true)
     return 0;
 }
 
-// per-instance models: the 16-lane kernel's gain rows in the form variant v computes in, packed from the records when they changed (the run-time-dimension
-// kernel reads the records themselves)
-int pack_models(TinyBatch *tb, int v)
+// per-instance models: the 16-lane kernel's gain rows in the arithmetic the plan computes in, packed from the records when they changed (the
+// run-time-dimension kernel reads the records themselves)
+int pack_models(TinyBatch *tb, const KernelPlan &pl)
 {
-    if (v != VAR_ROW_EXACT && v != VAR_ROW_FAST) return 0;
-    const int f = v == VAR_ROW_FAST ? 1 : 0;
+    if (pl.kernel != Kernel::Rowlane) return 0;
+    const int f = pl.exact ? 0 : 1;
     if (!tb->pm_row_dirty[f]) return 0;
     const long long n = (long long)tb->batch * pm_row_floats(tb->nx, tb->nu);
     if (!tb->pm_row[f]) HIP_TRY(guarded_malloc((void **)&tb->pm_row[f], (size_t)n * sizeof(float)));
@@ -1355,17 +1384,17 @@ int pack_models(TinyBatch *tb, int v)
     return 0;
 }
 
-ModelParams model_params(const TinyBatch *tb, int v)
+ModelParams model_params(const TinyBatch *tb, const KernelPlan &pl)
 {
     ModelParams M;
     M.rho = tb->pm_rho;
-    if (v == VAR_GENERIC) { M.mats = tb->pm_src; M.mats_stride = (unsigned)pm_gen_floats(tb->nx, tb->nu); }
-    else { M.mats = tb->pm_row[v == VAR_ROW_FAST ? 1 : 0]; M.mats_stride = (unsigned)pm_row_floats(tb->nx, tb->nu); }
+    if (pl.kernel == Kernel::Generic) { M.mats = tb->pm_src; M.mats_stride = (unsigned)pm_gen_floats(tb->nx, tb->nu); }
+    else { M.mats = tb->pm_row[pl.exact ? 0 : 1]; M.mats_stride = (unsigned)pm_row_floats(tb->nx, tb->nu); }
     return M;
 }
 
-// everything a solve needs that may allocate, copy or synchronise (not capturable in a hipGraph)
-int prepare_solve(TinyBatch *tb, int *variant)
+// everything a solve needs that may allocate, copy or synchronise (not capturable in a hipGraph); *plan: what the solve launches
+int prepare_solve(TinyBatch *tb, bool closed_loop, KernelPlan *plan)
 {
     if (!(tb->pm || (tb->have_cache && tb->have_dyn)) || !tb->have_settings)
         return fail(TINY_BATCH_ENOTREADY, "tiny_batch_solve: set_cache, set_dynamics (or set_models) and set_settings must be called first");
@@ -1378,9 +1407,12 @@ int prepare_solve(TinyBatch *tb, int *variant)
     }
     TRY(check_optional_terms(tb));
     TRY(set_device(tb));
-    int v = 0;
-    TRY(resolve_variant(tb, &v));
-    if (tb->pm) TRY(pack_models(tb, v));
+    // Provisional: the layout, the gain form and the dual width have to be settled BEFORE prepare_inputs, whose rows_vary the final plan reads.  The two can
+    // differ only between tile16 and another kernel of the ROW layout, in the same arithmetic, under fp32 storage (rows_vary enters through the pi
+    // tables' LDS fit alone, and fp16 storage excludes tile16), where settle_dual_width does nothing
+    KernelPlan pl;
+    TRY(resolve_plan(tb, closed_loop, &pl));
+    if (tb->pm) TRY(pack_models(tb, pl));
     else if (tb->gains_dirty) TRY(pack_gains(tb));
     // (whatever the mode says NOW: a launch sequence enqueued after one prepare_solve — the captured graph of tiny_batch_mpc_run_async — gains a history with its
     //  first solve, and its second one is then dispatched by it)
@@ -1389,100 +1421,147 @@ int prepare_solve(TinyBatch *tb, int *variant)
         TRY(dev_alloc_zero(&tb->key_buf, (size_t)tb->bpad4 / 4 + (size_t)tb->bpad4 / 16 + 16)); // group keys, then tile keys
         TRY(dev_alloc_zero((float **)&tb->order_buf, (size_t)tb->bpad4 / 4));
     }
-    {
-        const int layout = tile_variant(v) ? LAYOUT_TILE : LAYOUT_ROW;
-        TRY(ensure_layout(tb, layout));
-        TRY(settle_dual_width(tb, layout == LAYOUT_ROW && family_keeps_fp32_duals(row_family(tb))));
-        TRY(prepare_inputs(tb, layout));
-    }
+    const int layout = traits(pl.kernel).layout;
+    const bool inputs_rebuilt = tb->derived_dirty[layout];
+    TRY(ensure_layout(tb, layout));
+    TRY(settle_dual_width(tb, traits(pl.kernel).fp32_duals));
+    TRY(prepare_inputs(tb, layout));
     TRY(flush_x0_zero(tb)); // every solve reads x.col(0)
     if (tb->max_iter <= 0) TRY(flush_pending(tb));
     // A cold start that converges in its first iteration (x0 at the origin) runs no backward sweep, which is what writes p, d, v, z.
     // reset_workspace() is folded into the launch by every fused kernel: the register-resident ones start from zero registers,
     // the streaming ones (MFMA, rowstream, wavestream) read zeros in their first iteration and zero-fill p, d, v, z of such an
     // instance in their epilogue
-    update_kname(tb);
-    *variant = v;
+    if (inputs_rebuilt) return resolve_plan(tb, closed_loop, plan);
+    *plan = pl; // rows_vary did not move: the provisional plan is the final one
     return 0;
 }
 
-// the stream operations of one solve: counter reset + kernel launch (capturable)
-
-int enqueue_solve(TinyBatch *tb, int v, bool record_events)
+void fill_solve_params(const TinyBatch *tb, SolveParams &P)
 {
-    const int layout = tile_variant(v) ? LAYOUT_TILE : LAYOUT_ROW;
-    // longest-first dispatch (dispatch_order.hip): predictor sweep + bucket sort ahead of the register-resident 16-lane kernels;
-    // pays off only when the launch is several rounds of waves deep
-    const int fam_l = layout == LAYOUT_ROW ? row_family(tb) : -1;
+    P.nx = tb->nx; P.nu = tb->nu; P.N = tb->N; P.batch = tb->batch; P.ntiles = tb->ntiles;
+    P.rho = tb->rho; P.abs_pri_tol = tb->abs_pri_tol; P.abs_dua_tol = tb->abs_dua_tol;
+    P.max_iter = tb->max_iter; P.check_termination = tb->check_termination;
+    P.en_state_bound = tb->en_state_bound; P.en_input_bound = tb->en_input_bound;
+    P.duals_zero = tb->duals_zero_pending ? 1 : 0;
+    P.cold_start = tb->cold_pending ? 1 : 0;
+    P.xref_mode = tb->xref_mode;
+    P.x = tb->arr[TINY_ARR_X]; P.q = tb->arr[TINY_ARR_Q]; P.p = tb->arr[TINY_ARR_P];
+    P.v = tb->arr[TINY_ARR_V]; P.vnew = tb->arr[TINY_ARR_VNEW]; P.g = tb->arr[TINY_ARR_G];
+    P.u = tb->arr[TINY_ARR_U]; P.r = tb->arr[TINY_ARR_R]; P.d = tb->arr[TINY_ARR_D];
+    P.z = tb->arr[TINY_ARR_Z]; P.znew = tb->arr[TINY_ARR_ZNEW]; P.y = tb->arr[TINY_ARR_Y];
+    P.xmin = tb->t_bnd[0]; P.xmax = tb->t_bnd[1]; P.umin = tb->t_bnd[2]; P.umax = tb->t_bnd[3]; P.xref = tb->t_xref;
+    const long long xt = (long long)tb->N * WAVE * tb->NXC, ut = (long long)(tb->N - 1) * WAVE * tb->NUC;
+    P.xb_tile_stride = (tb->in_bnd[0].set && !tb->in_bnd[0].shared) ? xt : 0;
+    P.ub_tile_stride = (tb->in_bnd[2].set && !tb->in_bnd[2].shared) ? ut : 0;
+    P.xref_tile_stride = (tb->in_xref.set && !tb->in_xref.shared) ? xt : 0;
+    P.xref_table = tb->tab_tile; P.xref_start = tb->xref_start; P.table_rows = tb->table_rows;
+    P.res = tb->res; P.status = tb->status; P.iter = tb->iter; P.n_unsolved = tb->n_unsolved;
+    P.opnd = tb->opnd; P.qvec = tb->qvec;
+}
+
+// The dispatch order of one launch (dispatch_order.hip; pays off only when the launch is several rounds of waves deep): enqueues the sort by the previous
+// solve's iteration counts (history), the predictor sweep and its sort, or — where neither runs — the reset of the two counters ([0] unsolved count, [1] tile
+// queue of admm_tile16.hip; both sorts zero them themselves: one stream node less), and points P.order at the result.  Returns what tiny_batch_dispatch_applied()
+// reports (0 index order, 1 predicted, 2 the caller's order, 3 history) or a negative error code.
+// run_steps > 1: the launch is the on-chip closed loop of tiny_batch_mpc_run_*; it differs from a lone solve (also each solve of a captured run) in that
+//  * it asks tb->dispatch_mode where a lone solve asks dispatch_effective() for the predictor: flush_pending() has already cleared cold_pending, `from_reset` carries it;
+//  * history wins over the predictor (in a lone solve dispatch_effective() makes them exclusive);
+//  * tile16 orders its tiles by the SUM of the counts (a tile's total over the run), a lone solve by the largest;
+//  * the rolled-loop kernel has no on-chip run (KernelTraits::order_unit_run);
+//  * max_iter > 1 guards the predictor only: the run's later steps profit from the history order whatever the first one does.
+// Common to both: tile16 drops a caller's order, which lists groups of four instances, not tiles of sixteen.
+int enqueue_dispatch_order(TinyBatch *tb, const KernelPlan &pl, int run_steps, bool from_reset, RowParams &P)
+{
+    const bool run = run_steps > 1;
+    const int unit = run ? traits(pl.kernel).order_unit_run : traits(pl.kernel).order_unit_solve;
+    const bool eligible = unit && !tb->order_dev && tb->bpad4 / 4 >= kDispatchMinGroups && tb->order_buf;
+    // a run's tiles / groups go longest first by the counts of the solve before it (the last step of the previous run): a tile's total over the steps
+    // of a run spreads 150 ... 700 iterations around a mean of 280 (65 536 tracking instances, 20 steps) and four tiles per wave slot in index order end
+    // 33 % above even slots; ordered by the previous step's counts 15 % (tests/fuzz/sim_history_dispatch.py)
+    const bool history = eligible && dispatch_effective(tb) == 2 && (run || tb->max_iter > 1);
+    // a run that starts from a reset workspace goes by the predictor of its first, cold solve (which is also its longest: 22 iterations against 11): steps 0 - 19
+    // of the tracking loop, makespan 1 522 iterations in index order, 1 299 by the predictor (by the true first-step counts 1 291; 16-lane kernel 2 336 -> 2 175)
+    const bool want_predicted = run ? (tb->dispatch_mode == 1 || (tb->dispatch_mode == -1 && from_reset)) : dispatch_effective(tb) == 1;
     // (per-instance models: the predictor sweep reads the shared fma gains, which are unset or stale there — such a launch keeps index order)
-    const bool predicted_order = layout == LAYOUT_ROW && dispatch_effective(tb) == 1 && !tb->pm && !tb->order_dev && (fam_l == 0 || fam_l == 1 || fam_l == 5) && !tb->dual32 &&
-                                 tb->bpad4 / 4 >= kDispatchMinGroups && tb->max_iter > 1 && tb->order_buf;
-    // [0] unsolved count, [1] tile queue of admm_tile16.hip: zeroed by the sort kernel of the predicted order where that runs (one stream node less)
-    const bool history_order = layout == LAYOUT_ROW && dispatch_effective(tb) == 2 && !tb->order_dev && (fam_l == 0 || fam_l == 1 || fam_l == 5) &&
-                               tb->bpad4 / 4 >= kDispatchMinGroups && tb->max_iter > 1 && tb->order_buf;
-    if (history_order)
-    {
-        hipError_t ek = launch_dispatch_order_history(tb->iter, tb->batch, fam_l == 5 ? 16 : 4, tb->order_buf, tb->n_unsolved, tb->stream);
-        if (ek != hipSuccess) return fail(TINY_BATCH_EHIP, "kernel launch failed: %s", hipGetErrorString(ek));
-    }
-    else if (!predicted_order) HIP_TRY(hipMemsetAsync(tb->n_unsolved, 0, 2 * sizeof(int), tb->stream));
-    if (predicted_order)
+    const bool predicted = eligible && want_predicted && !history && !pl.pm && !tb->dual32 && tb->max_iter > 1;
+    if (traits(pl.kernel).order_unit_solve == 16) P.order = nullptr; // a caller's order lists groups of four instances, not tiles of sixteen
+    hipError_t e = hipSuccess;
+    if (history) e = launch_dispatch_order_history(tb->iter, tb->batch, unit, tb->order_buf, tb->n_unsolved, tb->stream, run && unit == 16);
+    else if (predicted)
     {
         RowParams K;
         fill_row_params(tb, K, false); // fma gains
-        hipError_t ek = launch_dispatch_order(tb->nx, tb->nu, tb->h16, K, tb->key_buf, tb->order_buf, tb->stream, fam_l == 5);
-        if (ek != hipSuccess) return fail(TINY_BATCH_EHIP, "kernel launch failed: %s", hipGetErrorString(ek));
+        e = launch_dispatch_order(tb->nx, tb->nu, tb->h16, K, tb->key_buf, tb->order_buf, tb->stream, unit == 16);
     }
+    else HIP_TRY(hipMemsetAsync(tb->n_unsolved, 0, 2 * sizeof(int), tb->stream));
+    if (e != hipSuccess) return fail(TINY_BATCH_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
+    if (history || predicted) P.order = tb->order_buf;
+    return history ? 3 : predicted ? 1 : (P.order ? 2 : 0);
+}
+
+// the ONE place that launches a solve kernel.  P: the row-layout arguments (the two TILE-layout kernels take theirs from fill_solve_params)
+hipError_t launch_kernel(const TinyBatch *tb, const KernelPlan &pl, RowParams &P)
+{
+    const int nx = tb->nx, nu = tb->nu, N = tb->N;
+    switch (pl.kernel)
+    {
+    case Kernel::Rowlane:
+        return pl.pm ? launch_admm_rowlane_pm(nx, nu, N, pl.exact, P, model_params(tb, pl), tb->stream) : launch_admm_rowlane(nx, nu, N, pl.exact, tb->h16, P, tb->stream);
+    case Kernel::Rowloop: return launch_admm_rowloop(nx, nu, pl.exact, tb->h16, P, tb->stream);
+    case Kernel::Rowstream: return launch_admm_rowstream(nx, nu, pl.exact, tb->h16, P, tb->stream);
+    case Kernel::Wavestream: return launch_admm_wavestream(nx, nu, P, tb->stream);
+    case Kernel::Quadlane: return launch_admm_quadlane(N, pl.exact, tb->h16, P, tb->stream);
+    case Kernel::Waveres: return launch_admm_waveres(nx, nu, pl.exact, P, tb->stream);
+    case Kernel::Tile48: return launch_admm_tile48(N, pl.exact, P, tb->stream);
+    case Kernel::Tile16:
+    {
+        if (!pl.pi) return launch_admm_tile16(N, pl.exact, P, tb->stream, tb->n_cu, tb->tile_queue);
+        const Tile16Pi &t = pl.pi_tables;
+        P.pi_flags = t.flags;
+        // ring tables are read from their tile images (a window of the trajectory table through the ring: from the table's rows)
+        if (t.bounds_ring && (t.flags & 1u))
+        {
+            if (!tb->r_bounds_img) return hipErrorInvalidValue;
+            P.bounds = tb->r_bounds_img;
+        }
+        if (t.xref_ring && (t.flags & 2u))
+        {
+            if (!tb->r_xref_img) return hipErrorInvalidValue;
+            P.xref = tb->r_xref_img;
+        }
+        return launch_admm_tile16_pi(N, pl.exact, t.bounds_ring, t.xref_ring, P, tb->stream, tb->n_cu, tb->tile_queue);
+    }
+    case Kernel::Stream:
+    case Kernel::Generic:
+    {
+        SolveParams S;
+        fill_solve_params(tb, S);
+        if (pl.kernel == Kernel::Stream) return launch_admm_stream(tb->NXC, tb->NUC, S, tb->stream);
+        return pl.pm ? launch_admm_generic_pm(S, model_params(tb, pl), tb->NXC, tb->NUC, tb->stream) : launch_admm_generic(S, tb->gen_mats, tb->NXC, tb->NUC, tb->stream);
+    }
+    }
+    return hipErrorInvalidValue;
+}
+
+// the stream operations of one solve: dispatch order or counter reset + kernel launch (capturable)
+int enqueue_solve(TinyBatch *tb, const KernelPlan &pl, bool record_events)
+{
+    const KernelTraits &t = traits(pl.kernel);
+    RowParams P;
+    if (t.layout == LAYOUT_ROW)
+    {
+        fill_row_params(tb, P, pl.exact);
+        const int applied = enqueue_dispatch_order(tb, pl, 1, false, P);
+        if (applied < 0) return applied;
+        tb->last_dispatch = applied;
+    }
+    else HIP_TRY(hipMemsetAsync(tb->n_unsolved, 0, 2 * sizeof(int), tb->stream)); // [0] unsolved count
     if (record_events) HIP_TRY(hipEventRecord(tb->ev0, tb->stream)); // the events bracket the solve kernel itself
-    hipError_t e;
-    if (layout == LAYOUT_TILE)
-    {
-        SolveParams P;
-        P.nx = tb->nx; P.nu = tb->nu; P.N = tb->N; P.batch = tb->batch; P.ntiles = tb->ntiles;
-        P.rho = tb->rho; P.abs_pri_tol = tb->abs_pri_tol; P.abs_dua_tol = tb->abs_dua_tol;
-        P.max_iter = tb->max_iter; P.check_termination = tb->check_termination;
-        P.en_state_bound = tb->en_state_bound; P.en_input_bound = tb->en_input_bound;
-        P.duals_zero = tb->duals_zero_pending ? 1 : 0;
-        P.cold_start = tb->cold_pending ? 1 : 0;
-        P.xref_mode = tb->xref_mode;
-        P.x = tb->arr[TINY_ARR_X]; P.q = tb->arr[TINY_ARR_Q]; P.p = tb->arr[TINY_ARR_P];
-        P.v = tb->arr[TINY_ARR_V]; P.vnew = tb->arr[TINY_ARR_VNEW]; P.g = tb->arr[TINY_ARR_G];
-        P.u = tb->arr[TINY_ARR_U]; P.r = tb->arr[TINY_ARR_R]; P.d = tb->arr[TINY_ARR_D];
-        P.z = tb->arr[TINY_ARR_Z]; P.znew = tb->arr[TINY_ARR_ZNEW]; P.y = tb->arr[TINY_ARR_Y];
-        P.xmin = tb->t_bnd[0]; P.xmax = tb->t_bnd[1]; P.umin = tb->t_bnd[2]; P.umax = tb->t_bnd[3]; P.xref = tb->t_xref;
-        const long long xt = (long long)tb->N * WAVE * tb->NXC, ut = (long long)(tb->N - 1) * WAVE * tb->NUC;
-        P.xb_tile_stride = (tb->in_bnd[0].set && !tb->in_bnd[0].shared) ? xt : 0;
-        P.ub_tile_stride = (tb->in_bnd[2].set && !tb->in_bnd[2].shared) ? ut : 0;
-        P.xref_tile_stride = (tb->in_xref.set && !tb->in_xref.shared) ? xt : 0;
-        P.xref_table = tb->tab_tile; P.xref_start = tb->xref_start; P.table_rows = tb->table_rows;
-        P.res = tb->res; P.status = tb->status; P.iter = tb->iter; P.n_unsolved = tb->n_unsolved;
-        P.opnd = tb->opnd; P.qvec = tb->qvec;
-        e = v == VAR_GENERIC ? (tb->pm ? launch_admm_generic_pm(P, model_params(tb, v), tb->NXC, tb->NUC, tb->stream)
-                                       : launch_admm_generic(P, tb->gen_mats, tb->NXC, tb->NUC, tb->stream))
-                             : launch_admm_stream(tb->NXC, tb->NUC, P, tb->stream);
-    }
-    else
-    {
-        RowParams P;
-        fill_row_params(tb, P, v == VAR_ROW_EXACT);
-        if (predicted_order || history_order) P.order = tb->order_buf;
-        const int fam = row_family(tb);
-        if (fam == 5 && !predicted_order && !history_order) P.order = nullptr; // a caller's order lists groups of four instances, not tiles of sixteen
-        tb->last_dispatch = predicted_order ? 1 : history_order ? 3 : (P.order ? 2 : 0);
-        if (P.dual32 && fam != 0 && fam != 4)
-            return fail(TINY_BATCH_EUNSUPPORTED, "fp16 storage with fp32 duals runs on the register-resident 16-lane and quad kernels only "
-                                                 "(batch-shared bounds, no optional terms, no forced row kernel)");
-        e = fam == 0   ? (tb->pm ? launch_admm_rowlane_pm(tb->nx, tb->nu, tb->N, v == VAR_ROW_EXACT, P, model_params(tb, v), tb->stream)
-                                 : launch_admm_rowlane(tb->nx, tb->nu, tb->N, v == VAR_ROW_EXACT, tb->h16, P, tb->stream))
-            : fam == 1 ? launch_admm_rowloop(tb->nx, tb->nu, v == VAR_ROW_EXACT, tb->h16, P, tb->stream)
-            : fam == 3 ? launch_admm_wavestream(tb->nx, tb->nu, P, tb->stream)
-            : fam == 4 ? launch_admm_quadlane(tb->N, v == VAR_ROW_EXACT, tb->h16, P, tb->stream)
-            : fam == 5 ? (tile16_per_instance(tb) ? launch_tile16_pi(tb, v == VAR_ROW_EXACT, P)
-                                                  : launch_admm_tile16(tb->N, v == VAR_ROW_EXACT, P, tb->stream, tb->n_cu, tb->tile_queue))
-            : fam == 6 ? launch_admm_waveres(tb->nx, tb->nu, v == VAR_ROW_EXACT, P, tb->stream)
-            : fam == 7 ? launch_admm_tile48(tb->N, v == VAR_ROW_EXACT, P, tb->stream)
-                       : launch_admm_rowstream(tb->nx, tb->nu, v == VAR_ROW_EXACT, tb->h16, P, tb->stream);
-    }
+    if (t.layout == LAYOUT_ROW && P.dual32 && !t.fp32_duals)
+        return fail(TINY_BATCH_EUNSUPPORTED, "fp16 storage with fp32 duals runs on the register-resident 16-lane and quad kernels only "
+                                             "(batch-shared bounds, no optional terms, no forced row kernel)");
+    const hipError_t e = launch_kernel(tb, pl, P);
     if (e != hipSuccess) return fail(TINY_BATCH_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
     if (record_events)
     {
@@ -1492,13 +1571,6 @@ int enqueue_solve(TinyBatch *tb, int v, bool record_events)
     if (tb->max_iter > 0) tb->duals_zero_pending = tb->cold_pending = false; // consumed by the kernel's first iteration
     if (tb->max_iter > 0) tb->iter_history = true;                            // iter[] now holds this launch's counts
     return 0;
-}
-
-int launch_solve(TinyBatch *tb)
-{
-    int v = 0;
-    TRY(prepare_solve(tb, &v));
-    return enqueue_solve(tb, v, tb->timing);
 }
 
 int enqueue_plant_step(TinyBatch *tb, int window_advance)
@@ -1603,7 +1675,6 @@ int tiny_batch_create(TinyBatch **out, int nx, int nu, int N, int batch, int dev
     if (hipEventCreate(&tb->ev0) != hipSuccess || hipEventCreate(&tb->ev1) != hipSuccess)
         return cleanup(fail(TINY_BATCH_EHIP, "hipEventCreate failed"));
     tb->cold_pending = true; // a fresh workspace IS a reset one (every array was allocated zero): its first solve is a cold start, like one after tiny_batch_reset_workspace
-    update_kname(tb);
     *out = tb;
     return TINY_BATCH_OK;
 }
@@ -1692,7 +1763,6 @@ int tiny_batch_set_models_device(TinyBatch *tb, const float *d_rho, const float 
     HIP_TRY(hipGetLastError());
     tb->pm = true;
     tb->pm_row_dirty[0] = tb->pm_row_dirty[1] = true; // the packed rows follow the records
-    update_kname(tb);
     return 0;
 }
 
@@ -1754,7 +1824,6 @@ int tiny_batch_clear_models(TinyBatch *tb)
     }
     tb->pm_row_dirty[0] = tb->pm_row_dirty[1] = true;
     tb->pm = false;
-    update_kname(tb);
     return 0;
 }
 
@@ -1850,7 +1919,6 @@ int tiny_batch_set_optional_terms(TinyBatch *tb, int en_uref, int en_coeff_d2p)
     tb->en_uref = en_uref != 0;
     tb->en_d2p = en_coeff_d2p != 0;
     invalidate_graph(tb);
-    update_kname(tb);
     return 0;
 }
 
@@ -1909,8 +1977,7 @@ int tiny_batch_set_dispatch_order_device(TinyBatch *tb, const int *d_order)
 {
     CHECK_TB(tb);
     tb->order_dev = d_order;
-    invalidate_graph(tb);
-    update_kname(tb); // a caller's order keeps the 16-lane kernel it is written for
+    invalidate_graph(tb); // (a caller's order keeps the 16-lane kernel it is written for)
     return 0;
 }
 
@@ -2008,7 +2075,9 @@ int tiny_batch_reset_dual_variables(TinyBatch *tb)
 int tiny_batch_solve_async(TinyBatch *tb)
 {
     CHECK_TB(tb);
-    return launch_solve(tb);
+    KernelPlan pl;
+    TRY(prepare_solve(tb, false, &pl));
+    return enqueue_solve(tb, pl, tb->timing);
 }
 
 int tiny_batch_wait(TinyBatch *tb, int *n_unsolved)
@@ -2052,7 +2121,7 @@ int tiny_batch_group_solve(TinyBatch **tbs, int n, int *n_unsolved)
             if (!tb->own_stream) HIP_TRY(hipStreamCreateWithFlags(&tb->own_stream, hipStreamNonBlocking));
             tb->stream = tb->own_stream;
         }
-        TRY(launch_solve(tb));
+        TRY(tiny_batch_solve_async(tb));
     }
     int total = 0;
     for (int i = 0; i < n; i++)
@@ -2229,16 +2298,7 @@ int tiny_batch_set_xref_device(TinyBatch *tb, const float *d_xref, int shared)
 {
     CHECK_TB(tb); CHECK_PTR(d_xref);
     TRY(set_device(tb));
-    InputArr &in = tb->in_xref;
-    const bool sh = shared != 0;
-    const size_t n = (size_t)(sh ? 1 : tb->batch) * tb->N * tb->nx;
-    if (in.dev && in.shared != sh) { (void)guarded_free(in.dev); in.dev = nullptr; }
-    if (!in.dev) HIP_TRY(guarded_malloc((void **)&in.dev, n * sizeof(float)));
-    HIP_TRY(hipMemcpyAsync(in.dev, d_xref, n * sizeof(float), hipMemcpyDeviceToDevice, tb->stream));
-    in.shared = sh;
-    in.set = true;
-    in.host.clear(); // only the bounds are ever read on the host
-    tb->derived_dirty[0] = tb->derived_dirty[1] = true;
+    TRY(store_input(tb, tb->in_xref, d_xref, shared != 0, tb->N, tb->nx, hipMemcpyDeviceToDevice));
     tb->xref_mode = 0;
     return 0;
 }
@@ -2278,46 +2338,19 @@ int tiny_batch_mpc_run_traj_async(TinyBatch *tb, int steps, int window_advance, 
     const bool from_reset = tb->cold_pending; // (flush_pending materialises the zeros and clears the flag: the run's first solve is the cold one all the same)
     TRY(flush_pending(tb)); // every solve of the run starts from "duals reset, workspace warm"
     tb->duals_zero_pending = true;
-    int v = 0;
-    struct Scope { TinyBatch *t; ~Scope() { t->closed_loop_run = false; } } scope{tb};
-    tb->closed_loop_run = steps > 1;
-    TRY(prepare_solve(tb, &v));
+    KernelPlan pl;
+    TRY(prepare_solve(tb, steps > 1, &pl));
     const size_t u0n = (size_t)tb->batch * tb->nu;
-    const int fam = !tile_variant(v) ? row_family(tb) : -1;
-    if ((fam == 0 || fam == 4 || fam == 5) && !tb->h16 && steps > 1 && bounds_all_shared(tb))
+    if (traits(pl.kernel).onchip_mpc && !tb->h16 && steps > 1 && bounds_all_shared(tb))
     {
         RowParams P;
-        fill_row_params(tb, P, v == VAR_ROW_EXACT);
+        fill_row_params(tb, P, pl.exact);
         P.mpc_steps = steps; P.window_advance = window_advance; P.u0_traj = d_u0_traj;
-        if (fam == 5) P.order = nullptr; // a caller's order lists groups of four instances, not tiles
-        // the run's tiles / groups longest first by the counts of the solve before it (the last step of the previous run): a tile's total over the steps
-        // of a run spreads 150 ... 700 iterations around a mean of 280 (65 536 tracking instances, 20 steps) and four tiles per wave slot in index order end
-        // 33 % above even slots; ordered by the previous step's counts 15 % (tests/fuzz/sim_history_dispatch.py)
-        const bool history_order = dispatch_effective(tb) == 2 && !tb->order_dev && (fam == 0 || fam == 5) && tb->bpad4 / 4 >= kDispatchMinGroups && tb->order_buf;
-        // ... and a run that starts from a reset workspace by the predictor of its first, cold solve (which is also its longest: 22 iterations against 11): steps 0 - 19
-        // of the tracking loop, makespan 1 522 iterations in index order, 1 299 by the predictor (by the true first-step counts 1 291; 16-lane kernel 2 336 -> 2 175)
-        const bool predicted_order = (tb->dispatch_mode == 1 || (tb->dispatch_mode == -1 && from_reset)) && !history_order && !tb->pm && !tb->order_dev && (fam == 0 || fam == 5) && !tb->dual32 && tb->bpad4 / 4 >= kDispatchMinGroups &&
-                                     tb->order_buf && tb->max_iter > 1;
-        if (history_order)
-        {
-            hipError_t ek = launch_dispatch_order_history(tb->iter, tb->batch, fam == 5 ? 16 : 4, tb->order_buf, tb->n_unsolved, tb->stream, fam == 5 /* a tile's total over the run: by the sum */);
-            if (ek != hipSuccess) return fail(TINY_BATCH_EHIP, "kernel launch failed: %s", hipGetErrorString(ek));
-            P.order = tb->order_buf;
-        }
-        else if (predicted_order)
-        {
-            RowParams K;
-            fill_row_params(tb, K, false); // fma gains
-            hipError_t ek = launch_dispatch_order(tb->nx, tb->nu, tb->h16, K, tb->key_buf, tb->order_buf, tb->stream, fam == 5); // (its sort zeroes the two counters)
-            if (ek != hipSuccess) return fail(TINY_BATCH_EHIP, "kernel launch failed: %s", hipGetErrorString(ek));
-            P.order = tb->order_buf;
-        }
-        else HIP_TRY(hipMemsetAsync(tb->n_unsolved, 0, 2 * sizeof(int), tb->stream)); // [0] unsolved count, [1] tile queue of admm_tile16.hip
-        tb->last_dispatch = history_order ? 3 : predicted_order ? 1 : (P.order ? 2 : 0);
-        hipError_t e = fam == 0   ? (tb->pm ? launch_admm_rowlane_pm(tb->nx, tb->nu, tb->N, v == VAR_ROW_EXACT, P, model_params(tb, v), tb->stream)
-                                            : launch_admm_rowlane(tb->nx, tb->nu, tb->N, v == VAR_ROW_EXACT, false, P, tb->stream))
-                       : fam == 5 ? launch_admm_tile16(tb->N, v == VAR_ROW_EXACT, P, tb->stream, tb->n_cu)
-                                  : launch_admm_quadlane(tb->N, v == VAR_ROW_EXACT, false, P, tb->stream);
+        const int applied = enqueue_dispatch_order(tb, pl, steps, from_reset, P);
+        if (applied < 0) return applied;
+        tb->last_dispatch = applied;
+        // (tile16 gets tb->tile_queue like a lone solve: its two-ended queue is off whenever mpc_steps > 1 — t16_tail_stride returns 0 — so the setting changes nothing here)
+        const hipError_t e = launch_kernel(tb, pl, P);
         if (e != hipSuccess) return fail(TINY_BATCH_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
         if (d_u0_traj) TRY(launch_unpack(tb, work_ptr(tb, TINY_ARR_U), d_u0_traj + (size_t)(steps - 1) * u0n, tb->layout, 1, tb->batch, 0, 1));
         TRY(enqueue_plant_step(tb, window_advance));
@@ -2338,7 +2371,7 @@ int tiny_batch_mpc_run_traj_async(TinyBatch *tb, int steps, int window_advance, 
     // in a loop replays one captured graph instead of re-capturing it every step)
     char sig[560];
     snprintf(sig, sizeof sig, "%p|%p|%p|%d|%d|%d|%s|%d|%d|%g|%g|%d|%d|%p|%p|%p|%d|%p|%p|%p|%p|%d%d|%a|%d%d%d|%d%d|%d|%p|%p|%p", (void *)tb->pm_src, (void *)tb->pm_row[0],
-             (void *)tb->pm_row[1], steps, window_advance, v, tb->kname.c_str(), tb->max_iter,
+             (void *)tb->pm_row[1], steps, window_advance, tb->variant, kernel_name(tb, pl).c_str(), tb->max_iter,
              tb->check_termination, (double)tb->abs_pri_tol, (double)tb->abs_dua_tol, tb->xref_mode, tb->table_rows, (void *)tb->pair[0],
              (void *)tb->arr[0], (void *)tb->r_bounds, (int)tb->h16, (void *)tb->stream, (void *)d_u0_traj, (void *)tb->r_xref,
              (void *)tb->r_uref, (int)tb->en_uref, (int)tb->en_d2p, (double)tb->rho, (int)bounds_all_shared(tb),
@@ -2353,7 +2386,7 @@ int tiny_batch_mpc_run_traj_async(TinyBatch *tb, int steps, int window_advance, 
         for (int k = 0; k < steps && rc == 0; k++)
         {
             tb->duals_zero_pending = true;
-            rc = enqueue_solve(tb, v, false);
+            rc = enqueue_solve(tb, pl, false);
             if (rc == 0 && d_u0_traj) rc = launch_unpack(tb, work_ptr(tb, TINY_ARR_U), d_u0_traj + (size_t)k * u0n, tb->layout, 1, tb->batch, 0, 1);
             if (rc == 0) rc = enqueue_plant_step(tb, window_advance);
         }
@@ -2434,12 +2467,11 @@ const char *tiny_batch_kernel_name(TinyBatch *tb)
     if (tb->tile16_ok && !tb->h16 && tb->derived_dirty[LAYOUT_ROW] && tile16_per_instance(tb))
     {
         const std::string keep = g_err;
-        int v = 0;
-        (void)prepare_solve(tb, &v); // (not ready yet: the name is then the one the present knowledge gives)
+        KernelPlan pl;
+        (void)prepare_solve(tb, false, &pl); // (not ready yet: the name is then the one the present knowledge gives)
         g_err = keep;
     }
-    update_kname(tb);
-    return tb->kname.c_str();
+    return plan_name(tb, false);
 }
 
 int tiny_batch_debug_graph_captures(TinyBatch *tb)
@@ -2495,9 +2527,9 @@ int tiny_batch_debug_poke(TinyBatch *tb, int which)
 int tiny_batch_arithmetic(TinyBatch *tb)
 {
     CHECK_TB(tb);
-    int v = 0;
-    TRY(resolve_variant(tb, &v));
-    return (v == VAR_ROW_EXACT || v == VAR_GENERIC) ? TINY_BATCH_ARITH_EXACT : TINY_BATCH_ARITH_FMA;
+    KernelPlan pl;
+    TRY(resolve_plan(tb, false, &pl));
+    return pl.exact ? TINY_BATCH_ARITH_EXACT : TINY_BATCH_ARITH_FMA;
 }
 
 // the kernel a closed-loop run of several steps (tiny_batch_mpc_run_async) launches: it can differ from the kernel of a lone solve (the automatic
@@ -2505,14 +2537,7 @@ int tiny_batch_arithmetic(TinyBatch *tb)
 const char *tiny_batch_closed_loop_kernel_name(TinyBatch *tb)
 {
     if (!tb) return "";
-    static thread_local std::string name;
-    const bool keep = tb->closed_loop_run;
-    tb->closed_loop_run = true;
-    update_kname(tb);
-    name = tb->kname;
-    tb->closed_loop_run = keep;
-    update_kname(tb);
-    return name.c_str();
+    return plan_name(tb, true);
 }
 
 int tiny_batch_set_row_kernel(TinyBatch *tb, int family)
@@ -2520,13 +2545,12 @@ int tiny_batch_set_row_kernel(TinyBatch *tb, int family)
     CHECK_TB(tb);
     if (family < 0 || family > 8)
         return fail(TINY_BATCH_EINVAL, "row kernel must be 0 (auto), 1 (rowlane), 2 (rowloop), 3 (rowstream), 4 (quadlane), 5 (tile16), 6 (wavestream), 7 (waveres) or 8 (tile48)");
-    const bool ok = family == 0 || (family == 1 && tb->row_dims_ok) || (family == 2 && tb->rowloop_ok) || (family == 3 && tb->rowmath_ok) ||
-                    (family == 4 && tb->quad_ok) || (family == 5 && tb->tile16_ok) || (family == 6 && tb->wave_ok) || (family == 7 && tb->waveres_ok) ||
-                    (family == 8 && tb->tile48_ok);
-    if (!ok)
+    std::optional<Kernel> forced; // the kernel with that number, if the class has an instantiation of it
+    for (const KernelTraits &t : kKernelTraits)
+        if (family && t.row_kernel_number == family && tb->*t.has) forced = (Kernel)(&t - kKernelTraits);
+    if (family && !forced)
         return fail(TINY_BATCH_EUNSUPPORTED, "row kernel %d has no instantiation for nx=%d nu=%d N=%d", family, tb->nx, tb->nu, tb->N);
-    static const int kFam[9] = {-1, 0, 1, 2, 4, 5, 3, 6, 7};
-    tb->row_family_forced = kFam[family];
+    tb->row_family_forced = forced;
     invalidate_graph(tb);
     return 0;
 }
@@ -2585,11 +2609,11 @@ int tiny_batch_select_kernel(TinyBatch *tb, int variant)
         return fail(TINY_BATCH_EINVAL, "variant must be 0 (auto), 1 (streaming, fma), 2 (row / wave kernels, exact), 3 (row / wave kernels, fma) or 4 (run-time dimensions, exact)");
     const int old = tb->variant;
     tb->variant = variant;
-    int v = 0;
-    if (int rc = resolve_variant(tb, &v)) { tb->variant = old; return rc; }
+    KernelPlan pl;
+    if (int rc = resolve_plan(tb, false, &pl)) { tb->variant = old; return rc; }
     invalidate_graph(tb);
     TRY(set_device(tb));
-    TRY(ensure_layout(tb, tile_variant(v) ? LAYOUT_TILE : LAYOUT_ROW));
+    TRY(ensure_layout(tb, traits(pl.kernel).layout));
     return 0;
 }
 
