@@ -75,20 +75,12 @@ __global__ __launch_bounds__(WAVE) void admm_step_kernel(const RowParams P, cons
     else if (fn == STEP_UPDATE_LINEAR_COST) // admm.cpp:77-85  r, q, p.col(N-1)
     {
         const float qrow = P.mats[(2 * NX + 2 * NU) * 16 + r16], rrow = input_cost_row<NX, NU>(P.mats, r16);
-        int wstart = 0;
-        if (P.xref_mode == 1 && valid) wstart = P.xref_start[inst];
-        const int xref_off = inst * (int)P.xref_inst_stride + r16, uref_off = inst * (int)P.uref_inst_stride + r16;
+        const RowXref<H16> xref(P, inst, valid, inst, r16);
+        const int uref_off = inst * (int)P.uref_inst_stride + r16;
         float xr = 0.f, t1 = 0.f;
         for (int i = 0; i < N; i++)
         {
-            if (P.xref_mode == 1)
-            {
-                int row = wstart + i;
-                row = row < P.table_rows ? row : P.table_rows - 1;
-                xr = ldw<H16>(P.xref_table, row * 16 + r16);
-            }
-            else
-                xr = ldw<H16>(P.xref, xref_off + i * 16);
+            xr = xref.at(P, i, r16);
             const float cq = cost_of<H16>(P, is_x, is_u, xr, qrow, rrow, uref_off + i * 16);
             t1 = ldw<H16>(P.vzn, rowbase + i * 16) - ldw<H16>(P.gy, rowbase + i * 16);
             const float lin = lin_cost<EXACT, H16>(cq, rho, t1);
@@ -110,14 +102,10 @@ __global__ __launch_bounds__(WAVE) void admm_step_kernel(const RowParams P, cons
                 pri = fmaxf(pri, fabsf(sv - t));
                 dua = fmaxf(dua, fabsf(ldw<H16>(P.vz, rowbase + i * 16) - t));
             }
-            const float r_ps = row_max(is_x ? pri : 0.f), r_ds = row_max(is_x ? dua : 0.f) * rho;
-            const float r_pi = row_max(is_u ? pri : 0.f), r_di = row_max(is_u ? dua : 0.f) * rho;
-            conv = (r_ps < P.abs_pri_tol) && (r_pi < P.abs_pri_tol) && (r_ds < P.abs_dua_tol) && (r_di < P.abs_dua_tol);
-            if (valid && r16 == 0)
-            {
-                P.res[4 * inst + 0] = r_ps; P.res[4 * inst + 1] = r_pi;
-                P.res[4 * inst + 2] = r_ds; P.res[4 * inst + 3] = r_di;
-            }
+            RowResiduals res;
+            res.measure(pri, dua, is_x, is_u, rho);
+            conv = res.below_tol(P);
+            if (valid && r16 == 0) res.store(P, inst);
         }
         if (valid && r16 == 0)
         {
@@ -166,27 +154,11 @@ __global__ __launch_bounds__(WAVE) void admm_rowstream_kernel(const RowParams P)
     const float qrow = P.mats[(2 * NX + 2 * NU) * 16 + r16], rrow = input_cost_row<NX, NU>(P.mats, r16);
     float CD[NU];
     load_d2p<NX, NU>(CD, P.mats, r16);
-    int wstart = 0;
-    if (P.xref_mode == 1 && valid) wstart = P.xref_start[inst];
-    const int xref_off = inst * (int)P.xref_inst_stride + r16, uref_off = inst * (int)P.uref_inst_stride + r16;
-    auto xref_at = [&](int i) {
-        if (P.xref_mode == 1)
-        {
-            int row = wstart + i;
-            row = row < P.table_rows ? row : P.table_rows - 1;
-            return ldw<H16>(P.xref_table, row * 16 + r16);
-        }
-        return ldw<H16>(P.xref, xref_off + i * 16);
-    };
+    const RowXref<H16> xref(P, inst, valid, inst, r16);
+    const int uref_off = inst * (int)P.uref_inst_stride + r16;
     const float x0 = ldw<H16>(P.xu, rowbase);
-    const float pterm = terminal_term<NX, NU, EXACT, H16>(P.mats, r16, xref_at(N - 1));
-    int st = TINY_STATUS_UNSOLVED_, itn = 1;
-    float r_ps = 0.f, r_pi = 0.f, r_ds = 0.f, r_di = 0.f;
-    if (valid && !P.cold_start) // reset_workspace() zeroes the residual fields too
-    {
-        r_ps = P.res[4 * inst + 0]; r_pi = P.res[4 * inst + 1];
-        r_ds = P.res[4 * inst + 2]; r_di = P.res[4 * inst + 3];
-    }
+    const float pterm = terminal_term<NX, NU, EXACT, H16>(P.mats, r16, xref.at(P, N - 1, r16));
+    SolveFrame F(P, inst, valid);
     bool active = valid && (P.max_iter > 0);
     for (int it = 0; it < P.max_iter; ++it)
     {
@@ -218,20 +190,7 @@ __global__ __launch_bounds__(WAVE) void admm_rowstream_kernel(const RowParams P)
             }
             const float pN = lin_cost<EXACT, H16>(pterm, rho, t1);
             stw<H16>(P.pd, rowbase + (N - 1) * 16, is_x ? pN : 0.f);
-            const float pri_x = row_max(is_x ? pri : 0.f), dua_x = row_max(is_x ? dua : 0.f);
-            const float pri_u = row_max(is_u ? pri : 0.f), dua_u = row_max(is_u ? dua : 0.f);
-            itn = it + 1;
-            bool conv = false;
-            if ((it + 1) % P.check_termination == 0)
-            {
-                r_ps = pri_x; r_ds = dua_x * rho; r_pi = pri_u; r_di = dua_u * rho;
-                conv = (r_ps < P.abs_pri_tol) && (r_pi < P.abs_pri_tol) && (r_ds < P.abs_dua_tol) && (r_di < P.abs_dua_tol);
-            }
-            if (conv)
-            {
-                st = TINY_STATUS_SOLVED_;
-                active = false;
-            }
+            if (F.check(P, it, pri, dua, is_x, is_u, rho)) active = false;
             else
             {
                 float p = pN;
@@ -240,7 +199,7 @@ __global__ __launch_bounds__(WAVE) void admm_rowstream_kernel(const RowParams P)
                 {
                     const int o = rowbase + i * 16;
                     const float sni = ldw<H16>(P.vzn, o);
-                    const float cq = cost_of<H16>(P, is_x, is_u, xref_at(i), qrow, rrow, uref_off + i * 16);
+                    const float cq = cost_of<H16>(P, is_x, is_u, xref.at(P, i, r16), qrow, rrow, uref_off + i * 16);
                     float pn, dd;
                     riccati_step<NX, NU, EXACT, H16>(G, is_x, p, lin_cost<EXACT, H16>(cq, rho, sni - ldw<H16>(P.gy, o)), pn, dd);
                     if (P.en_d2p) pn = d2p_term<NX, NU, EXACT, H16>(CD, pn, dd);
@@ -251,22 +210,13 @@ __global__ __launch_bounds__(WAVE) void admm_rowstream_kernel(const RowParams P)
             }
         }
     }
-    if (P.max_iter <= 0)
-    {
-        if (valid && r16 == 0)
-        {
-            P.status[inst] = TINY_STATUS_UNSOLVED_;
-            P.iter[inst] = 1;
-            atomicAdd(P.n_unsolved, 1);
-        }
-        return;
-    }
+    if (F.no_iterations(P, inst, valid && r16 == 0)) return;
     {
         // live-out: q, r (admm.cpp:80-82) and, for converged instances, x,u regenerated from the frozen d
-        const bool solved = (st == TINY_STATUS_SOLVED_);
+        const bool solved = F.solved();
         // reset_workspace() folded into this launch (cold start): an instance that converged in its FIRST iteration ran no
         // backward sweep, which is what writes [p;d] and [v;z] — they are the zeros of the reset, materialised here
-        const bool fresh = valid && (P.cold_start != 0) && solved && itn == 1;
+        const bool fresh = valid && (P.cold_start != 0) && solved && F.itn == 1;
         float s = x0;
         for (int i = 0; i < N; i++)
         {
@@ -281,18 +231,11 @@ __global__ __launch_bounds__(WAVE) void admm_rowstream_kernel(const RowParams P)
             }
             if (valid && solved) stw<H16>(P.xu, o, sv);
             s = xn;
-            const float cq = cost_of<H16>(P, is_x, is_u, xref_at(i), qrow, rrow, uref_off + i * 16);
+            const float cq = cost_of<H16>(P, is_x, is_u, xref.at(P, i, r16), qrow, rrow, uref_off + i * 16);
             const float lin = lin_cost<EXACT, H16>(cq, rho, ldw<H16>(P.vzn, o) - ldw<H16>(P.gy, o));
             if (valid) stw<H16>(P.qr, o, (i < N - 1 || is_x) ? lin : 0.f);
         }
-        if (valid && r16 == 0)
-        {
-            P.res[4 * inst + 0] = r_ps; P.res[4 * inst + 1] = r_pi;
-            P.res[4 * inst + 2] = r_ds; P.res[4 * inst + 3] = r_di;
-            P.status[inst] = st;
-            P.iter[inst] = itn;
-            if (!solved) atomicAdd(P.n_unsolved, 1);
-        }
+        if (valid && r16 == 0) F.store(P, inst);
     }
 }
 
@@ -301,14 +244,11 @@ hipError_t launch_admm_rowstream(int nx, int nu, bool exact, bool h16, const Row
     const int nblocks = (P.batch + 3) / 4;
 #define TINY_ROWSTREAM_LAUNCH(NX, NU, EX, H) \
     hipLaunchKernelGGL((admm_rowstream_kernel<NX, NU, EX, H>), dim3(nblocks), dim3(WAVE), 0, stream, P)
-#define TINY_ROWSTREAM_DISPATCH(NX, NU)                                                                                \
-    if (nx == NX && nu == NU)                                                                                          \
-    {                                                                                                                  \
-        if (exact && !h16) TINY_ROWSTREAM_LAUNCH(NX, NU, true, false);                                                 \
-        else if (exact) TINY_ROWSTREAM_LAUNCH(NX, NU, true, true);                                                     \
-        else if (!h16) TINY_ROWSTREAM_LAUNCH(NX, NU, false, false);                                                    \
-        else TINY_ROWSTREAM_LAUNCH(NX, NU, false, true);                                                               \
-        return hipGetLastError();                                                                                      \
+#define TINY_ROWSTREAM_DISPATCH(NX, NU)                                  \
+    if (nx == NX && nu == NU)                                            \
+    {                                                                    \
+        TINY_FOR_EXACT_H16(exact, h16, TINY_ROWSTREAM_LAUNCH, NX, NU);   \
+        return hipGetLastError();                                        \
     }
     TINY_FOR_EACH_ROWDIMS(TINY_ROWSTREAM_DISPATCH)
     return hipErrorInvalidValue;
@@ -327,14 +267,11 @@ hipError_t launch_admm_step(int nx, int nu, bool exact, bool h16, int fn, const 
     const int nblocks = (P.batch + 3) / 4;
 #define TINY_STEP_LAUNCH(NX, NU, EX, H) \
     hipLaunchKernelGGL((admm_step_kernel<NX, NU, EX, H>), dim3(nblocks), dim3(WAVE), 0, stream, P, fn, conv_out)
-#define TINY_ROWDIMS_DISPATCH(NX, NU)                                                                                       \
-    if (nx == NX && nu == NU)                                                                                               \
-    {                                                                                                                       \
-        if (exact && !h16) TINY_STEP_LAUNCH(NX, NU, true, false);                                                           \
-        else if (exact) TINY_STEP_LAUNCH(NX, NU, true, true);                                                               \
-        else if (!h16) TINY_STEP_LAUNCH(NX, NU, false, false);                                                              \
-        else TINY_STEP_LAUNCH(NX, NU, false, true);                                                                         \
-        return hipGetLastError();                                                                                           \
+#define TINY_ROWDIMS_DISPATCH(NX, NU)                               \
+    if (nx == NX && nu == NU)                                       \
+    {                                                               \
+        TINY_FOR_EXACT_H16(exact, h16, TINY_STEP_LAUNCH, NX, NU);   \
+        return hipGetLastError();                                   \
     }
     TINY_FOR_EACH_ROWDIMS(TINY_ROWDIMS_DISPATCH)
     return hipErrorInvalidValue;

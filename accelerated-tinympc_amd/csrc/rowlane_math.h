@@ -1,6 +1,7 @@
 // rowlane_math.h — per-step arithmetic of the "row lane" mapping (one DPP row of 16 lanes = one instance; lane r owns
-// row r of the stacked vector [x ; u]), shared by the register-resident solver (admm_rowlane.hip) and the single-function
-// kernels (admm_steps.hip).  See admm_rowlane.hip for the mapping and the two arithmetic modes.
+// row r of the stacked vector [x ; u]), shared by the register-resident solvers (admm_rowlane.hip, admm_rowloop.hip) and
+// the streaming and single-function kernels (admm_steps.hip); at the end of the file, the frame of tiny_solve around the
+// sweeps for the rolled-loop and streaming kernels.  See admm_rowlane.hip for the mapping and the two arithmetic modes.
 #pragma once
 #include "tinympc_internal.h"
 #include "dpp_ops_gen.h"
@@ -349,5 +350,100 @@ __device__ __forceinline__ float terminal_term(const float *mats, int r16, float
     else
         return rnd<H16>(-dpp_fma_dot<0, NX>(xrN, PT));
 }
+
+// ---------------------------------------------------------------------------------------------
+// The frame of tiny_solve (admm.cpp:111-152) around the sweeps, stated once for the rolled-loop kernels (admm_rowloop.hip)
+// and the streaming ones (admm_steps.hip).  The other row kernels still carry their own copies.
+// ---------------------------------------------------------------------------------------------
+
+// Xref.col(i) of one instance, row r16: a window of the shared table that starts at the instance's own row and is clamped to
+// the table's last row (xref_mode 1), or the instance's / the shared array.  `ld` is the instance index to LOAD with.
+template <bool H16>
+struct RowXref
+{
+    int wstart = 0, off;
+    __device__ __forceinline__ RowXref(const RowParams &P, int inst, bool valid, int ld, int r16) : off(ld * (int)P.xref_inst_stride + r16)
+    {
+        if (P.xref_mode == 1 && valid) wstart = P.xref_start[inst];
+    }
+    __device__ __forceinline__ float at(const RowParams &P, int i, int r16) const
+    {
+        if (P.xref_mode == 1)
+        {
+            int row = wstart + i;
+            row = row < P.table_rows ? row : P.table_rows - 1;
+            return ldw<H16>(P.xref_table, row * 16 + r16);
+        }
+        return ldw<H16>(P.xref, off + i * 16);
+    }
+};
+
+// The four residual fields of TinyWorkspace, res[4 * inst + 0..3] = primal state | primal input | dual state | dual input.
+struct RowResiduals
+{
+    float ps = 0.f, pi = 0.f, ds = 0.f, di = 0.f;
+    // admm.cpp:95-98 from the per-lane maxima over the horizon: pri = max |[x;u] - [vnew;znew]|, dua = max |[v;z] - [vnew;znew]|
+    __device__ __forceinline__ void measure(float pri, float dua, bool is_x, bool is_u, float rho)
+    {
+        const float pri_x = row_max(is_x ? pri : 0.f), dua_x = row_max(is_x ? dua : 0.f);
+        const float pri_u = row_max(is_u ? pri : 0.f), dua_u = row_max(is_u ? dua : 0.f);
+        ps = pri_x; ds = dua_x * rho; pi = pri_u; di = dua_u * rho;
+    }
+    // admm.cpp:100-103
+    __device__ __forceinline__ bool below_tol(const RowParams &P) const
+    {
+        return (ps < P.abs_pri_tol) && (pi < P.abs_pri_tol) && (ds < P.abs_dua_tol) && (di < P.abs_dua_tol);
+    }
+    __device__ __forceinline__ void load(const RowParams &P, int inst) { ps = P.res[4 * inst + 0]; pi = P.res[4 * inst + 1]; ds = P.res[4 * inst + 2]; di = P.res[4 * inst + 3]; }
+    __device__ __forceinline__ void store(const RowParams &P, int inst) const { P.res[4 * inst + 0] = ps; P.res[4 * inst + 1] = pi; P.res[4 * inst + 2] = ds; P.res[4 * inst + 3] = di; }
+};
+
+// status, iter and the residual fields of one instance through a fused solve.  `lead` is the one lane that writes them
+// (lane 0 of a valid instance's row).
+struct SolveFrame
+{
+    RowResiduals res;                            // a warm start keeps the fields of the previous solve until a check overwrites them;
+    int st = TINY_STATUS_UNSOLVED_, itn = 1;     // reset_workspace() (cold start) zeroes them.  admm.cpp:114-115
+    __device__ __forceinline__ SolveFrame(const RowParams &P, int inst, bool valid)
+    {
+        if (valid && !P.cold_start) res.load(P, inst);
+    }
+    // admm.cpp:120 and termination_condition (admm.cpp:91-109, 135-136) after the forward sweep of iteration `it`; true: converged
+    __device__ __forceinline__ bool check(const RowParams &P, int it, float pri, float dua, bool is_x, bool is_u, float rho)
+    {
+        RowResiduals now;
+        now.measure(pri, dua, is_x, is_u, rho);
+        itn = it + 1;
+        bool conv = false;
+        if ((it + 1) % P.check_termination == 0)
+        {
+            res = now;
+            conv = res.below_tol(P);
+        }
+        if (conv) st = TINY_STATUS_SOLVED_;
+        return conv;
+    }
+    __device__ __forceinline__ bool solved() const { return st == TINY_STATUS_SOLVED_; }
+    // max_iter <= 0: tiny_solve only sets status and iter (admm.cpp:114-117,151).  true: the kernel returns, nothing else is written
+    __device__ __forceinline__ bool no_iterations(const RowParams &P, int inst, bool lead) const
+    {
+        if (P.max_iter > 0) return false;
+        if (lead)
+        {
+            P.status[inst] = TINY_STATUS_UNSOLVED_;
+            P.iter[inst] = 1;
+            atomicAdd(P.n_unsolved, 1);
+        }
+        return true;
+    }
+    // live-out of the frame: residual fields, status, iter and the batch's count of unsolved instances
+    __device__ __forceinline__ void store(const RowParams &P, int inst) const
+    {
+        res.store(P, inst);
+        P.status[inst] = st;
+        P.iter[inst] = itn;
+        if (!solved()) atomicAdd(P.n_unsolved, 1);
+    }
+};
 
 } // namespace tinympc

@@ -140,6 +140,16 @@ hipError_t launch_riccati_batch(int nx, int nu, int s0, int n, int count, const 
 // (nx, nu) pairs with single-function kernels (admm_steps.hip), any N
 // (2, 2): the reference's own examples/codegen_random.cpp:19-31 (n = 2, m = 2, N = 3, min > max bounds)
 #define TINY_FOR_EACH_ROWDIMS(X) X(12, 4) X(4, 1) X(8, 3) X(8, 4) X(12, 2) X(4, 2) X(4, 4) X(2, 2)
+// X(NX, NU, EXACT, H16) with the compile-time twins of the run-time pair (exact, h16): the four arithmetic x storage
+// instantiations a row kernel has per (nx, nu)
+#define TINY_FOR_EXACT_H16(exact, h16, X, NX, NU)  \
+    do                                             \
+    {                                              \
+        if ((exact) && !(h16)) X(NX, NU, true, false); \
+        else if (exact) X(NX, NU, true, true);     \
+        else if (!(h16)) X(NX, NU, false, false);  \
+        else X(NX, NU, false, true);               \
+    } while (0)
 enum { STEP_FORWARD_PASS = 0, STEP_UPDATE_SLACK, STEP_UPDATE_DUAL, STEP_UPDATE_LINEAR_COST, STEP_TERMINATION_CONDITION,
        STEP_BACKWARD_PASS_GRAD };
 

@@ -199,6 +199,23 @@ def test_tile48_short_horizon_instantiation_fits_two_waves_per_simd(listings):
         assert m and int(m.group(1)) <= 256, (key, m and m.group(1))
 
 
+def test_rolled_loop_shapes_keep_their_occupancy(listings):
+    """The two register shapes of the rolled-loop body (admm_rowloop.hip): every admm_rowloop_kernel instantiation must fit three waves per
+    SIMD (512 / 3 -> 168 VGPRs), every admm_rowloop64_kernel one two (256); neither they nor the streaming / step kernels may spill."""
+    for src, counts in (("admm_rowloop.hip", {"admm_rowloop_kernel": 32, "admm_rowloop64_kernel": 32}),
+                        ("admm_steps.hip", {"admm_rowstream_kernel": 32, "admm_step_kernel": 32})):
+        txt = listings[src]
+        scratch = scratch_sizes(txt)
+        for family, n in counts.items():
+            names = [k for k in scratch if f"{len(family)}{family}I" in k]
+            assert len(names) == n, (family, len(names))
+            for k in names:
+                assert scratch[k] == 0, (k, scratch[k])
+                if src == "admm_rowloop.hip":
+                    vgprs = int(re.search(r"; TotalNumVgprs: (\d+)", txt[re.search(rf"^{k}:", txt, re.M).start():]).group(1))
+                    assert vgprs <= (168 if family == "admm_rowloop_kernel" else 256), (k, vgprs)
+
+
 def test_packed_adds_only_where_they_are_deliberate(listings):
     """-fno-slp-vectorize keeps hipcc from pairing the scalar adds of the 16-lane and wave kernels into v_pk_add_f32 (slower at two
     waves per SIMD); admm_tile16.hip writes its sums over 4-vectors on purpose and must contain them."""
