@@ -620,8 +620,15 @@ __global__ __launch_bounds__(WAVE * TILE16_WAVES, 1) void admm_tile16_kernel(con
     if (P.order) tile = P.order[slot];
     const bool tile_ok = tile >= 0 && tile < ntiles; // also rejects a bad entry of a caller-supplied order: such a wave stores nothing
     T16_STAMP(stamp_k, 3, (unsigned long long)(unsigned)tile);
-    const int inst = tile * 16 + c;
-    const bool valid = tile_ok && inst < P.batch;
+    // Instance map (GM instantiations: a launch from a reset workspace with the shared table): column c serves instance inst_map[16 tile + c] — the
+    // host groups instances whose reference windows start at the same table row, whose iteration counts are alike (dispatch_order.hip) —; an
+    // entry outside [0, batch) is a padding column.  The mapped index is NOT carried across the iteration loop: the epilogue reads the map again.
+    constexpr bool GM = COLD && !MPC && !BR && !XR;
+    int inst = tile * 16 + c;
+    if constexpr (GM)
+        if (P.inst_map) inst = P.inst_map[(tile_ok ? tile : 0) * 16 + c];
+    auto in_batch = [&](int i) { return GM ? (unsigned)i < (unsigned)P.batch : i < P.batch; }; // (i >= 0 wherever it is not a map entry)
+    const bool valid = tile_ok && in_batch(inst);
     const int inst_a = valid ? inst : P.batch - 1; // padding columns of the last tile load a valid instance and store nothing
 
     // ---- per-instance state, four words per horizon step (row 4v + g) ----
@@ -1064,12 +1071,35 @@ __global__ __launch_bounds__(WAVE * TILE16_WAVES, 1) void admm_tile16_kernel(con
     } // MPC steps
     T16_STAMP(stamp_k, 1, __builtin_amdgcn_s_memrealtime());
 
+    // the instance a column of this tile serves, made again behind the iteration loop (GM: read from the map; the tile number and the lane number pass
+    // through opaque statements like ozt and the lane number of load_xref, so that nothing of it is carried across the loop)
+    auto inst_of = [&](int col) {
+        if constexpr (GM)
+        {
+            int tl = tile_ok ? tile : 0;
+            asm volatile("" : "+s"(tl));
+            if (P.inst_map) return P.inst_map[tl * 16 + col];
+            return tl * 16 + col;
+        }
+        else return tile * 16 + col;
+    };
+    int inst_e = inst, ebase_e = ebase; // (the other instantiations: the expressions of the prologue)
+    bool valid_e = valid;
+    if constexpr (GM)
+    {
+        unsigned ll = lane;
+        asm volatile("" : "+v"(ll));
+        inst_e = inst_of((int)(ll & 15u));
+        valid_e = tile_ok && in_batch(inst_e);
+        ebase_e = ((valid_e ? inst_e : P.batch - 1) * N) * 16 + (int)(ll >> 4);
+    }
+
     if (P.max_iter <= 0) // tiny_solve only sets status and iter (admm.cpp:114-117,151)
     {
-        if (valid && g == 0)
+        if (valid_e && g == 0)
         {
-            P.status[inst] = TINY_STATUS_UNSOLVED_;
-            P.iter[inst] = 1;
+            P.status[inst_e] = TINY_STATUS_UNSOLVED_;
+            P.iter[inst_e] = 1;
             atomicAdd(P.n_unsolved, 1);
         }
         T16_STAMP(stamp_k, 2, __builtin_amdgcn_s_memrealtime());
@@ -1088,15 +1118,15 @@ __global__ __launch_bounds__(WAVE * TILE16_WAVES, 1) void admm_tile16_kernel(con
     {
         const bool solved = st == TINY_STATUS_SOLVED_;
         const int c2 = lane >> 2, q2 = lane & 3;
-        const int inst2 = tile * 16 + c2;
-        const bool valid2 = tile_ok && inst2 < P.batch;
+        const int inst2 = inst_of(c2);
+        const bool valid2 = tile_ok && in_batch(inst2);
         const int obase2 = ((valid2 ? inst2 : 0) * N) * 16 + 4 * q2;
         // (may_alias: the same LDS words are accessed as float4 slack, as 4-vectors and as single floats, in program order)
         typedef float float_ma __attribute__((may_alias));
         typedef f32x4 f32x4_ma __attribute__((may_alias));
         float_ma *const stage_w = reinterpret_cast<float_ma *>(lds4 + wv * (N * WAVE));     // wave's slack area, as floats
         const int rd_off = (c2 * 4 + q2);                                                    // + 64 * r floats, r = 0..3
-        const int obase4 = ebase + 3 * g; // element 4g of the lane's own instance: ebase = (inst_a N) 16 + g
+        const int obase4 = ebase_e + 3 * g; // element 4g of the lane's own instance: ebase = (inst_a N) 16 + g
         // (the exact warm-start instantiations keep the LDS path: with the register transpose their iteration loop falls off the allocator's cliff,
         //  600 - 800 scratch accesses per iteration on the listing, where every other instantiation drops to 0 - 1)
         constexpr bool XPOSE = TINY_T16_XPOSE && !(EXACT && !COLD && !MPC);
@@ -1104,7 +1134,7 @@ __global__ __launch_bounds__(WAVE * TILE16_WAVES, 1) void admm_tile16_kernel(con
             if constexpr (XPOSE)
             {
                 const f32x4 o = t16_transpose4(val); // elements 4g .. 4g + 3 of instance c
-                if (valid) *reinterpret_cast<f32x4 *>(dst + obase4 + i * 16) = o;
+                if (valid_e) *reinterpret_cast<f32x4 *>(dst + obase4 + i * 16) = o;
                 return;
             }
             float_ma *slot = stage_w + i * (WAVE * 4);
@@ -1146,9 +1176,11 @@ __global__ __launch_bounds__(WAVE * TILE16_WAVES, 1) void admm_tile16_kernel(con
             // Steps in pairs, each array's two rows as whole 128-byte lines (t16_pair_lines): the lane stores piece g + 4 (c >> 3) of the line of
             // instance tile 16 + (c & 7) (lo8) and of that + 8 (hi8).  The arrays the state holds go first; x, u last, behind the regeneration chain,
             // whose products are in flight while the other stores issue.  (An odd N leaves its last step to the row-wise store.)
-            const int instL = tile * 16 + (c & 7);
-            const bool validL = tile_ok && instL < P.batch, validH = tile_ok && instL + 8 < P.batch;
-            const int obaseL = (validL ? instL : 0) * (N * 16) + ((c >> 3) << 4) + 4 * g, offH = 8 * N * 16;
+            // (with an instance map the two are any two instances: a line is two consecutive steps of ONE instance, so no line is split)
+            const int instL = inst_of(c & 7), instH = inst_of((c & 7) + 8);
+            const bool validL = tile_ok && in_batch(instL), validH = tile_ok && in_batch(instH);
+            const int obaseL = (validL ? instL : 0) * (N * 16) + ((c >> 3) << 4) + 4 * g;
+            const int offH = ((validH ? instH : 0) - (validL ? instL : 0)) * (N * 16);
             auto put2 = [&](float *dst, int i, const f32x4 &ve, const f32x4 &vo) {
                 f32x4 lo8, hi8;
                 t16_pair_lines(t16_transpose4(ve), t16_transpose4(vo), lo8, hi8);
@@ -1223,7 +1255,7 @@ __global__ __launch_bounds__(WAVE * TILE16_WAVES, 1) void admm_tile16_kernel(con
         // exhausted max_iter get p, d from it; the others keep what pass 1 stored.  (Row-wise pass 1: the same lanes store again, in program
         // order.  Paired pass 1: OTHER lanes of the same wave wrote these rows; the later store wins because the stores of one wave to one
         // address complete in issue order — the bitwise tile16 tests at max_iter 1 / 2 cover it.)
-        const unsigned long long umask = __ballot(valid && !solved);
+        const unsigned long long umask = __ballot(valid_e && !solved);
         if (umask != 0ull)
         {
             const bool unsolved2 = valid2 && ((umask >> c2) & 1ull); // storing lane l serves instance l >> 2 (g = 0 holds its flag at bit c)
@@ -1239,7 +1271,7 @@ __global__ __launch_bounds__(WAVE * TILE16_WAVES, 1) void admm_tile16_kernel(con
                 if constexpr (XPOSE)
                 {
                     const f32x4 o = t16_transpose4(f32x4{pn[0], pn[1], pn[2], dd});
-                    if (valid && !solved) *reinterpret_cast<f32x4 *>(P.pd + obase4 + i * 16) = o;
+                    if (valid_e && !solved) *reinterpret_cast<f32x4 *>(P.pd + obase4 + i * 16) = o;
                 }
                 else
                 {
@@ -1254,12 +1286,12 @@ __global__ __launch_bounds__(WAVE * TILE16_WAVES, 1) void admm_tile16_kernel(con
                 p[0] = pn[0]; p[1] = pn[1]; p[2] = pn[2];
             }
         }
-        if (valid && g == 0)
+        if (valid_e && g == 0)
         {
-            P.res[4 * inst + 0] = r_ps; P.res[4 * inst + 1] = r_pi;
-            P.res[4 * inst + 2] = r_ds; P.res[4 * inst + 3] = r_di;
-            P.status[inst] = st;
-            P.iter[inst] = itn;
+            P.res[4 * inst_e + 0] = r_ps; P.res[4 * inst_e + 1] = r_pi;
+            P.res[4 * inst_e + 2] = r_ds; P.res[4 * inst_e + 3] = r_di;
+            P.status[inst_e] = st;
+            P.iter[inst_e] = itn;
             if (!solved) atomicAdd(P.n_unsolved, 1);
         }
         if (MPC && valid) // the host's plant step of the last solve continues from here
@@ -1289,7 +1321,8 @@ __global__ __launch_bounds__(WAVE * TILE16_WAVES, 1) void admm_tile16_kernel(con
 // left for last cost 2 %, and in index order (no predictor: warm-started steps, the on-chip closed loop) both ends are alike.  So: a predictor's
 // order, one solve per launch, at least three tiles per wave slot, and a tile count the two 16-bit halves of the queue word can hold.
 // tiny_batch_set_tile_queue(tb, k) / TINYMPC_T16_TAIL=<k> override (0 = plain counter) for A/B runs and tests.
-static inline unsigned t16_tail_stride(const RowParams &P, int ntiles, int nblocks, int asked)
+// grouped: the tiles are formed through an instance map (P.inst_map: instances of one reference window share a tile), which moves the best stride.
+static inline unsigned t16_tail_stride(const RowParams &P, int ntiles, int nblocks, int asked, bool grouped)
 {
     static const int env = [] { const char *e = getenv("TINYMPC_T16_TAIL"); return e ? atoi(e) : -1; }();
     const int forced = asked >= 0 ? asked : env; // tiny_batch_set_tile_queue, then the environment
@@ -1301,6 +1334,11 @@ static inline unsigned t16_tail_stride(const RowParams &P, int ntiles, int nbloc
     // iterations; q = 8: 240 against 238): every 4th wave for 4 <= q < 8, every 8th otherwise
     const int slots = nblocks * TILE16_WAVES;
     if (ntiles < 3 * slots) return 0u;
+    // tiles formed by window start (grouped): their counts spread less and the short end holds more tiles of one length, so fewer waves are wanted there.
+    // Same-box A/B, grouped, strides 4 / 8 / 12 / 16 (tools/t16_group_ab.py, kernel ms, three passes each; a first run of two passes with 6 and 12 agrees):
+    // q = 3: 1.087 / 1.084 / 1.078 / 1.077, q = 4: 1.380 / 1.353 / 1.331 / 1.363, q = 5: 1.706 / 1.711 / 1.701 / 1.740, q = 6: 2.031 / 2.073 / 2.014 / 2.082,
+    // q = 8: 2.707 / 2.656 / 2.680 / 2.684 (the replay expected 8 at q = 4: 119.0 against 123.0 at stride 4): every 12th wave for 3 <= q < 8, every 8th beyond
+    if (grouped) return ntiles < 8 * slots ? 12u : 8u;
     return (ntiles >= 4 * slots && ntiles < 8 * slots) ? 4u : 8u;
 }
 
@@ -1327,7 +1365,8 @@ hipError_t launch_admm_tile16_pi(int N, bool exact, bool bounds_ring, bool xref_
     const size_t lds = tile16_pi_lds_bytes(N, bounds_ring, xref_ring, P.pi_flags, P.xref_mode == 1 ? P.table_rows : N);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     RowParams Q = P;
-    Q.pi_flags = (Q.pi_flags & 0xffu) | (t16_tail_stride(P, ntiles, nblocks, tail) << 8);
+    Q.inst_map = nullptr; // (ring tables are tile images in index order)
+    Q.pi_flags = (Q.pi_flags & 0xffu) | (t16_tail_stride(P, ntiles, nblocks, tail, false) << 8);
 #define TINY_TILE16_PI_LAUNCH3(NN, EX, BRR, XRR)                                                                           \
     {                                                                                                                      \
         auto kern = P.cold_start ? admm_tile16_kernel<NN, EX, true, false, BRR, XRR> : admm_tile16_kernel<NN, EX, false, false, BRR, XRR>; \
@@ -1362,6 +1401,19 @@ bool tile16_supported(int nx, int nu, int N)
 }
 
 int tile16_max_table_rows() { return TILE16_MAX_TABLE_ROWS; }
+
+// whether a predicted-order cold-start launch of `batch` instances runs the two-ended queue (t16_tail_stride's conditions on the launch's size and
+// the tile_queue setting): the automatic tile grouping follows it
+bool tile16_two_ended(int batch, int n_cu, int tail)
+{
+    RowParams P{};
+    static const int dummy_order = 0;
+    P.batch = batch; P.cold_start = 1; P.mpc_steps = 1; P.order = &dummy_order;
+    const int ntiles = (batch + 15) / 16;
+    if (n_cu <= 0) n_cu = 256;
+    const int want = (ntiles + TILE16_WAVES - 1) / TILE16_WAVES, nblocks = want < n_cu ? want : n_cu;
+    return t16_tail_stride(P, ntiles, nblocks, tail, true) != 0u;
+}
 
 #if TINY_T16_STAMP
 // measurement build only: a zeroed stamp buffer with one record set per wave slot of the current device (one persistent workgroup of
@@ -1402,7 +1454,8 @@ hipError_t launch_admm_tile16(int N, bool exact, const RowParams &P, hipStream_t
     if (rows > TILE16_MAX_TABLE_ROWS) return hipErrorInvalidValue;
     const size_t lds = (size_t)(TILE16_WAVES * N * WAVE + 2 * N * 4 + (rows + N - 1) * 4) * sizeof(float4); // the staged table is padded with N - 1 copies of its last row
     RowParams Q = P;
-    Q.pi_flags = (Q.pi_flags & 0xffu) | (t16_tail_stride(P, ntiles, nblocks, tail) << 8);
+    if (P.mpc_steps > 1 || !P.cold_start) Q.inst_map = nullptr; // the map belongs to the launch from a reset workspace
+    Q.pi_flags = (Q.pi_flags & 0xffu) | (t16_tail_stride(P, ntiles, nblocks, tail, Q.inst_map != nullptr) << 8);
 #define TINY_TILE16_LAUNCH(NN, EX)                                                                                         \
     {                                                                                                                      \
         auto kern = P.mpc_steps > 1 ? (P.cold_start ? admm_tile16_kernel<NN, EX, true, true> : admm_tile16_kernel<NN, EX, false, true>) \

@@ -19,14 +19,17 @@ namespace tinympc
 constexpr int kPredictorSteps = 4; // (round 4: 8 -> 4, the same order on the bench workload, 4 us less in the timed step)
 
 // TILES: one workgroup of four waves per TILE of 16 instances (admm_tile16.hip) and key[] receives the tile's key — the largest of its four
-// groups' — directly (round 4: a separate kernel used to reduce the group keys, 5 us and a launch gap of the headline step)
+// groups' — directly (round 4: a separate kernel used to reduce the group keys, 5 us and a launch gap of the headline step).  With an instance map
+// (P.inst_map, below) the tile's sixteen instances are the ones the solve kernel will put into it: key[t] stays the key of tile t.
 template <int NX, int NU, bool H16, bool TILES = false>
 __global__ __launch_bounds__(TILES ? 4 * WAVE : WAVE) void dispatch_key_kernel(const RowParams P, float *__restrict__ key)
 {
     const int lane = threadIdx.x & (WAVE - 1), r16 = lane & 15;
     const int grp = TILES ? (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6) : (int)blockIdx.x;
-    const int inst = grp * 4 + (lane >> 4);
-    const bool valid = inst < P.batch;
+    int inst = grp * 4 + (lane >> 4);
+    if constexpr (TILES)
+        if (P.inst_map) inst = P.inst_map[inst];
+    const bool valid = (unsigned)inst < (unsigned)P.batch;
     const int inst_a = valid ? inst : P.batch - 1; // padding rows of the last group read a valid instance
     const bool is_x = r16 < NX, is_u = (r16 >= NX) && (r16 < NX + NU);
     const int N = P.N;
@@ -98,6 +101,76 @@ __global__ __launch_bounds__(1024) void dispatch_order_kernel(const float *__res
 {
     bucket_sort_descending([key](int g) { return (int)((__builtin_bit_cast(unsigned, key[g]) & 0x7fffffffu) >> 20); }, order, n, counters);
 }
+
+// Instance map of admm_tile16.hip's cold-start launches: the instances sorted by the table row their reference window starts at (a counting sort, the
+// bucket is the row; the order inside one row is arbitrary), the padding columns of the last tile (-1) behind them.  Tiles are then formed from
+// instances that share a window: in a fleet that tracks one trajectory at different phases the iteration count follows the window (bench batch:
+// correlation 0.82, standard deviation inside one start 1.4 against 2.9 overall), so the sixteen instances of a wave, which run in lock step until
+// the slowest has converged, waste less (tests/fuzz/sim_tile_regroup.py).  Results do not depend on the map.
+//
+// One workgroup per 1 024 instances, two launches (one workgroup sorting 65 536 instances through its LDS atomics took 76 us, more than the grouping
+// saves per solve): instance_hist_kernel counts the instances per start (per-workgroup histogram in LDS, one global add per bucket it saw);
+// instance_map_kernel ranks its instances inside their buckets (LDS), scans the global histogram, reserves its run of every bucket with one global
+// add on the bucket's cursor, and scatters.  hist[] and cursor[] (2 x NBUCKET ints) are zeroed by the host in front.
+__device__ inline int start_bucket(int s) { return min(max(s, 0), NBUCKET - 1); }
+
+__global__ __launch_bounds__(1024) void instance_hist_kernel(const int *__restrict__ start, int batch, int *__restrict__ hist)
+{
+    __shared__ int cnt[NBUCKET];
+    const int t = threadIdx.x, i = (int)blockIdx.x * 1024 + t;
+    for (int b = t; b < NBUCKET; b += 1024) cnt[b] = 0;
+    __syncthreads();
+    if (i < batch) atomicAdd(&cnt[start_bucket(start[i])], 1);
+    __syncthreads();
+    for (int b = t; b < NBUCKET; b += 1024)
+        if (cnt[b]) atomicAdd(&hist[b], cnt[b]);
+}
+
+__global__ __launch_bounds__(1024) void instance_map_kernel(const int *__restrict__ start, int batch, const int *__restrict__ hist, int *__restrict__ cursor,
+                                                            int *__restrict__ map)
+{
+    __shared__ int cnt[NBUCKET], sa[NBUCKET], sb[NBUCKET];
+    const int t = threadIdx.x, i = (int)blockIdx.x * 1024 + t;
+    for (int b = t; b < NBUCKET; b += 1024) { cnt[b] = 0; sa[b] = hist[b]; }
+    __syncthreads();
+    int bk = 0, rank = 0;
+    if (i < batch)
+    {
+        bk = start_bucket(start[i]);
+        rank = atomicAdd(&cnt[bk], 1); // the instance's place among this workgroup's instances of the bucket
+    }
+    // inclusive scan of the histogram, ascending start
+    int *src = sa, *dst = sb;
+    for (int d = 1; d < NBUCKET; d <<= 1)
+    {
+        __syncthreads();
+        for (int b = t; b < NBUCKET; b += 1024) dst[b] = src[b] + (b >= d ? src[b - d] : 0);
+        int *tmp = src; src = dst; dst = tmp;
+    }
+    __syncthreads();
+    // cnt[b] <- where this workgroup's run of bucket b starts: the bucket's exclusive offset + what the workgroups before it (in claim order) took
+    for (int b = t; b < NBUCKET; b += 1024)
+    {
+        const int c = cnt[b];
+        if (c) cnt[b] = src[b] - hist[b] + atomicAdd(&cursor[b], c);
+    }
+    __syncthreads();
+    if (i < batch) map[cnt[bk] + rank] = i;
+    if (blockIdx.x == 0)
+        for (int e = batch + t; e < ((batch + 15) & ~15); e += 1024) map[e] = -1;
+}
+
+// scratch: 2 x NBUCKET ints (histogram, cursors)
+hipError_t launch_instance_map(const int *start, int batch, int *map, int *scratch, hipStream_t stream)
+{
+    hipError_t e = hipMemsetAsync(scratch, 0, 2 * NBUCKET * sizeof(int), stream);
+    if (e != hipSuccess) return e;
+    const int nwg = (batch + 1023) / 1024;
+    hipLaunchKernelGGL(instance_hist_kernel, dim3(nwg), dim3(1024), 0, stream, start, batch, scratch);
+    hipLaunchKernelGGL(instance_map_kernel, dim3(nwg), dim3(1024), 0, stream, start, batch, scratch, scratch + NBUCKET, map);
+    return hipGetLastError();
+}
+int instance_map_scratch_ints() { return 2 * NBUCKET; }
 
 // Warm-started launches (round 4, second session).  The predictor above is blind there — one sweep from a warm workspace sees residuals of the
 // size of the tolerance — but the instance's own PAST is not: iteration counts of consecutive MPC steps are strongly correlated (an instance at

@@ -502,6 +502,11 @@ struct TinyBatch
     int graph_captures = 0;                               // closed-loop graphs captured so far (tiny_batch_debug_graph_captures)
     int n_cu = 256;                                       // compute units of the handle's device
     int tile_queue = -1;                                  // tiny_batch_set_tile_queue: -1 automatic, 0 plain counter, k every k-th wave from the short end
+    int tile_grouping = -1;                               // tiny_batch_set_tile_grouping: -1 automatic, 0 off, 1 tiles formed from instances of one window start
+    int *tile_map = nullptr;                              // [16 ceil(batch/16)] tile16's instance map (dispatch_order.hip); allocated once: the address is in captured launches
+    bool tile_map_dirty = true;                           // xref_start[] has changed since the map was built
+    int tile_map_builds = 0;
+    bool last_grouped = false;                            // the most recent solve launch formed its tiles through the map
     float *tab_tile = nullptr, *tab_row = nullptr;        // trajectory table in both forms
     float *tab_row_h = nullptr;                           // ... and [rows][16] binary16 for fp16 storage
     int table_rows = 0;
@@ -1323,6 +1328,7 @@ void fill_row_params(TinyBatch *tb, RowParams &P, bool exact)
     P.res = tb->res; P.status = tb->status; P.iter = tb->iter; P.n_unsolved = tb->n_unsolved;
     P.mpc_steps = 1; P.window_advance = 0; P.u0_traj = nullptr; P.x0buf = tb->x0buf;
     P.dual32 = (tb->h16 && tb->dual32) ? 1 : 0;
+    P.inst_map = nullptr; // enqueue_dispatch_order sets it for the one launch that reads it
 }
 
 int check_optional_terms(const TinyBatch *tb)
@@ -1393,6 +1399,32 @@ ModelParams model_params(const TinyBatch *tb, const KernelPlan &pl)
     return M;
 }
 
+// Tile grouping (tiny_batch_set_tile_grouping): whether the launch of a lone solve with this plan forms tile16's tiles through the instance map — the
+// shared-table cold-start instantiations, a window reference, the predictor's dispatch (no caller's order).  Automatic: where the two-ended tile
+// queue is on (at least three tiles per wave slot), which is where the replay of the true counts says it pays (tests/fuzz/sim_tile_regroup.py).
+bool tile_grouping_wanted(const TinyBatch *tb, const KernelPlan &pl)
+{
+    static const int env = [] { const char *e = getenv("TINYMPC_T16_GROUP"); return e ? atoi(e) : -1; }();
+    const int mode = tb->tile_grouping >= 0 ? tb->tile_grouping : env; // the setter, then the environment
+    if (mode == 0) return false;
+    if (pl.kernel != Kernel::Tile16 || pl.pi || pl.pm || tb->xref_mode != 1 || tb->order_dev) return false;
+    if (!tb->cold_pending || dispatch_effective(tb) != 1 || tb->max_iter <= 0) return false;
+    return mode >= 1 || tile16_two_ended(tb->batch, tb->n_cu, tb->tile_queue);
+}
+
+// the map is (re)built on the handle's stream when such a launch is next and the window starts have moved since the last build
+int ensure_tile_map(TinyBatch *tb, const KernelPlan &pl)
+{
+    if (!tile_grouping_wanted(tb, pl) || (tb->tile_map && !tb->tile_map_dirty)) return 0;
+    const size_t n = (size_t)((tb->batch + 15) / 16) * 16;
+    if (!tb->tile_map) TRY(dev_alloc_zero((float **)&tb->tile_map, n + (size_t)instance_map_scratch_ints())); // the map, then the sort's histogram and cursors
+    const hipError_t e = launch_instance_map(tb->xref_start, tb->batch, tb->tile_map, tb->tile_map + n, tb->stream);
+    if (e != hipSuccess) return fail(TINY_BATCH_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
+    tb->tile_map_dirty = false;
+    ++tb->tile_map_builds;
+    return 0;
+}
+
 // everything a solve needs that may allocate, copy or synchronise (not capturable in a hipGraph); *plan: what the solve launches
 int prepare_solve(TinyBatch *tb, bool closed_loop, KernelPlan *plan)
 {
@@ -1432,9 +1464,9 @@ int prepare_solve(TinyBatch *tb, bool closed_loop, KernelPlan *plan)
     // reset_workspace() is folded into the launch by every fused kernel: the register-resident ones start from zero registers,
     // the streaming ones (MFMA, rowstream, wavestream) read zeros in their first iteration and zero-fill p, d, v, z of such an
     // instance in their epilogue
-    if (inputs_rebuilt) return resolve_plan(tb, closed_loop, plan);
-    *plan = pl; // rows_vary did not move: the provisional plan is the final one
-    return 0;
+    if (inputs_rebuilt) TRY(resolve_plan(tb, closed_loop, plan));
+    else *plan = pl; // rows_vary did not move: the provisional plan is the final one
+    return closed_loop ? 0 : ensure_tile_map(tb, *plan);
 }
 
 void fill_solve_params(const TinyBatch *tb, SolveParams &P)
@@ -1486,12 +1518,15 @@ int enqueue_dispatch_order(TinyBatch *tb, const KernelPlan &pl, int run_steps, b
     // (per-instance models: the predictor sweep reads the shared fma gains, which are unset or stale there — such a launch keeps index order)
     const bool predicted = eligible && want_predicted && !history && !pl.pm && !tb->dual32 && tb->max_iter > 1;
     if (traits(pl.kernel).order_unit_solve == 16) P.order = nullptr; // a caller's order lists groups of four instances, not tiles of sixteen
+    // tile16 from a reset workspace: tiles formed from instances of one window start; the predictor's keys are then those tiles' keys
+    P.inst_map = (!run && tb->tile_map && tile_grouping_wanted(tb, pl)) ? tb->tile_map : nullptr;
     hipError_t e = hipSuccess;
     if (history) e = launch_dispatch_order_history(tb->iter, tb->batch, unit, tb->order_buf, tb->n_unsolved, tb->stream, run && unit == 16);
     else if (predicted)
     {
         RowParams K;
         fill_row_params(tb, K, false); // fma gains
+        K.inst_map = P.inst_map;
         e = launch_dispatch_order(tb->nx, tb->nu, tb->h16, K, tb->key_buf, tb->order_buf, tb->stream, unit == 16);
     }
     else HIP_TRY(hipMemsetAsync(tb->n_unsolved, 0, 2 * sizeof(int), tb->stream));
@@ -1555,8 +1590,13 @@ int enqueue_solve(TinyBatch *tb, const KernelPlan &pl, bool record_events)
         const int applied = enqueue_dispatch_order(tb, pl, 1, false, P);
         if (applied < 0) return applied;
         tb->last_dispatch = applied;
+        tb->last_grouped = P.inst_map != nullptr;
     }
-    else HIP_TRY(hipMemsetAsync(tb->n_unsolved, 0, 2 * sizeof(int), tb->stream)); // [0] unsolved count
+    else
+    {
+        HIP_TRY(hipMemsetAsync(tb->n_unsolved, 0, 2 * sizeof(int), tb->stream)); // [0] unsolved count
+        tb->last_grouped = false;
+    }
     if (record_events) HIP_TRY(hipEventRecord(tb->ev0, tb->stream)); // the events bracket the solve kernel itself
     if (t.layout == LAYOUT_ROW && P.dual32 && !t.fp32_duals)
         return fail(TINY_BATCH_EUNSUPPORTED, "fp16 storage with fp32 duals runs on the register-resident 16-lane and quad kernels only "
@@ -1575,6 +1615,7 @@ int enqueue_solve(TinyBatch *tb, const KernelPlan &pl, bool record_events)
 
 int enqueue_plant_step(TinyBatch *tb, int window_advance)
 {
+    if (tb->xref_mode == 1 && window_advance) tb->tile_map_dirty = true; // the kernel slides xref_start[]
     if (tb->pm)
     {
         hipLaunchKernelGGL(plant_step_pm_kernel, dim3((tb->batch + 127) / 128), dim3(128), 0, tb->stream, tb->x0buf, work_ptr(tb, TINY_ARR_X), work_ptr(tb, TINY_ARR_U),
@@ -1691,7 +1732,7 @@ void tiny_batch_destroy(TinyBatch *tb)
     for (int k = 0; k < 4; k++) { (void)guarded_free(tb->in_bnd[k].dev); (void)guarded_free(tb->t_bnd[k]); }
     (void)guarded_free(tb->t_xref); (void)guarded_free(tb->r_xref); (void)guarded_free(tb->r_bounds); (void)guarded_free((float *)tb->rows_vary_dev);
     (void)guarded_free(tb->r_bounds_img); (void)guarded_free(tb->r_xref_img);
-    (void)guarded_free(tb->tab_tile); (void)guarded_free(tb->tab_row); (void)guarded_free(tb->tab_row_h); (void)guarded_free(tb->xref_start);
+    (void)guarded_free(tb->tab_tile); (void)guarded_free(tb->tab_row); (void)guarded_free(tb->tab_row_h); (void)guarded_free(tb->xref_start); (void)guarded_free(tb->tile_map);
     (void)guarded_free(tb->res); (void)guarded_free(tb->status); (void)guarded_free(tb->iter); (void)guarded_free(tb->n_unsolved);
     (void)guarded_free(tb->opnd); (void)guarded_free(tb->qvec); (void)guarded_free(tb->gen_mats); (void)guarded_free(tb->mats_exact); (void)guarded_free(tb->mats_fast);
     (void)guarded_free(tb->pm_src); (void)guarded_free(tb->pm_rho); (void)guarded_free(tb->pm_row[0]); (void)guarded_free(tb->pm_row[1]);
@@ -1967,6 +2008,36 @@ int tiny_batch_set_tile_queue(TinyBatch *tb, int stride)
     return TINY_BATCH_OK;
 }
 
+int tiny_batch_set_tile_grouping(TinyBatch *tb, int mode)
+{
+    CHECK_TB(tb);
+    if (mode < -1 || mode > 1) return fail(TINY_BATCH_EINVAL, "tiny_batch_set_tile_grouping: mode must be -1 (automatic), 0 (off) or 1 (by window start)");
+    tb->tile_grouping = mode;
+    invalidate_graph(tb);
+    return TINY_BATCH_OK;
+}
+
+int tiny_batch_tile_grouping_applied(TinyBatch *tb)
+{
+    CHECK_TB(tb);
+    return tb->last_grouped ? 1 : 0;
+}
+
+int tiny_batch_get_tile_map(TinyBatch *tb, int *map, int *builds)
+{
+    CHECK_TB(tb);
+    if (builds) *builds = tb->tile_map_builds;
+    if (!tb->tile_map) return 0;
+    const int n = (tb->batch + 15) / 16 * 16;
+    if (map)
+    {
+        TRY(set_device(tb));
+        HIP_TRY(hipMemcpyAsync(map, tb->tile_map, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, tb->stream));
+        HIP_TRY(hipStreamSynchronize(tb->stream));
+    }
+    return n;
+}
+
 int tiny_batch_dispatch_applied(TinyBatch *tb)
 {
     CHECK_TB(tb);
@@ -2056,6 +2127,7 @@ int tiny_batch_set_xref_window(TinyBatch *tb, const float *table, int rows, cons
     HIP_TRY(hipStreamSynchronize(tb->stream));
     tb->table_rows = rows;
     tb->xref_mode = 1;
+    tb->tile_map_dirty = true;
     invalidate_graph(tb);
     return 0;
 }
@@ -2335,6 +2407,7 @@ int tiny_batch_mpc_run_traj_async(TinyBatch *tb, int steps, int window_advance, 
     if (tb->nx > 64) return fail(TINY_BATCH_EUNSUPPORTED, "mpc_run supports nx <= 64");
     if (tb->max_iter <= 0) return fail(TINY_BATCH_EINVAL, "tiny_batch_mpc_run_async needs max_iter > 0");
     TRY(set_device(tb));
+    if (tb->xref_mode == 1 && window_advance) tb->tile_map_dirty = true; // every path below slides xref_start[] (the on-chip loop writes it back)
     const bool from_reset = tb->cold_pending; // (flush_pending materialises the zeros and clears the flag: the run's first solve is the cold one all the same)
     TRY(flush_pending(tb)); // every solve of the run starts from "duals reset, workspace warm"
     tb->duals_zero_pending = true;
@@ -2349,6 +2422,7 @@ int tiny_batch_mpc_run_traj_async(TinyBatch *tb, int steps, int window_advance, 
         const int applied = enqueue_dispatch_order(tb, pl, steps, from_reset, P);
         if (applied < 0) return applied;
         tb->last_dispatch = applied;
+        tb->last_grouped = false;
         // (tile16 gets tb->tile_queue like a lone solve: its two-ended queue is off whenever mpc_steps > 1 — t16_tail_stride returns 0 — so the setting changes nothing here)
         const hipError_t e = launch_kernel(tb, pl, P);
         if (e != hipSuccess) return fail(TINY_BATCH_EHIP, "kernel launch failed: %s", hipGetErrorString(e));

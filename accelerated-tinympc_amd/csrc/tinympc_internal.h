@@ -115,6 +115,9 @@ struct RowParams
     float *u0_traj;              // [mpc_steps][batch][nu] or NULL: u.col(0) of every step
     float *x0buf;                // [batch][nx]: x0 of the LAST solve of the launch (the host's plant step reads it)
     int dual32;                  // with fp16 storage: gy (the duals g, y) stays fp32 in HBM and is not rounded (rowlane and quadlane kernels only)
+    const int *inst_map;         // NULL = identity, or [16 ceil(batch/16)]: column c of tile t serves instance inst_map[16 t + c]; an entry outside
+                                 // [0, batch) is a padding column (dispatch_order.hip: instances grouped by window start).  Read by the cold-start
+                                 // shared-table instantiations of admm_tile16.hip and by the tile key kernel only; NULL for every other launch
 };
 
 // Per-instance models (tiny_batch_set_models): a kernel argument of its own beside RowParams / SolveParams, whose layouts stay as they are.
@@ -185,6 +188,7 @@ hipError_t launch_admm_tile16(int N, bool exact, const RowParams &P, hipStream_t
 hipError_t launch_admm_tile16_pi(int N, bool exact, bool bounds_ring, bool xref_ring, const RowParams &P, hipStream_t stream, int n_cu, int tail = -1);
 size_t tile16_pi_lds_bytes(int N, bool bounds_ring, bool xref_ring, unsigned pi_flags, int table_rows);
 int tile16_max_table_rows(); // rows of a trajectory table that fit the kernel's LDS share
+bool tile16_two_ended(int batch, int n_cu, int tail); // a predicted-order cold-start launch of this size takes tiles from both ends of the order
 
 // wave-per-instance exact kernel (admm_wave.hip): 16 < nx + nu <= 64, any N, state in HBM, row width 64
 #define TINY_FOR_EACH_WAVEDIMS(X) X(32, 16) X(16, 8) X(16, 4) X(20, 8) X(24, 4)
@@ -210,5 +214,9 @@ hipError_t launch_admm_generic_pm(const SolveParams &P, const ModelParams &M, in
 hipError_t launch_dispatch_order(int nx, int nu, bool h16, const RowParams &P, float *key, int *order, hipStream_t stream, int tile = 0);
 // order[] = the ceil(batch/unit) units (unit = 4: groups, 16: tiles) sorted by the largest iter[] of their instances, largest first; zeroes counters[0..1]
 hipError_t launch_dispatch_order_history(const int *iter, int batch, int unit, int *order, int *counters, hipStream_t stream, int use_sum = 0);
+// map[0 .. 16 ceil(batch/16)) = the instances sorted by start[] (ascending; any order inside one value), then -1 for the padding columns
+// (scratch: instance_map_scratch_ints() ints, zeroed by the call)
+hipError_t launch_instance_map(const int *start, int batch, int *map, int *scratch, hipStream_t stream);
+int instance_map_scratch_ints();
 
 } // namespace tinympc

@@ -76,7 +76,7 @@ def load_library(build_if_missing: bool = False) -> C.CDLL:
         "tiny_batch_enable_timing": [P, C.c_int], "tiny_batch_last_solve_ms": [P, F],
         "tiny_batch_select_kernel": [P, C.c_int], "tiny_batch_arithmetic": [P], "tiny_batch_debug_graph_captures": [P], "tiny_batch_set_storage": [P, C.c_int], "tiny_batch_set_storage_ex": [P, C.c_int, C.c_int],
         "tiny_batch_set_row_kernel": [P, C.c_int],
-        "tiny_batch_set_dispatch": [P, C.c_int], "tiny_batch_set_tile_queue": [P, C.c_int], "tiny_batch_set_dispatch_order_device": [P, P], "tiny_batch_dispatch_applied": [P],
+        "tiny_batch_set_dispatch": [P, C.c_int], "tiny_batch_set_tile_queue": [P, C.c_int], "tiny_batch_set_tile_grouping": [P, C.c_int], "tiny_batch_tile_grouping_applied": [P], "tiny_batch_get_tile_map": [P, I, I], "tiny_batch_set_dispatch_order_device": [P, P], "tiny_batch_dispatch_applied": [P],
         "tiny_batch_set_optional_terms": [P, C.c_int, C.c_int], "tiny_batch_set_input_cost": [P, F],
         "tiny_batch_set_coeff_d2p": [P, F], "tiny_batch_set_uref": [P, F, C.c_int],
         "tiny_batch_group_solve": [C.POINTER(P), C.c_int, I],
@@ -501,6 +501,25 @@ class TinyBatchSolver:
     def set_tile_queue(self, stride: int):
         """tile16's tile queue under longest-first dispatch: -1 automatic, 0 one counter, k = every k-th wave takes tiles from the short end of the order."""
         self._check(self.lib.tiny_batch_set_tile_queue(self._h, stride))
+
+    def set_tile_grouping(self, mode: int):
+        """tile16's tiles in a cold-start launch with a window reference: -1 automatic (on where the two-ended tile queue is on), 0 sixteen consecutive
+        instances, 1 instances sorted by window start (TINYMPC_T16_GROUP overrides the automatic choice)."""
+        self._check(self.lib.tiny_batch_set_tile_grouping(self._h, mode))
+
+    def tile_grouping_applied(self) -> bool:
+        """whether the most recent solve launch formed its tiles through the instance map"""
+        return bool(self._check(self.lib.tiny_batch_tile_grouping_applied(self._h)))
+
+    def tile_map(self):
+        """(map, builds): the instance map as int32 [16 ceil(B/16)] (None while none has been built) and how often it has been built"""
+        builds = C.c_int(0)
+        n = self._check(self.lib.tiny_batch_get_tile_map(self._h, None, C.byref(builds)))
+        if n == 0:
+            return None, builds.value
+        m = np.empty(n, np.int32)
+        self._check(self.lib.tiny_batch_get_tile_map(self._h, m.ctypes.data_as(C.POINTER(C.c_int)), None))
+        return m, builds.value
 
     def dispatch_applied(self) -> int:
         """0 index order, 1 predicted longest first, 2 the caller's order, 3 longest first by the previous solve's iteration counts — what the most recent

@@ -283,8 +283,24 @@ extern "C"
      * stride k every k-th wave takes its tiles from the SHORT end of the predicted order instead of the long one, fits one tile more into the same
      * time, and the partial round disappears (65 536 tracking instances: makespan 132.5 -> 123 iterations simulated on the true counts,
      * tests/fuzz/sim_tile_deque.py).  -1 (default): automatic — for cold-start launches in predicted order of at least three tiles per slot and at most 32 768 tiles stride 4
-     * (four to eight tiles per slot: the headline's 65 536 instances) or 8, otherwise one counter; 0: one counter; 1 .. 255: that stride.  Results never depend on it. */
+     * (four to eight tiles per slot: the headline's 65 536 instances) or 8 — with tiles grouped by window start (tiny_batch_set_tile_grouping) stride 12 below eight tiles
+     * per slot and 8 from there —, otherwise one counter; 0: one counter; 1 .. 255: that stride.  Results never depend on it. */
     int tiny_batch_set_tile_queue(TinyBatch *tb, int stride);
+    /* How the 16-instances-per-wave kernel (tile16) forms its tiles in a cold-start launch with a window reference (tiny_batch_set_xref_window).  The
+     * sixteen instances of a wave run in lock step until the slowest has converged; in a fleet that tracks one trajectory at different phases the
+     * iteration count follows the window (correlation 0.82 on the benchmark batch), so tiles formed from instances whose windows start at the same
+     * table row waste less of it (tests/fuzz/sim_tile_regroup.py).  mode 1: the library sorts the instances by window start on the device (a
+     * counting sort on the handle's stream, redone only after the starts have changed) and column c of tile t serves instance map[16 t + c]; it
+     * applies to a launch from a reset workspace under the predictor's dispatch (tiny_batch_set_dispatch 1 or automatic, no caller's order) on the
+     * shared-table tile16 kernel.  0: tiles are sixteen consecutive instances.  -1 (default): automatic — mode 1 where the two-ended tile queue is on
+     * (at least three tiles per wave slot).  TINYMPC_T16_GROUP=<mode> overrides the automatic choice.  Results never depend on it. */
+    int tiny_batch_set_tile_grouping(TinyBatch *tb, int mode);
+    /* 1 if the most recent solve launch formed its tiles through the instance map, else 0 (tiny_batch_dispatch_applied() is unchanged by grouping). */
+    int tiny_batch_tile_grouping_applied(TinyBatch *tb);
+    /* For tests: copies the instance map (16 ceil(batch/16) ints: a permutation of the instances sorted by window start, then -1 for the padding
+     * columns) to `map` (may be NULL) and the number of times it has been built to `*builds` (may be NULL).  Returns the number of entries, 0 when
+     * no map has been built. */
+    int tiny_batch_get_tile_map(TinyBatch *tb, int *map, int *builds);
     /* What the most recent solve launch actually did: 0 = index order (also when mode 1 / 2 did not apply: small launch, a kernel
      * without dispatch order, no history), 1 = longest first by the predicted iteration count, 2 = the caller's order, 3 = longest first by the
      * previous solve's iteration counts. */
