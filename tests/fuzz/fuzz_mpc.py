@@ -13,7 +13,7 @@ import accelerated_tinympc_amd as T  # noqa: E402
 pr = T.problems
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
-CLASSES = [("quad", 30), ("quad", 20), ("quad", 10), ("quad", 17), ("quad", 36), ("cartpole", 10), ("cartpole", 23), ("odd", 7)]
+CLASSES = [("quad", 30), ("quad", 25), ("quad", 20), ("quad", 10), ("quad", 17), ("quad", 36), ("cartpole", 10), ("cartpole", 23), ("odd", 7)]
 NAMES = ("x", "u", "q", "r", "p", "d", "v", "vnew", "z", "znew", "g", "y", "residuals", "status", "iter")
 t_end, rounds, t_note, onchip = time.time() + budget, 0, time.time(), 0
 while time.time() < t_end:
