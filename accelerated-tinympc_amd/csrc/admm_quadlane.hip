@@ -102,24 +102,14 @@ __global__ __launch_bounds__(WAVE) void admm_quadlane_kernel(const RowParams P)
     // the last instance's rows (and store nothing)
     const int inst_a = valid ? inst : P.batch - 1;
     const int rowx = (inst_a * N) * 16 + j, rowu = (inst_a * N) * 16 + NX;
-    int wstart = 0;
-    if (P.xref_mode == 1 && valid) wstart = P.xref_start[inst];
-    const int xref_off = inst_a * (int)P.xref_inst_stride + j;
+    RowXref<H16> xref(P, inst, valid, inst_a, j);
     const bool cold = P.cold_start != 0;
     const bool zdual = cold || (P.duals_zero != 0);
     float xrN = 0.f;
 #pragma unroll
     for (int i = 0; i < N; i++)
     {
-        float xr;
-        if (P.xref_mode == 1)
-        {
-            int row = wstart + i;
-            row = row < P.table_rows ? row : P.table_rows - 1;
-            xr = ldw<H16>(P.xref_table, row * 16 + j);
-        }
-        else
-            xr = ldw<H16>(P.xref, xref_off + i * 16);
+        const float xr = xref.at(P, i, j);
         cq[i] = rnd<H16>(-(xr * qrow)); // admm.cpp:81
         dd[i] = (cold || i == N - 1) ? 0.f : ldw<H16>(P.pd, rowu + i * 16);
         dl[i] = dd[i];
@@ -158,19 +148,13 @@ __global__ __launch_bounds__(WAVE) void admm_quadlane_kernel(const RowParams P)
         }
     };
 
-    int st = TINY_STATUS_UNSOLVED_, itn = 1; // admm.cpp:114-115
-    float r_ps = 0.f, r_pi = 0.f, r_ds = 0.f, r_di = 0.f;
-    if (valid && !P.cold_start)
-    {
-        r_ps = P.res[4 * inst + 0]; r_pi = P.res[4 * inst + 1];
-        r_ds = P.res[4 * inst + 2]; r_di = P.res[4 * inst + 3];
-    }
+    SolveFrame F(P, inst, valid);
     float pN = 0.f;
     bool ran_bwd = false;
     for (int ms = 0;; ++ms) // MPC steps of the closed-loop variant; an ordinary solve runs the body once
     {
     bool active = valid && (P.max_iter > 0);
-    st = TINY_STATUS_UNSOLVED_; itn = 1;
+    F.reset();
     for (int it = 0; it < P.max_iter; ++it)
     {
         if (!__any(active)) break;
@@ -204,20 +188,10 @@ __global__ __launch_bounds__(WAVE) void admm_quadlane_kernel(const RowParams P)
                 s = xn;
             }
             pN = lin_cost<EXACT, H16>(pterm, rho, sx[N - 1] - ax[N - 1]); // admm.cpp:83-84
-            // ---------------- termination_condition (admm.cpp:91-109) ----------------
-            const float pri_x = quad_max(prx), dua_x = quad_max(dux);
-            itn = it + 1;
-            bool conv = false;
-            if ((it + 1) % P.check_termination == 0)
-            {
-                r_ps = pri_x; r_ds = dua_x * rho; r_pi = pru; r_di = duu * rho;
-                conv = (r_ps < P.abs_pri_tol) && (r_pi < P.abs_pri_tol) && (r_ds < P.abs_dua_tol) && (r_di < P.abs_dua_tol);
-            }
-            if (conv)
-            {
-                st = TINY_STATUS_SOLVED_;
-                active = false;
-            }
+            // ---------------- termination_condition (admm.cpp:91-109): the state rows over the quad, the input row is lane-local ----------------
+            RowResiduals now;
+            now.set(quad_max(prx), quad_max(dux), pru, duu, rho);
+            if (F.judge(P, it, now)) active = false;
             else
             {
                 // ---------------- backward sweep: v = vnew, z = znew, linear cost, backward_pass_grad ----------------
@@ -266,15 +240,13 @@ __global__ __launch_bounds__(WAVE) void admm_quadlane_kernel(const RowParams P)
             quad_products2(tK, tA, x0, Kneg, Arow);
             x0 = (((tA[0] + tA[1]) + tA[2]) + tA[3]) + Bj * u0v;
         }
-        wstart += P.window_advance;
+        xref.advance(P);
 #pragma unroll
         for (int i = 0; i < N; i++)
         {
             if (P.xref_mode == 1)
             {
-                int row = wstart + i;
-                row = row < P.table_rows ? row : P.table_rows - 1;
-                const float xr = ldw<H16>(P.xref_table, row * 16 + j);
+                const float xr = xref.window(P, i, j);
                 cq[i] = rnd<H16>(-(xr * qrow));
                 if (i == N - 1) xrN = xr;
             }
@@ -285,21 +257,11 @@ __global__ __launch_bounds__(WAVE) void admm_quadlane_kernel(const RowParams P)
     }
     }
 
-    if (P.max_iter <= 0) // tiny_solve only sets status and iter (admm.cpp:114-117,151)
-    {
-        if (valid && lead)
-        {
-            P.status[inst] = TINY_STATUS_UNSOLVED_;
-            P.iter[inst] = 1;
-            atomicAdd(P.n_unsolved, 1);
-        }
-        return;
-    }
+    if (F.no_iterations(P, inst, valid && lead)) return;
 
     // ---------------- live-out: every work array written once ----------------
     if (valid)
     {
-        const bool solved = (st == TINY_STATUS_SOLVED_);
         float s = x0;
 #pragma unroll
         for (int i = 0; i < N; i++)
@@ -329,16 +291,9 @@ __global__ __launch_bounds__(WAVE) void admm_quadlane_kernel(const RowParams P)
         if (MPC) // the host's plant step continues from here
         {
             P.x0buf[inst * NX + j] = x0;
-            if (lead && P.xref_mode == 1) P.xref_start[inst] = wstart;
+            if (lead && P.xref_mode == 1) P.xref_start[inst] = xref.wstart;
         }
-        if (lead)
-        {
-            P.res[4 * inst + 0] = r_ps; P.res[4 * inst + 1] = r_pi;
-            P.res[4 * inst + 2] = r_ds; P.res[4 * inst + 3] = r_di;
-            P.status[inst] = st;
-            P.iter[inst] = itn;
-            if (!solved) atomicAdd(P.n_unsolved, 1);
-        }
+        if (lead) F.store(P, inst);
     }
 }
 

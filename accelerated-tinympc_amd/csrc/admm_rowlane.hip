@@ -113,9 +113,7 @@ __device__ __forceinline__ void rowlane_body(const RowParams &P, const ModelPara
     // 32-bit element offset: lets the compiler address every array as SGPR base + one shared VGPR offset instead of
     // keeping a 64-bit address pair per array alive through the loop (the host checks batch*N*16 < 2^30)
     const int rowbase = (inst_a * N) * 16 + r16;
-    int wstart = 0;
-    if (P.xref_mode == 1 && valid) wstart = P.xref_start[inst];
-    const int xref_off = inst_a * (int)P.xref_inst_stride + r16;
+    RowXref<H16> xref(P, inst, valid, inst_a, r16);
     const bool cold = P.cold_start != 0;
     const bool zdual = cold || (P.duals_zero != 0);
     float xrN = 0.f; // Xref_{N-1}(r)
@@ -124,15 +122,7 @@ __device__ __forceinline__ void rowlane_body(const RowParams &P, const ModelPara
 #pragma unroll
         for (int i = 0; i < N; i++)
         {
-            float xr;
-            if (P.xref_mode == 1)
-            {
-                int row = wstart + i;
-                row = row < P.table_rows ? row : P.table_rows - 1;
-                xr = ldw<H16>(P.xref_table, row * 16 + r16);
-            }
-            else
-                xr = ldw<H16>(P.xref, xref_off + i * 16);
+            const float xr = xref.at(P, i, r16);
             pd[i] = cold ? 0.f : ldw<H16>(P.pd, rowbase + i * 16); // live-in [p_i ; d_i]: kept by an instance that runs no backward sweep
             c[i] = is_x ? rnd<H16>(-(xr * qrow)) : pd[i];    // admm.cpp:81  q(i,j) = -(Xref(i,j) * Q(i))
             b[i * WAVE] = cold ? 0.f : ldw<H16>(P.vz, rowbase + i * 16);
@@ -146,13 +136,7 @@ __device__ __forceinline__ void rowlane_body(const RowParams &P, const ModelPara
     // -(Xref_{N-1}^T Pinf): constant during a solve (admm.cpp:83)
     float pterm = terminal_term<NX, NU, EXACT, H16>(mats, r16, xrN);
 
-    int st = TINY_STATUS_UNSOLVED_, itn = 1; // admm.cpp:114-115
-    float r_ps = 0.f, r_pi = 0.f, r_ds = 0.f, r_di = 0.f;
-    if (valid && !P.cold_start) // reset_workspace() zeroes the residual fields too
-    {
-        r_ps = P.res[4 * inst + 0]; r_pi = P.res[4 * inst + 1];
-        r_ds = P.res[4 * inst + 2]; r_di = P.res[4 * inst + 3];
-    }
+    SolveFrame F(P, inst, valid);
     float pN = 0.f; // p_{N-1} of the last executed forward sweep (x rows)
     bool ran_bwd = false;
 
@@ -163,7 +147,7 @@ __device__ __forceinline__ void rowlane_body(const RowParams &P, const ModelPara
     for (int ms = 0;; ++ms)
     {
     bool active = valid && (P.max_iter > 0);
-    st = TINY_STATUS_UNSOLVED_; itn = 1;
+    F.reset();
     for (int it = 0; it < P.max_iter; ++it)
     {
         if (!__any(active)) break;
@@ -213,21 +197,11 @@ __device__ __forceinline__ void rowlane_body(const RowParams &P, const ModelPara
                 const float t1 = sn[(N - 1) * WAVE] - a[N - 1];
                 pN = lin_cost<EXACT, H16>(pterm, rho, t1); // admm.cpp:83-84
             }
-            // ---------------- termination_condition (admm.cpp:91-109) ----------------
-            const float pri_x = row_max(is_x ? pri : 0.f), dua_x = row_max(is_x ? dua : 0.f);
-            const float pri_u = row_max(is_u ? pri : 0.f), dua_u = row_max(is_u ? dua : 0.f);
-            itn = it + 1;
-            bool conv = false;
-            if ((it + 1) % P.check_termination == 0)
-            {
-                r_ps = pri_x; r_ds = dua_x * rho; r_pi = pri_u; r_di = dua_u * rho;
-                conv = (r_ps < P.abs_pri_tol) && (r_pi < P.abs_pri_tol) && (r_ds < P.abs_dua_tol) && (r_di < P.abs_dua_tol);
-            }
-            if (conv)
-            {
-                st = TINY_STATUS_SOLVED_;
-                active = false;
-            }
+            // termination_condition (admm.cpp:91-109).  (The status is read back, not the value check() returns, and further down max_iter is
+            // tested in front of no_iterations(), so that the lead flag is formed behind the test: either way the fma N = 50 instantiations, which
+            // sit at 256 registers, spill one or two registers less — what their scratch is pinned at.)
+            F.check(P, it, pri, dua, is_x, is_u, rho);
+            if (F.solved()) active = false;
             else
             {
                 // ---------------- backward sweep: v=vnew, z=znew, linear cost, backward_pass_grad ----------------
@@ -277,7 +251,7 @@ __device__ __forceinline__ void rowlane_body(const RowParams &P, const ModelPara
         lqr(x0, c[0], sv0, x1); // [x_0 ; u_0] of the solve that just finished, in the solver's own arithmetic
         if (P.u0_traj && valid && is_u) P.u0_traj[((long long)ms * P.batch + inst) * NU + (r16 - NX)] = sv0;
         if constexpr (MPC) x0 = plant_step<NX, NU>(G, sv0); // x_1 = Adyn x0 + Bdyn u_0 (:110), the plant kernel's arithmetic
-        wstart += P.window_advance;
+        xref.advance(P);
         const float qrow = mats[(2 * NX + 2 * NU) * 16 + r16];
 #pragma unroll
         for (int i = 0; i < N; i++)
@@ -285,9 +259,7 @@ __device__ __forceinline__ void rowlane_body(const RowParams &P, const ModelPara
             float cqn = c[i];
             if (P.xref_mode == 1)
             {
-                int row = wstart + i;
-                row = row < P.table_rows ? row : P.table_rows - 1;
-                const float xr = ldw<H16>(P.xref_table, row * 16 + r16);
+                const float xr = xref.window(P, i, r16);
                 cqn = rnd<H16>(-(xr * qrow));
                 if (i == N - 1) xrN = xr;
             }
@@ -298,21 +270,11 @@ __device__ __forceinline__ void rowlane_body(const RowParams &P, const ModelPara
     }
     }
 
-    if (P.max_iter <= 0) // tiny_solve only sets status and iter (admm.cpp:114-117,151)
-    {
-        if (valid && r16 == 0)
-        {
-            P.status[inst] = TINY_STATUS_UNSOLVED_;
-            P.iter[inst] = 1;
-            atomicAdd(P.n_unsolved, 1);
-        }
-        return;
-    }
+    if (P.max_iter <= 0 && F.no_iterations(P, inst, valid && r16 == 0)) return;
 
     // ---------------- live-out: every work array written once ----------------
     if (valid)
     {
-        const bool solved = (st == TINY_STATUS_SOLVED_);
         float s = x0;
 #pragma unroll
         for (int i = 0; i < N; i++)
@@ -344,16 +306,9 @@ __device__ __forceinline__ void rowlane_body(const RowParams &P, const ModelPara
         if (MPC) // the host's plant step continues from here
         {
             if (is_x) P.x0buf[inst * NX + r16] = x0;
-            if (r16 == 0 && P.xref_mode == 1) P.xref_start[inst] = wstart;
+            if (r16 == 0 && P.xref_mode == 1) P.xref_start[inst] = xref.wstart;
         }
-        if (r16 == 0)
-        {
-            P.res[4 * inst + 0] = r_ps; P.res[4 * inst + 1] = r_pi;
-            P.res[4 * inst + 2] = r_ds; P.res[4 * inst + 3] = r_di;
-            P.status[inst] = st;
-            P.iter[inst] = itn;
-            if (!solved) atomicAdd(P.n_unsolved, 1);
-        }
+        if (r16 == 0) F.store(P, inst);
     }
 }
 
@@ -378,71 +333,36 @@ bool rowlane_supported(int nx, int nu, int N)
     return false;
 }
 
+// The run-time features and the template flags (H16, MPC, BPI, D32, OPT) they turn on.  Six tuples are instantiated per class and arithmetic:
+//   mpc_steps > 1 (closed loop on chip)      MPC    |  fp32 storage and batch-shared bounds only
+//   bounds_inst_stride != 0                  BPI    |  fp32 storage only (fp16 storage with them runs on the streaming row kernel)
+//   uref / en_d2p (the optional terms)       OPT    |  fp32 storage, batch-shared bounds, one solve per launch (read only then)
+//   dual32 (fp16 storage with fp32 duals)    D32 + H16
+//   h16                                      H16
 hipError_t launch_admm_rowlane(int nx, int nu, int N, bool exact, bool h16, const RowParams &P, hipStream_t stream)
 {
     const int nblocks = (P.batch + 3) / 4;
-    if (P.mpc_steps > 1) // closed loop on chip: fp32 storage and batch-shared bounds only
-    {
-        if (h16 || P.dual32 || P.bounds_inst_stride != 0) return hipErrorInvalidValue;
-#define TINY_ROWLANE_MPC_DISPATCH(NX, NU, NN)                                                               \
-    if (nx == NX && nu == NU && N == NN)                                                                    \
-    {                                                                                                       \
-        if (exact) hipLaunchKernelGGL((admm_rowlane_kernel<NX, NU, NN, true, false, true>), dim3(nblocks), dim3(WAVE), 0, stream, P);  \
-        else hipLaunchKernelGGL((admm_rowlane_kernel<NX, NU, NN, false, false, true>), dim3(nblocks), dim3(WAVE), 0, stream, P);     \
-        return hipGetLastError();                                                                           \
-    }
-        TINY_FOR_EACH_ROWLANE(TINY_ROWLANE_MPC_DISPATCH)
-        return hipErrorInvalidValue;
-    }
-    if (P.bounds_inst_stride != 0) // per-instance bounds: fp32 storage only (fp16 storage with them runs on the streaming row kernel)
-    {
-        if (h16 || P.dual32) return hipErrorInvalidValue;
-#define TINY_ROWLANE_BPI_DISPATCH(NX, NU, NN)                                                                            \
-    if (nx == NX && nu == NU && N == NN)                                                                                 \
-    {                                                                                                                    \
-        if (exact) hipLaunchKernelGGL((admm_rowlane_kernel<NX, NU, NN, true, false, false, true>), dim3(nblocks), dim3(WAVE), 0, stream, P);  \
-        else hipLaunchKernelGGL((admm_rowlane_kernel<NX, NU, NN, false, false, false, true>), dim3(nblocks), dim3(WAVE), 0, stream, P);      \
-        return hipGetLastError();                                                                                        \
-    }
-        TINY_FOR_EACH_ROWLANE(TINY_ROWLANE_BPI_DISPATCH)
-        return hipErrorInvalidValue;
-    }
-    if (P.uref != nullptr || P.en_d2p) // the optional terms (round 4): fp32 storage, batch-shared bounds
-    {
-        if (h16 || P.dual32) return hipErrorInvalidValue;
-#define TINY_ROWLANE_OPT_DISPATCH(NX, NU, NN)                                                                            \
-    if (nx == NX && nu == NU && N == NN)                                                                                 \
-    {                                                                                                                    \
-        if (exact) hipLaunchKernelGGL((admm_rowlane_kernel<NX, NU, NN, true, false, false, false, false, true>), dim3(nblocks), dim3(WAVE), 0, stream, P);  \
-        else hipLaunchKernelGGL((admm_rowlane_kernel<NX, NU, NN, false, false, false, false, false, true>), dim3(nblocks), dim3(WAVE), 0, stream, P);      \
-        return hipGetLastError();                                                                                        \
-    }
-        TINY_FOR_EACH_ROWLANE(TINY_ROWLANE_OPT_DISPATCH)
-        return hipErrorInvalidValue;
-    }
-    if (P.dual32) // fp16 storage with fp32 duals
-    {
-        if (!h16) return hipErrorInvalidValue;
-#define TINY_ROWLANE_D32_DISPATCH(NX, NU, NN)                                                                            \
-    if (nx == NX && nu == NU && N == NN)                                                                                 \
-    {                                                                                                                    \
-        if (exact) hipLaunchKernelGGL((admm_rowlane_kernel<NX, NU, NN, true, true, false, false, true>), dim3(nblocks), dim3(WAVE), 0, stream, P);  \
-        else hipLaunchKernelGGL((admm_rowlane_kernel<NX, NU, NN, false, true, false, false, true>), dim3(nblocks), dim3(WAVE), 0, stream, P);      \
-        return hipGetLastError();                                                                                        \
-    }
-        TINY_FOR_EACH_ROWLANE(TINY_ROWLANE_D32_DISPATCH)
-        return hipErrorInvalidValue;
-    }
-#define TINY_ROWLANE_LAUNCH(NX, NU, NN, EX, H) \
-    hipLaunchKernelGGL((admm_rowlane_kernel<NX, NU, NN, EX, H>), dim3(nblocks), dim3(WAVE), 0, stream, P)
-#define TINY_ROWLANE_DISPATCH(NX, NU, NN)                                                                   \
-    if (nx == NX && nu == NU && N == NN)                                                                    \
-    {                                                                                                       \
-        if (exact && !h16) TINY_ROWLANE_LAUNCH(NX, NU, NN, true, false);                                    \
-        else if (exact) TINY_ROWLANE_LAUNCH(NX, NU, NN, true, true);                                        \
-        else if (!h16) TINY_ROWLANE_LAUNCH(NX, NU, NN, false, false);                                       \
-        else TINY_ROWLANE_LAUNCH(NX, NU, NN, false, true);                                                  \
-        return hipGetLastError();                                                                           \
+    const bool mpc = P.mpc_steps > 1, bpi = P.bounds_inst_stride != 0, d32 = P.dual32 != 0;
+    const bool opt = !mpc && !bpi && (P.uref != nullptr || P.en_d2p);
+    if ((mpc && bpi) || ((mpc || bpi || opt) && (h16 || d32)) || (d32 && !h16)) return hipErrorInvalidValue;
+#define TINY_ROWLANE_LAUNCH(NX, NU, NN, EX, H, MP, BP, D, O) \
+    hipLaunchKernelGGL((admm_rowlane_kernel<NX, NU, NN, EX, H, MP, BP, D, O>), dim3(nblocks), dim3(WAVE), 0, stream, P)
+#define TINY_ROWLANE_FLAGS(NX, NU, NN, EX)                                                   \
+    do                                                                                       \
+    {                                                                                        \
+        if (mpc) TINY_ROWLANE_LAUNCH(NX, NU, NN, EX, false, true, false, false, false);      \
+        else if (bpi) TINY_ROWLANE_LAUNCH(NX, NU, NN, EX, false, false, true, false, false); \
+        else if (opt) TINY_ROWLANE_LAUNCH(NX, NU, NN, EX, false, false, false, false, true); \
+        else if (d32) TINY_ROWLANE_LAUNCH(NX, NU, NN, EX, true, false, false, true, false);  \
+        else if (h16) TINY_ROWLANE_LAUNCH(NX, NU, NN, EX, true, false, false, false, false); \
+        else TINY_ROWLANE_LAUNCH(NX, NU, NN, EX, false, false, false, false, false);         \
+    } while (0)
+#define TINY_ROWLANE_DISPATCH(NX, NU, NN)               \
+    if (nx == NX && nu == NU && N == NN)                \
+    {                                                   \
+        if (exact) TINY_ROWLANE_FLAGS(NX, NU, NN, true); \
+        else TINY_ROWLANE_FLAGS(NX, NU, NN, false);     \
+        return hipGetLastError();                       \
     }
     TINY_FOR_EACH_ROWLANE(TINY_ROWLANE_DISPATCH)
     return hipErrorInvalidValue;
@@ -455,13 +375,19 @@ hipError_t launch_admm_rowlane_pm(int nx, int nu, int N, bool exact, const RowPa
     if (P.dual32 || (mpc && bpi) || P.uref != nullptr || P.en_d2p || !M.mats || !M.rho) return hipErrorInvalidValue;
 #define TINY_ROWLANE_PM_LAUNCH(NX, NU, NN, EX, MP, BP) \
     hipLaunchKernelGGL((admm_rowlane_pm_kernel<NX, NU, NN, EX, MP, BP>), dim3(nblocks), dim3(WAVE), 0, stream, P, M)
-#define TINY_ROWLANE_PM_DISPATCH(NX, NU, NN)                                                                \
-    if (nx == NX && nu == NU && N == NN)                                                                    \
-    {                                                                                                       \
-        if (mpc) { if (exact) TINY_ROWLANE_PM_LAUNCH(NX, NU, NN, true, true, false); else TINY_ROWLANE_PM_LAUNCH(NX, NU, NN, false, true, false); } \
-        else if (bpi) { if (exact) TINY_ROWLANE_PM_LAUNCH(NX, NU, NN, true, false, true); else TINY_ROWLANE_PM_LAUNCH(NX, NU, NN, false, false, true); } \
-        else { if (exact) TINY_ROWLANE_PM_LAUNCH(NX, NU, NN, true, false, false); else TINY_ROWLANE_PM_LAUNCH(NX, NU, NN, false, false, false); } \
-        return hipGetLastError();                                                                           \
+#define TINY_ROWLANE_PM_FLAGS(NX, NU, NN, EX)                                \
+    do                                                                       \
+    {                                                                        \
+        if (mpc) TINY_ROWLANE_PM_LAUNCH(NX, NU, NN, EX, true, false);        \
+        else if (bpi) TINY_ROWLANE_PM_LAUNCH(NX, NU, NN, EX, false, true);   \
+        else TINY_ROWLANE_PM_LAUNCH(NX, NU, NN, EX, false, false);           \
+    } while (0)
+#define TINY_ROWLANE_PM_DISPATCH(NX, NU, NN)                \
+    if (nx == NX && nu == NU && N == NN)                    \
+    {                                                       \
+        if (exact) TINY_ROWLANE_PM_FLAGS(NX, NU, NN, true); \
+        else TINY_ROWLANE_PM_FLAGS(NX, NU, NN, false);      \
+        return hipGetLastError();                           \
     }
     TINY_FOR_EACH_ROWLANE(TINY_ROWLANE_PM_DISPATCH)
     return hipErrorInvalidValue;

@@ -33,18 +33,7 @@ __global__ __launch_bounds__(WAVE, WPS) void admm_wavestream_kernel(const RowPar
     WaveGains<NX, NU> G;
     G.load(P.mats, lane);
     const float qrow = P.mats[(2 * NX + 2 * NU) * WAVE + lane];
-    int wstart = 0;
-    if (P.xref_mode == 1) wstart = P.xref_start[inst];
-    const int xref_off = inst * (int)P.xref_inst_stride + lane;
-    auto xref_at = [&](int i) {
-        if (P.xref_mode == 1)
-        {
-            int row = wstart + i;
-            row = row < P.table_rows ? row : P.table_rows - 1;
-            return P.xref_table[row * WAVE + lane];
-        }
-        return P.xref[xref_off + i * WAVE];
-    };
+    const RowXref<false, WAVE> xref(P, inst, true, inst, lane);
     const float x0 = P.xu[rowbase];
     float pterm;
     {
@@ -52,25 +41,10 @@ __global__ __launch_bounds__(WAVE, WPS) void admm_wavestream_kernel(const RowPar
         float PT[NX], t[NX];
 #pragma unroll
         for (int k = 0; k < NX; k++) PT[k] = P.mats[(2 * NX + 2 * NU + 1 + k) * WAVE + lane];
-        lane_products<0, NX>(t, xref_at(N - 1), PT, vec, lane);
+        lane_products<0, NX>(t, xref.at(P, N - 1, lane), PT, vec, lane);
         pterm = -wreduce<PL::TERM>(t);
     }
-    int st = TINY_STATUS_UNSOLVED_, itn = 1;
-    float r_ps = 0.f, r_pi = 0.f, r_ds = 0.f, r_di = 0.f;
-    if (!P.cold_start)
-    {
-        r_ps = P.res[4 * inst + 0]; r_pi = P.res[4 * inst + 1];
-        r_ds = P.res[4 * inst + 2]; r_di = P.res[4 * inst + 3];
-    }
-    // max over the lanes of the wave, every lane gets the result
-    auto wave_max = [](float v) {
-        v = fmaxf(v, dpp_mov<0x128>(v)); v = fmaxf(v, dpp_mov<0x124>(v)); v = fmaxf(v, dpp_mov<0x122>(v)); v = fmaxf(v, dpp_mov<0x121>(v));
-        float m = v; // row maxima -> wave maximum through SGPRs
-        m = fmaxf(m, __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 16)));
-        m = fmaxf(m, __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 32)));
-        m = fmaxf(m, __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 48)));
-        return fmaxf(m, __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 0)));
-    };
+    SolveFrame F(P, inst, true);
     for (int it = 0; it < P.max_iter; ++it)
     {
         const bool last_iter = (it == P.max_iter - 1);
@@ -120,27 +94,14 @@ __global__ __launch_bounds__(WAVE, WPS) void admm_wavestream_kernel(const RowPar
         }
         const float pN = pterm - rho * t1; // admm.cpp:83-84
         P.pd[rowbase + (N - 1) * WAVE] = is_x ? pN : 0.f;
-        const float pri_x = wave_max(is_x ? pri : 0.f), dua_x = wave_max(is_x ? dua : 0.f);
-        const float pri_u = wave_max(is_u ? pri : 0.f), dua_u = wave_max(is_u ? dua : 0.f);
-        itn = it + 1;
-        bool conv = false;
-        if ((it + 1) % P.check_termination == 0) // admm.cpp:91-109
-        {
-            r_ps = pri_x; r_ds = dua_x * rho; r_pi = pri_u; r_di = dua_u * rho;
-            conv = (r_ps < P.abs_pri_tol) && (r_pi < P.abs_pri_tol) && (r_ds < P.abs_dua_tol) && (r_di < P.abs_dua_tol);
-        }
-        if (conv) // wave-uniform: the instance is the wave
-        {
-            st = TINY_STATUS_SOLVED_;
-            break;
-        }
+        if (F.judge(P, it, wave_residuals(pri, dua, is_x, is_u, rho))) break; // admm.cpp:91-109; wave-uniform: the instance is the wave
         float p = pN;
         P.vz[rowbase + (N - 1) * WAVE] = P.vzn[rowbase + (N - 1) * WAVE]; // admm.cpp:141-142
         struct Bwd { float sn, g, xr; };
         auto load_bwd = [&](int i) {
             const int o = rowbase + i * WAVE;
             Bwd f;
-            f.sn = P.vzn[o]; f.g = P.gy[o]; f.xr = xref_at(i);
+            f.sn = P.vzn[o]; f.g = P.gy[o]; f.xr = xref.at(P, i, lane);
             return f;
         };
         Bwd bq[PF];
@@ -167,22 +128,13 @@ __global__ __launch_bounds__(WAVE, WPS) void admm_wavestream_kernel(const RowPar
             }
         }
     }
-    if (P.max_iter <= 0) // tiny_solve only sets status and iter (admm.cpp:114-117,151)
-    {
-        if (lane == 0)
-        {
-            P.status[inst] = TINY_STATUS_UNSOLVED_;
-            P.iter[inst] = 1;
-            atomicAdd(P.n_unsolved, 1);
-        }
-        return;
-    }
+    if (F.no_iterations(P, inst, lane == 0)) return;
     {
         // live-out: q, r (admm.cpp:80-82) and, for a converged instance, x,u regenerated from the d it converged with
-        const bool solved = (st == TINY_STATUS_SOLVED_);
+        const bool solved = F.solved();
         // reset_workspace() folded into this launch (cold start): an instance that converged in its FIRST iteration ran no
         // backward sweep, which is what writes [p;d] and [v;z] — they are the zeros of the reset, materialised here
-        const bool fresh = (P.cold_start != 0) && solved && itn == 1;
+        const bool fresh = (P.cold_start != 0) && solved && F.itn == 1;
         float s = x0;
         for (int i = 0; i < N; i++)
         {
@@ -197,18 +149,11 @@ __global__ __launch_bounds__(WAVE, WPS) void admm_wavestream_kernel(const RowPar
             }
             if (solved) P.xu[o] = sv;
             s = xn;
-            const float cq = is_x ? -(xref_at(i) * qrow) : -0.f; // -0: r = -rho*(znew - y) keeps the sign of a zero difference
+            const float cq = is_x ? -(xref.at(P, i, lane) * qrow) : -0.f; // -0: r = -rho*(znew - y) keeps the sign of a zero difference
             const float lin = cq - rho * (P.vzn[o] - P.gy[o]);
             P.qr[o] = (i < N - 1 || is_x) ? lin : 0.f;
         }
-        if (lane == 0)
-        {
-            P.res[4 * inst + 0] = r_ps; P.res[4 * inst + 1] = r_pi;
-            P.res[4 * inst + 2] = r_ds; P.res[4 * inst + 3] = r_di;
-            P.status[inst] = st;
-            P.iter[inst] = itn;
-            if (!solved) atomicAdd(P.n_unsolved, 1);
-        }
+        if (lane == 0) F.store(P, inst);
     }
 }
 

@@ -61,18 +61,7 @@ __global__ __launch_bounds__(WAVE, 2) void admm_waveres_kernel(const RowParams P
     const float rho = P.rho;
     const float2 *bnd = reinterpret_cast<const float2 *>(P.bounds) + (size_t)inst * P.bounds_inst_stride + lane; // bnd[i * WAVE]
     const float qrow = P.mats[(2 * NX + 2 * NU) * WAVE + lane];
-    int wstart = 0;
-    if (P.xref_mode == 1) wstart = P.xref_start[inst];
-    const int xref_off = inst * (int)P.xref_inst_stride + lane;
-    auto xref_at = [&](int i) {
-        if (P.xref_mode == 1)
-        {
-            int row = wstart + i;
-            row = row < P.table_rows ? row : P.table_rows - 1;
-            return P.xref_table[row * WAVE + lane];
-        }
-        return P.xref[xref_off + i * WAVE];
-    };
+    const RowXref<false, WAVE> xref(P, inst, true, inst, lane);
     const bool cold = P.cold_start != 0, zdual = cold || (P.duals_zero != 0);
 
     // ---- live-in: a, c into registers, the slack into LDS ----
@@ -81,7 +70,7 @@ __global__ __launch_bounds__(WAVE, 2) void admm_waveres_kernel(const RowParams P
     {
         auto live_in = [&](int i, float &ai, float &ci) {
             const int o = rowbase + i * WAVE;
-            const float xr = xref_at(i);
+            const float xr = xref.at(P, i, lane);
             const float pd = cold ? 0.f : P.pd[o];
             ci = is_x ? -(xr * qrow) : pd; // admm.cpp:81 | d_i
             ai = zdual ? 0.f : P.gy[o];
@@ -109,21 +98,7 @@ __global__ __launch_bounds__(WAVE, 2) void admm_waveres_kernel(const RowParams P
         }
         else pterm = -lane_fma_dot<0, NX>(0.f, xrN, PT, vec, lane);
     }
-    int st = TINY_STATUS_UNSOLVED_, itn = 1;
-    float r_ps = 0.f, r_pi = 0.f, r_ds = 0.f, r_di = 0.f;
-    if (!P.cold_start)
-    {
-        r_ps = P.res[4 * inst + 0]; r_pi = P.res[4 * inst + 1];
-        r_ds = P.res[4 * inst + 2]; r_di = P.res[4 * inst + 3];
-    }
-    auto wave_max = [](float v) { // max over the lanes of the wave, every lane gets the result
-        v = fmaxf(v, dpp_mov<0x128>(v)); v = fmaxf(v, dpp_mov<0x124>(v)); v = fmaxf(v, dpp_mov<0x122>(v)); v = fmaxf(v, dpp_mov<0x121>(v));
-        float m = v;
-        m = fmaxf(m, __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 16)));
-        m = fmaxf(m, __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 32)));
-        m = fmaxf(m, __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 48)));
-        return fmaxf(m, __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 0)));
-    };
+    SolveFrame F(P, inst, true);
     float pN = 0.f;
     bool ran_bwd = false;
 
@@ -207,20 +182,7 @@ __global__ __launch_bounds__(WAVE, 2) void admm_waveres_kernel(const RowParams P
             if (N > 49) a.t1 = fwd_step(49, a.t1, c.t1);
         }
         pN = EXACT ? pterm - rho * t1 : __builtin_fmaf(-rho, t1, pterm); // admm.cpp:83-84
-        const float pri_x = wave_max(is_x ? pri : 0.f), dua_x = wave_max(is_x ? dua : 0.f);
-        const float pri_u = wave_max(is_u ? pri : 0.f), dua_u = wave_max(is_u ? dua : 0.f);
-        itn = it + 1;
-        bool conv = false;
-        if ((it + 1) % P.check_termination == 0) // admm.cpp:91-109
-        {
-            r_ps = pri_x; r_ds = dua_x * rho; r_pi = pri_u; r_di = dua_u * rho;
-            conv = (r_ps < P.abs_pri_tol) && (r_pi < P.abs_pri_tol) && (r_ds < P.abs_dua_tol) && (r_di < P.abs_dua_tol);
-        }
-        if (conv) // wave-uniform: the instance is the wave
-        {
-            st = TINY_STATUS_SOLVED_;
-            break;
-        }
+        if (F.judge(P, it, wave_residuals(pri, dua, is_x, is_u, rho))) break; // admm.cpp:91-109; wave-uniform: the instance is the wave
         // ---------------- backward sweep: (v = vnew is the in-place slack) linear cost + backward_pass_grad ----------------
         ran_bwd = true;
         {
@@ -302,19 +264,10 @@ __global__ __launch_bounds__(WAVE, 2) void admm_waveres_kernel(const RowParams P
             c.lo[0] = bwd_step(0, c.lo[0], 0.f, 0.f, false);
         }
     }
-    if (P.max_iter <= 0) // tiny_solve only sets status and iter (admm.cpp:114-117,151)
-    {
-        if (lane == 0)
-        {
-            P.status[inst] = TINY_STATUS_UNSOLVED_;
-            P.iter[inst] = 1;
-            atomicAdd(P.n_unsolved, 1);
-        }
-        return;
-    }
+    if (F.no_iterations(P, inst, lane == 0)) return;
     {
         // ---------------- live-out ----------------
-        const bool solved = (st == TINY_STATUS_SOLVED_);
+        const bool solved = F.solved();
         WaveGains<NX, NU> G;
         int oz;
         asm volatile("s_mov_b32 %0, 0" : "=s"(oz));
@@ -341,14 +294,7 @@ __global__ __launch_bounds__(WAVE, 2) void admm_waveres_kernel(const RowParams P
             P.gy[o] = ai;
             o += WAVE;
         }
-        if (lane == 0)
-        {
-            P.res[4 * inst + 0] = r_ps; P.res[4 * inst + 1] = r_pi;
-            P.res[4 * inst + 2] = r_ds; P.res[4 * inst + 3] = r_di;
-            P.status[inst] = st;
-            P.iter[inst] = itn;
-            if (!solved) atomicAdd(P.n_unsolved, 1);
-        }
+        if (lane == 0) F.store(P, inst);
     }
 }
 

@@ -1,7 +1,7 @@
 // rowlane_math.h — per-step arithmetic of the "row lane" mapping (one DPP row of 16 lanes = one instance; lane r owns
 // row r of the stacked vector [x ; u]), shared by the register-resident solvers (admm_rowlane.hip, admm_rowloop.hip) and
 // the streaming and single-function kernels (admm_steps.hip); at the end of the file, the frame of tiny_solve around the
-// sweeps for the rolled-loop and streaming kernels.  See admm_rowlane.hip for the mapping and the two arithmetic modes.
+// sweeps, which the quad-lane and wave kernels share too.  See admm_rowlane.hip for the mapping and the two arithmetic modes.
 #pragma once
 #include "tinympc_internal.h"
 #include "dpp_ops_gen.h"
@@ -352,42 +352,56 @@ __device__ __forceinline__ float terminal_term(const float *mats, int r16, float
 }
 
 // ---------------------------------------------------------------------------------------------
-// The frame of tiny_solve (admm.cpp:111-152) around the sweeps, stated once for the rolled-loop kernels (admm_rowloop.hip)
-// and the streaming ones (admm_steps.hip).  The other row kernels still carry their own copies.
+// The frame of tiny_solve (admm.cpp:111-152) around the sweeps, stated once for every kernel that restates the fused solve in
+// the row mapping, whatever its lane geometry: 16 lanes per instance (admm_rowlane.hip, admm_rowloop.hip, admm_rowstream_kernel
+// and the single-function kernel in admm_steps.hip), four lanes per instance (admm_quadlane.hip) and a wave per instance
+// (admm_wave.hip, admm_waveres.hip).  A kernel measures its residual maxima with its own reduction and hands them over; the rest
+// — the live-in of a warm start, the check_termination test, the tolerances, status / iter, the max_iter <= 0 exit, the live-out
+// and the reference row — is here.  (The tile kernels interleave their frame with the tile queue and keep their own.)
 // ---------------------------------------------------------------------------------------------
 
-// Xref.col(i) of one instance, row r16: a window of the shared table that starts at the instance's own row and is clamped to
-// the table's last row (xref_mode 1), or the instance's / the shared array.  `ld` is the instance index to LOAD with.
-template <bool H16>
+// Xref.col(i) of one instance, row r of a W-wide row layout (16, or WAVE for the wave kernels): a window of the shared table that
+// starts at the instance's own row and is clamped to the table's last row (xref_mode 1), or the instance's / the shared array.
+// `ld` is the instance index to LOAD with.
+template <bool H16, int W = 16>
 struct RowXref
 {
     int wstart = 0, off;
-    __device__ __forceinline__ RowXref(const RowParams &P, int inst, bool valid, int ld, int r16) : off(ld * (int)P.xref_inst_stride + r16)
+    __device__ __forceinline__ RowXref(const RowParams &P, int inst, bool valid, int ld, int r) : off(ld * (int)P.xref_inst_stride + r)
     {
         if (P.xref_mode == 1 && valid) wstart = P.xref_start[inst];
     }
-    __device__ __forceinline__ float at(const RowParams &P, int i, int r16) const
+    // row i of the window (xref_mode 1 only)
+    __device__ __forceinline__ float window(const RowParams &P, int i, int r) const
     {
-        if (P.xref_mode == 1)
-        {
-            int row = wstart + i;
-            row = row < P.table_rows ? row : P.table_rows - 1;
-            return ldw<H16>(P.xref_table, row * 16 + r16);
-        }
-        return ldw<H16>(P.xref, off + i * 16);
+        int row = wstart + i;
+        row = row < P.table_rows ? row : P.table_rows - 1;
+        return ldw<H16>(P.xref_table, row * W + r);
     }
+    __device__ __forceinline__ float at(const RowParams &P, int i, int r) const
+    {
+        if (P.xref_mode == 1) return window(P, i, r);
+        return ldw<H16>(P.xref, off + i * W);
+    }
+    // the on-chip closed loop moves the window between its solves; the kernel writes wstart back to xref_start at its end
+    __device__ __forceinline__ void advance(const RowParams &P) { wstart += P.window_advance; }
 };
 
 // The four residual fields of TinyWorkspace, res[4 * inst + 0..3] = primal state | primal input | dual state | dual input.
 struct RowResiduals
 {
     float ps = 0.f, pi = 0.f, ds = 0.f, di = 0.f;
-    // admm.cpp:95-98 from the per-lane maxima over the horizon: pri = max |[x;u] - [vnew;znew]|, dua = max |[v;z] - [vnew;znew]|
+    // admm.cpp:95-98 from the maxima over the horizon and the rows of a kind: pri = max |[x;u] - [vnew;znew]|, dua = max |[v;z] - [vnew;znew]|
+    __device__ __forceinline__ void set(float pri_x, float dua_x, float pri_u, float dua_u, float rho)
+    {
+        ps = pri_x; ds = dua_x * rho; pi = pri_u; di = dua_u * rho;
+    }
+    // the same from the per-lane maxima of a 16-lane row
     __device__ __forceinline__ void measure(float pri, float dua, bool is_x, bool is_u, float rho)
     {
         const float pri_x = row_max(is_x ? pri : 0.f), dua_x = row_max(is_x ? dua : 0.f);
         const float pri_u = row_max(is_u ? pri : 0.f), dua_u = row_max(is_u ? dua : 0.f);
-        ps = pri_x; ds = dua_x * rho; pi = pri_u; di = dua_u * rho;
+        set(pri_x, dua_x, pri_u, dua_u, rho);
     }
     // admm.cpp:100-103
     __device__ __forceinline__ bool below_tol(const RowParams &P) const
@@ -399,7 +413,7 @@ struct RowResiduals
 };
 
 // status, iter and the residual fields of one instance through a fused solve.  `lead` is the one lane that writes them
-// (lane 0 of a valid instance's row).
+// (the first lane of a valid instance).
 struct SolveFrame
 {
     RowResiduals res;                            // a warm start keeps the fields of the previous solve until a check overwrites them;
@@ -408,11 +422,12 @@ struct SolveFrame
     {
         if (valid && !P.cold_start) res.load(P, inst);
     }
-    // admm.cpp:120 and termination_condition (admm.cpp:91-109, 135-136) after the forward sweep of iteration `it`; true: converged
-    __device__ __forceinline__ bool check(const RowParams &P, int it, float pri, float dua, bool is_x, bool is_u, float rho)
+    // top of every solve of the on-chip closed loop (admm.cpp:114-115): the residual fields carry over, as in the workspace
+    __device__ __forceinline__ void reset() { st = TINY_STATUS_UNSOLVED_; itn = 1; }
+    // admm.cpp:120 and termination_condition (admm.cpp:91-109, 135-136) after the forward sweep of iteration `it`, from the
+    // residuals `now` the kernel measured there; true: converged
+    __device__ __forceinline__ bool judge(const RowParams &P, int it, const RowResiduals &now)
     {
-        RowResiduals now;
-        now.measure(pri, dua, is_x, is_u, rho);
         itn = it + 1;
         bool conv = false;
         if ((it + 1) % P.check_termination == 0)
@@ -422,6 +437,13 @@ struct SolveFrame
         }
         if (conv) st = TINY_STATUS_SOLVED_;
         return conv;
+    }
+    // the same for 16 lanes per instance, from the per-lane maxima
+    __device__ __forceinline__ bool check(const RowParams &P, int it, float pri, float dua, bool is_x, bool is_u, float rho)
+    {
+        RowResiduals now;
+        now.measure(pri, dua, is_x, is_u, rho);
+        return judge(P, it, now);
     }
     __device__ __forceinline__ bool solved() const { return st == TINY_STATUS_SOLVED_; }
     // max_iter <= 0: tiny_solve only sets status and iter (admm.cpp:114-117,151).  true: the kernel returns, nothing else is written

@@ -33,6 +33,26 @@ __device__ __forceinline__ float wreduce(const float (&t)[NN])
     else return reduce<PLAN>(t);
 }
 
+// max over the lanes of the wave, every lane gets the result: row maxima, then the four rows through SGPRs
+__device__ __forceinline__ float wave_max(float v)
+{
+    v = row_max(v);
+    float m = v;
+    m = fmaxf(m, __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 16)));
+    m = fmaxf(m, __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 32)));
+    m = fmaxf(m, __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 48)));
+    return fmaxf(m, __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 0)));
+}
+// the four residual fields (admm.cpp:95-98) from the per-lane maxima of a wave that holds one instance
+__device__ __forceinline__ RowResiduals wave_residuals(float pri, float dua, bool is_x, bool is_u, float rho)
+{
+    const float pri_x = wave_max(is_x ? pri : 0.f), dua_x = wave_max(is_x ? dua : 0.f);
+    const float pri_u = wave_max(is_u ? pri : 0.f), dua_u = wave_max(is_u ? dua : 0.f);
+    RowResiduals now;
+    now.set(pri_x, dua_x, pri_u, dua_u, rho);
+    return now;
+}
+
 template <int NX, int NU>
 struct WavePlans
 {

@@ -1306,7 +1306,7 @@ def test_quadlane_kernel_vs_oracle(tinympc, oracle_mod, B):
     umn = umn * np.linspace(0.2, 1.0, N - 1, dtype=np.float32)[:, None]   # per-step input bounds, some of them active
     bnds = (xmn, xmx, umn, umx)
     for settings in (dict(max_iter=150), dict(max_iter=40, check_termination=3), dict(max_iter=1), dict(max_iter=4),
-                     dict(max_iter=30, en_state_bound=0, en_input_bound=0)):
+                     dict(max_iter=30, en_state_bound=0, en_input_bound=0), dict(max_iter=0)):
         settings = dict(O.DEFAULT_SETTINGS, **settings)
         for exact in (True, False):
             sol = tinympc.TinyBatchSolver(prob, B, settings=settings)
