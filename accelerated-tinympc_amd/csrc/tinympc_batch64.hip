@@ -18,6 +18,8 @@
 
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -102,6 +104,17 @@ struct Params64
     double *res;        // [4][bpad]
     int *status, *iter, *n_unsolved;
 };
+// closed loop on chip: the further arguments of the MPC instantiations of the sixteen-lane kernel (a struct of their own: the one-solve kernels
+// keep their kernel arguments, and with them their code)
+struct Mpc64
+{
+    int mpc_steps, window_advance, table_rows; // table_rows > 0: the reference is a window into `table`
+    const double *table;                       // [table_rows][nx]
+    int *xref_start;                           // [batch], read at live-in and written back after the last solve
+    double *u0_traj;                           // [mpc_steps][batch][nu] or NULL; the kernel stores every step but the last
+};
+__device__ __forceinline__ Mpc64 loop_args() { return Mpc64{}; }
+__device__ __forceinline__ Mpc64 loop_args(const Mpc64 &l) { return l; }
 
 template <int NX, int NU>
 __global__ __launch_bounds__(WAVE64) void admm_f64_kernel(const Params64 P)
@@ -355,9 +368,16 @@ constexpr int F64_AHEAD = 4; // bounds are fetched this many steps ahead of thei
 // (32 or 64 steps: registers are indexed statically, so the body stays unrolled) and the horizon n = P.N <= N is a launch parameter;
 // the steps past it are skipped by wave-uniform branches.  With a capacity of 64 the backward sweep's [p ; d] (live-out only) is
 // written through to its arrays instead of being held in 2 x 64 registers.
-template <int NX, int NU, int N, bool RT = false>
-__global__ __launch_bounds__(WAVE64, (N <= 12 ? 2 : 1)) void admm_f64_rows_kernel(const Params64 P, const double *__restrict__ gains)
+//
+// MPC = true (instantiated separately, so that the one-solve kernels keep their code): the examples' closed loop on chip.  L.mpc_steps times
+// {y = g = 0; tiny_solve; x.col(0) = Adyn x.col(0) + Bdyn u.col(0); start += window_advance} with the whole workspace staying in registers / LDS
+// between two solves; the plant step after the last solve is the host's (plant64_run_kernel).  Only where [p ; d] is held in registers.
+template <int NX, int NU, int N, bool RT = false, bool MPC = false, class... LOOP>
+__global__ __launch_bounds__(WAVE64, (N <= 12 ? 2 : 1)) void admm_f64_rows_kernel(const Params64 P, const double *__restrict__ gains, const LOOP... loop)
 {
+    static_assert(sizeof...(LOOP) == (MPC ? 1 : 0), "the closed-loop instantiations take one further argument, an Mpc64; the one-solve kernels none");
+    [[maybe_unused]] const Mpc64 L = loop_args(loop...);
+    static_assert(!MPC || !(RT && N > 32), "the on-chip loop takes the workspace's d from the registers of [p ; d]");
     static_assert(NX + NU <= 16 && !(NX >= 8 && NU >= 8), "16-lane mapping; both dims >= 8 would take Eigen's GEMV kernel");
     static_assert(!RT || N > 20, "the runtime-horizon variant indexes the slack by the horizon: it keeps it in LDS");
     const int n = RT ? P.N : N; // the horizon
@@ -420,21 +440,30 @@ __global__ __launch_bounds__(WAVE64, (N <= 12 ? 2 : 1)) void admm_f64_rows_kerne
 #define BB_SET(i, v) do { if constexpr (LDS_SLACK) sl[(2 * (i)) * WAVE64] = (v); else bb_r[LDS_SLACK ? 0 : (i)] = (v); } while (0)
 #define SN_SET(i, v) do { if constexpr (LDS_SLACK) sl[(2 * (i) + 1) * WAVE64] = (v); else sn_r[LDS_SLACK ? 0 : (i)] = (v); } while (0)
     double xrN = 0.0;
+    // row i of a window reference: table[min(start + i, rows - 1)] (the clamp of the window gather); the table is small and stays in L2
+    [[maybe_unused]] const bool window = MPC && L.table_rows > 0;
+    [[maybe_unused]] int wstart = 0;
+    if constexpr (MPC) wstart = window ? L.xref_start[b] : 0;
+    [[maybe_unused]] auto win_at = [&](int i) -> double {
+        const int tr = wstart + i < L.table_rows - 1 ? wstart + i : L.table_rows - 1;
+        return is_x ? L.table[(size_t)tr * NX + row] : 0.0;
+    };
 #pragma unroll
     for (int i = 0; i < N; i++)
     {
         if (RT && i >= n) continue;
         double xr = 0.0;
-        if (is_x) xr = P.xref[((size_t)i * NX + row) * (size_t)P.xref_stride + (P.xref_stride > 1 ? b : 0)];
+        if (MPC && window) xr = win_at(i);
+        else if (is_x) xr = P.xref[((size_t)i * NX + row) * (size_t)P.xref_stride + (P.xref_stride > 1 ? b : 0)];
         const double pdi = ld(TINY_ARR_P, TINY_ARR_D, i);
         if constexpr (PD_REG) pd[i] = pdi;
         C_(i) = is_x ? -(xr * qrow) : pdi;            // admm.cpp:81 | d_i
-        A_(i) = ld(TINY_ARR_G, TINY_ARR_Y, i);
+        A_(i) = MPC ? 0.0 : ld(TINY_ARR_G, TINY_ARR_Y, i); // (the closed loop starts every solve from y = g = 0)
         BB_SET(i, ld(TINY_ARR_V, TINY_ARR_Z, i));
         SN_SET(i, 0.0);
         if (i == n - 1) xrN = xr;
     }
-    const double x0 = ld(TINY_ARR_X, TINY_ARR_U, 0); // x.col(0) on the x rows
+    double x0 = ld(TINY_ARR_X, TINY_ARR_U, 0); // x.col(0) on the x rows
     double pterm;
     {
         double PT[NX], t[NX]; // p.col(N-1) = -(Xref.col(N-1)^T * Pinf)  (admm.cpp:83): a vectorised reduction over k
@@ -452,6 +481,8 @@ __global__ __launch_bounds__(WAVE64, (N <= 12 ? 2 : 1)) void admm_f64_rows_kerne
     bool active = valid;
     double pN = 0.0;
 
+    [[maybe_unused]] int ms = 0; // the MPC step of the on-chip closed loop
+next_solve: // (a label, not a loop around the solve: the one-solve instantiations keep the code they had without one)
     for (int it = 0; it < P.max_iter; ++it)
     {
         if (!__any(active)) break;
@@ -550,6 +581,61 @@ __global__ __launch_bounds__(WAVE64, (N <= 12 ? 2 : 1)) void admm_f64_rows_kerne
             p = pn;
         }
     }
+    if constexpr (MPC)
+    if (ms + 1 < L.mpc_steps)
+    {
+        // ---- advance to the next MPC step (quadrotor_tracking.cpp:101-118): nothing leaves the chip but u.col(0) ----
+        double t[NX], t2[NU];
+        row_products<0, NX>(t, x0, M1);
+        const double acc = is_x ? lazy_sum<NX>(t) : lazy_sum<NU>(t);
+        const double u0 = -acc - C_(0); // [. ; u_0] of the solve that just finished: step 0 of the forward recursion (admm.cpp:31)
+        if (L.u0_traj && valid && is_u) L.u0_traj[((size_t)ms * P.batch + inst) * NU + row] = u0;
+        // x.col(0) = Adyn * x.col(0) + Bdyn * u.col(0) in plant64_kernel's order: rows and depth >= 8 is the GEMV accumulator from +0
+        double ax;
+        if constexpr (NX >= 8)
+        {
+            double c = 0.0;
+#pragma unroll
+            for (int j = 0; j < NX; j++) c = t[j] + c;
+            ax = c * 1.0 + 0.0;
+        }
+        else ax = lazy_sum<NX>(t);
+        row_products<NX, NU>(t2, u0, M2);
+        x0 = ax + lazy_sum<NX>(t2); // (x rows; the other lanes' value is never read as a state)
+        if (window) wstart += L.window_advance;
+        // the gains through an offset the compiler cannot see through (as the bounds above): otherwise it keeps Q and the NX registers of
+        // Pinf's row from live-in alive through every solve instead of loading them again here
+        int ozg;
+        asm volatile("s_mov_b32 %0, 0" : "=s"(ozg));
+        const double *const gains_again = gains + ozg;
+        const double qrow_again = gains_again[(2 * NX + 2 * NU) * 16 + r16];
+#pragma unroll
+        for (int i = 0; i < N; i++)
+        {
+            if (RT && i >= n) continue;
+            double cx = C_(i);
+            if (window)
+            {
+                const double xr = win_at(i);
+                cx = -(xr * qrow_again);
+                if (i == n - 1) xrN = xr;
+            }
+            C_(i) = is_x ? cx : pd[i]; // d of the workspace is that of the last executed backward sweep (keep_d)
+            A_(i) = 0.0;               // y = g = 0 (quadrotor_hovering.cpp:100-101)
+            __builtin_amdgcn_sched_barrier(0); // one table row in flight at a time: hoisted together the N loads cost 2N registers
+        }
+        if (window) // admm.cpp:83 for the window's new last row, as at live-in
+        {
+            double PT[NX], tp[NX];
+#pragma unroll
+            for (int k = 0; k < NX; k++) PT[k] = gains_again[(2 * NX + 2 * NU + 1 + k) * 16 + r16];
+            row_products<0, NX>(tp, xrN, PT);
+            pterm = -vec_sum(tp);
+        }
+        status = ST_UNSOLVED; itn = 1; active = valid; // the residual fields carry over: they are live-in of the next tiny_solve
+        ++ms;
+        goto next_solve;
+    }
     // ---- live-out: every work array once ----
     {
         const bool solved = status == ST_SOLVED;
@@ -586,6 +672,8 @@ __global__ __launch_bounds__(WAVE64, (N <= 12 ? 2 : 1)) void admm_f64_rows_kerne
             P.status[inst] = status;
             P.iter[inst] = itn;
             if (!solved) atomicAdd(P.n_unsolved, 1);
+            if constexpr (MPC)
+                if (window) L.xref_start[inst] = wstart;
         }
     }
 #undef A_
@@ -801,18 +889,14 @@ __global__ void unpack64_kernel(const double *__restrict__ src, double *__restri
 // sequential sum (tests/test_oracle.py: test_plant_step_bit_exact_vs_compiled_reference pins the oracle's restatement of
 // this against the compiled expression, fp64 configurations included).
 template <int NX, int NU>
-__global__ void plant64_kernel(double *__restrict__ X, const double *__restrict__ U, const double *__restrict__ mats, int batch, int bpad)
+__device__ __forceinline__ void plant64_step(double *__restrict__ X, const double (&u)[NU], const double *__restrict__ mats, int b, int bpad)
 {
     static_assert(!(NX >= 8 && NU >= 8), "Bdyn*u would take the GEMV kernel too");
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= batch) return;
     constexpr int OFF_A = NU * NX + NX * NX + NU * NU + NX * NX, OFF_B = OFF_A + NX * NX;
     const double *A = mats + OFF_A, *Bm = mats + OFF_B;
-    double x[NX], u[NU], xn[NX];
+    double x[NX], xn[NX];
 #pragma unroll
     for (int j = 0; j < NX; j++) x[j] = X[(size_t)j * bpad + b];
-#pragma unroll
-    for (int j = 0; j < NU; j++) u[j] = U[(size_t)j * bpad + b];
 #pragma unroll
     for (int i = 0; i < NX; i++)
     {
@@ -829,6 +913,49 @@ __global__ void plant64_kernel(double *__restrict__ X, const double *__restrict_
     }
 #pragma unroll
     for (int i = 0; i < NX; i++) X[(size_t)i * bpad + b] = xn[i];
+}
+template <int NX, int NU>
+__global__ void plant64_kernel(double *__restrict__ X, const double *__restrict__ U, const double *__restrict__ mats, int batch, int bpad)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= batch) return;
+    double u[NU];
+#pragma unroll
+    for (int j = 0; j < NU; j++) u[j] = U[(size_t)j * bpad + b];
+    plant64_step<NX, NU>(X, u, mats, b, bpad);
+}
+// The plant step of a multi-step run (tiny_batch64_mpc_run): the same step; it also records u.col(0) in this MPC step's row of the
+// trajectory ([B][nu], may be NULL) and slides the instance's reference window (start may be NULL).
+template <int NX, int NU>
+__global__ void plant64_run_kernel(double *__restrict__ X, const double *__restrict__ U, const double *__restrict__ mats, int batch, int bpad,
+                                   double *__restrict__ u0_row, int *__restrict__ start, int window_advance)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= batch) return;
+    double u[NU];
+#pragma unroll
+    for (int j = 0; j < NU; j++) u[j] = U[(size_t)j * bpad + b];
+    if (u0_row)
+    {
+#pragma unroll
+        for (int j = 0; j < NU; j++) u0_row[(size_t)b * NU + j] = u[j];
+    }
+    plant64_step<NX, NU>(X, u, mats, b, bpad);
+    if (start) start[b] += window_advance;
+}
+// a window reference as the per-instance array the one-solve kernels read: row i of instance b is table[min(start[b] + i, rows - 1)]
+__global__ void gather_window64_kernel(const double *__restrict__ table, const int *__restrict__ start, double *__restrict__ dst, int rows, int N, int nx,
+                                       int batch, int bpad)
+{
+    const long long total = (long long)batch * N * nx;
+    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x)
+    {
+        const int b = (int)(e % batch);
+        const long long t = e / batch;
+        const int row = (int)(t % nx), i = (int)(t / nx);
+        const int tr = start[b] + i < rows - 1 ? start[b] + i : rows - 1;
+        dst[((long long)i * nx + row) * bpad + b] = table[(long long)tr * nx + row];
+    }
 }
 
 thread_local std::string g_err64;
@@ -871,6 +998,13 @@ struct TinyBatch64
     double *row_gains = nullptr; // [3nx + 2nu + 1 + nx][16]: the matrices as one register per column and lane (admm_f64_rows_kernel)
     int kernel_choice = 0;       // tiny_batch64_select_kernel: 0 auto, 1 thread per instance, 2 sixteen lanes per instance
     int *status = nullptr, *iter = nullptr, *n_unsolved = nullptr;
+    // window reference (tiny_batch64_set_xref_window): the table and the per-instance starts live on the device; xwin is the window gathered
+    // into a per-instance array for the kernels that read one (allocated on first use, redone after the starts have moved)
+    double *table = nullptr, *xwin = nullptr, *u0_traj = nullptr;
+    int *xref_start = nullptr;
+    int table_rows = 0;      // > 0: the reference is the window
+    bool xwin_valid = false;
+    size_t u0_traj_cap = 0;  // doubles
     std::vector<double> hm; // host copy of the packed matrices
     bool have_cache = false, have_dyn = false, have_settings = false, mats_dirty = true;
     double rho = 0, abs_pri_tol = 0, abs_dua_tol = 0;
@@ -955,9 +1089,27 @@ int set_input(TinyBatch64 *tb, int which, const double *src, int shared)
     HIP64(hipDeviceSynchronize());
     tb->in_stride[which] = stride;
     tb->in_set[which] = true;
+    if (which == 0) tb->table_rows = 0; // an array reference replaces a window
     return 0;
 }
-int prepare64(TinyBatch64 *tb, Params64 &P)
+// gathers the window into tb->xwin where the starts have moved since the last gather
+int gather_window64(TinyBatch64 *tb)
+{
+    if (tb->xwin_valid) return 0;
+    const size_t bytes = (size_t)tb->N * tb->nx * tb->bpad * sizeof(double);
+    if (!tb->xwin)
+    {
+        HIP64(hipMalloc((void **)&tb->xwin, bytes));
+        HIP64(hipMemsetAsync(tb->xwin, 0, bytes, 0));
+    }
+    hipLaunchKernelGGL(gather_window64_kernel, dim3(grid64((long long)tb->batch * tb->N * tb->nx)), dim3(256), 0, 0, (const double *)tb->table,
+                       (const int *)tb->xref_start, tb->xwin, tb->table_rows, tb->N, tb->nx, tb->batch, tb->bpad);
+    HIP64(hipGetLastError());
+    tb->xwin_valid = true;
+    return 0;
+}
+// gathered_ref = false: the launch reads a window reference from the table itself (the on-chip closed loop)
+int prepare64(TinyBatch64 *tb, Params64 &P, bool gathered_ref = true)
 {
     if (!tb->have_cache || !tb->have_dyn || !tb->have_settings)
         return fail64(TINY_BATCH_ENOTREADY, "set_cache, set_dynamics and set_settings must be called first");
@@ -980,6 +1132,12 @@ int prepare64(TinyBatch64 *tb, Params64 &P)
     P.xref = tb->in[0]; P.xmin = tb->in[1]; P.xmax = tb->in[2]; P.umin = tb->in[3]; P.umax = tb->in[4];
     P.xref_stride = tb->in_stride[0]; P.xb_stride = tb->in_stride[1]; P.ub_stride = tb->in_stride[3];
     P.mats = tb->mats; P.res = tb->res; P.status = tb->status; P.iter = tb->iter; P.n_unsolved = tb->n_unsolved;
+    if (tb->table_rows > 0 && gathered_ref)
+    {
+        const int rc = gather_window64(tb);
+        if (rc < 0) return rc;
+        P.xref = tb->xwin; P.xref_stride = tb->bpad;
+    }
     return 0;
 }
 
@@ -997,6 +1155,58 @@ int run_step64(TinyBatch64 *tb, int *conv_dev)
     TINY_FOR_EACH_F64DIMS(TINY_F64_STEP_LAUNCH)
     HIP64(hipGetLastError());
     HIP64(hipDeviceSynchronize());
+    return 0;
+}
+
+bool rows_chosen(const TinyBatch64 *tb) { return tb->kernel_choice == 2 || (tb->kernel_choice == 0 && rows_supported(tb->nx, tb->nu, tb->N)); }
+// whether a closed-loop run takes the on-chip loop: the sixteen-lane kernel with [p ; d] in registers (the unrolled instantiations and the capacity-32
+// body).  max_iter <= 0 (tiny_solve sets status and iter only) is left to the launch sequence.  Developer aid: TINYMPC_F64_LOOP=sequence sends
+// every run through the launch sequence (tools/closed_loop64_time.py times the two against each other over the same solve kernel).
+bool onchip64(const TinyBatch64 *tb)
+{
+    const char *force = getenv("TINYMPC_F64_LOOP");
+    if (force && !strcmp(force, "sequence")) return false;
+    return rows_chosen(tb) && rows_supported(tb->nx, tb->nu, tb->N) && (rows_unrolled(tb->nx, tb->nu, tb->N) || tb->N <= 32) && tb->max_iter >= 1;
+}
+// the solve kernel the handle selects, on the null stream; mpc: the on-chip closed-loop instantiation (L->mpc_steps solves)
+int launch_solve64(TinyBatch64 *tb, const Params64 &P, const Mpc64 *L = nullptr)
+{
+    const bool mpc = L != nullptr;
+    const bool rows = rows_chosen(tb);
+    if (rows && !rows_supported(tb->nx, tb->nu, tb->N))
+        return fail64(TINY_BATCH_EUNSUPPORTED, "the sixteen-lane fp64 kernel has no instantiation for nx=%d nu=%d N=%d", tb->nx, tb->nu, tb->N);
+    const int nblocks = tb->bpad / WAVE64;
+    if (rows)
+    {
+        const int nrow_blocks = (tb->batch + 3) / 4;
+#define TINY_F64ROWS_LAUNCH(NX, NU, NN)                                                                                                          \
+    if (tb->nx == NX && tb->nu == NU && tb->N == NN)                                                                                             \
+    {                                                                                                                                            \
+        if (mpc) hipLaunchKernelGGL((admm_f64_rows_kernel<NX, NU, NN, false, true, Mpc64>), dim3(nrow_blocks), dim3(WAVE64), 0, 0, P, (const double *)tb->row_gains, *L); \
+        else hipLaunchKernelGGL((admm_f64_rows_kernel<NX, NU, NN>), dim3(nrow_blocks), dim3(WAVE64), 0, 0, P, (const double *)tb->row_gains);   \
+    }
+        if (rows_unrolled(tb->nx, tb->nu, tb->N)) { TINY_FOR_EACH_F64ROWS(TINY_F64ROWS_LAUNCH) }
+        else
+        {
+#define TINY_F64ROWS_RT_LAUNCH(NX, NU)                                                                                                            \
+    if (tb->nx == NX && tb->nu == NU)                                                                                                             \
+    {                                                                                                                                             \
+        if (tb->N <= 32 && mpc) hipLaunchKernelGGL((admm_f64_rows_kernel<NX, NU, 32, true, true, Mpc64>), dim3(nrow_blocks), dim3(WAVE64), 0, 0, P, (const double *)tb->row_gains, *L); \
+        else if (tb->N <= 32) hipLaunchKernelGGL((admm_f64_rows_kernel<NX, NU, 32, true>), dim3(nrow_blocks), dim3(WAVE64), 0, 0, P, (const double *)tb->row_gains); \
+        else if (mpc) return fail64(TINY_BATCH_EUNSUPPORTED, "the capacity-64 body has no on-chip closed loop");                                 \
+        else hipLaunchKernelGGL((admm_f64_rows_kernel<NX, NU, 64, true>), dim3(nrow_blocks), dim3(WAVE64), 0, 0, P, (const double *)tb->row_gains);             \
+    }
+            TINY_FOR_EACH_F64ROWS_RT(TINY_F64ROWS_RT_LAUNCH)
+        }
+    }
+    else
+    {
+        if (mpc) return fail64(TINY_BATCH_EUNSUPPORTED, "the thread-per-instance kernel has no on-chip closed loop");
+#define TINY_F64_LAUNCH(NX, NU) \
+    if (tb->nx == NX && tb->nu == NU) hipLaunchKernelGGL((admm_f64_kernel<NX, NU>), dim3(nblocks), dim3(WAVE64), 0, 0, P);
+        TINY_FOR_EACH_F64DIMS(TINY_F64_LAUNCH)
+    }
+    HIP64(hipGetLastError());
     return 0;
 }
 
@@ -1054,6 +1264,7 @@ void tiny_batch64_destroy(TinyBatch64 *tb)
     for (int w = 0; w < 5; w++) (void)hipFree(tb->in[w]);
     (void)hipFree(tb->mats); (void)hipFree(tb->res); (void)hipFree(tb->staging); (void)hipFree(tb->row_gains);
     (void)hipFree(tb->status); (void)hipFree(tb->iter); (void)hipFree(tb->n_unsolved);
+    (void)hipFree(tb->table); (void)hipFree(tb->xwin); (void)hipFree(tb->u0_traj); (void)hipFree(tb->xref_start);
     delete tb;
 }
 
@@ -1146,36 +1357,11 @@ int tiny_batch64_solve(TinyBatch64 *tb)
         const int rc = prepare64(tb, P);
         if (rc < 0) return rc;
     }
-    const bool rows = tb->kernel_choice == 2 || (tb->kernel_choice == 0 && rows_supported(tb->nx, tb->nu, tb->N));
-    if (rows && !rows_supported(tb->nx, tb->nu, tb->N))
-        return fail64(TINY_BATCH_EUNSUPPORTED, "the sixteen-lane fp64 kernel has no instantiation for nx=%d nu=%d N=%d", tb->nx, tb->nu, tb->N);
     HIP64(hipMemset(tb->n_unsolved, 0, sizeof(int)));
-    const int nblocks = tb->bpad / WAVE64;
-    if (rows)
     {
-        const int nrow_blocks = (tb->batch + 3) / 4;
-#define TINY_F64ROWS_LAUNCH(NX, NU, NN)                                                                                            \
-    if (tb->nx == NX && tb->nu == NU && tb->N == NN)                                                                               \
-        hipLaunchKernelGGL((admm_f64_rows_kernel<NX, NU, NN>), dim3(nrow_blocks), dim3(WAVE64), 0, 0, P, (const double *)tb->row_gains);
-        if (rows_unrolled(tb->nx, tb->nu, tb->N)) { TINY_FOR_EACH_F64ROWS(TINY_F64ROWS_LAUNCH) }
-        else
-        {
-#define TINY_F64ROWS_RT_LAUNCH(NX, NU)                                                                                              \
-    if (tb->nx == NX && tb->nu == NU)                                                                                               \
-    {                                                                                                                               \
-        if (tb->N <= 32) hipLaunchKernelGGL((admm_f64_rows_kernel<NX, NU, 32, true>), dim3(nrow_blocks), dim3(WAVE64), 0, 0, P, (const double *)tb->row_gains); \
-        else hipLaunchKernelGGL((admm_f64_rows_kernel<NX, NU, 64, true>), dim3(nrow_blocks), dim3(WAVE64), 0, 0, P, (const double *)tb->row_gains);             \
+        const int rc = launch_solve64(tb, P);
+        if (rc < 0) return rc;
     }
-            TINY_FOR_EACH_F64ROWS_RT(TINY_F64ROWS_RT_LAUNCH)
-        }
-    }
-    else
-    {
-#define TINY_F64_LAUNCH(NX, NU) \
-    if (tb->nx == NX && tb->nu == NU) hipLaunchKernelGGL((admm_f64_kernel<NX, NU>), dim3(nblocks), dim3(WAVE64), 0, 0, P);
-        TINY_FOR_EACH_F64DIMS(TINY_F64_LAUNCH)
-    }
-    HIP64(hipGetLastError());
     int n = 0;
     HIP64(hipMemcpy(&n, tb->n_unsolved, sizeof(int), hipMemcpyDeviceToHost));
     return n > 0 ? 1 : 0;
@@ -1196,6 +1382,105 @@ int tiny_batch64_mpc_step(TinyBatch64 *tb)
     HIP64(hipGetLastError());
     return rc;
 }
+
+int tiny_batch64_set_xref_window(TinyBatch64 *tb, const double *table, int rows, const int *start)
+{
+    CHECK64(tb && table && start, "NULL argument");
+    CHECK64(rows >= tb->N, "trajectory table has %d rows, need at least N=%d", rows, tb->N);
+    for (int b = 0; b < tb->batch; b++)
+        CHECK64(start[b] >= 0 && start[b] + tb->N <= rows, "window start[%d]=%d out of range for %d rows, N=%d", b, start[b], rows, tb->N);
+    HIP64(hipSetDevice(tb->device));
+    if (tb->table && tb->table_rows != rows) { (void)hipFree(tb->table); tb->table = nullptr; }
+    tb->table_rows = 0;
+    if (!tb->table) HIP64(hipMalloc((void **)&tb->table, (size_t)rows * tb->nx * sizeof(double)));
+    if (!tb->xref_start)
+    {
+        HIP64(hipMalloc((void **)&tb->xref_start, (size_t)tb->bpad * sizeof(int)));
+        HIP64(hipMemset(tb->xref_start, 0, (size_t)tb->bpad * sizeof(int)));
+    }
+    HIP64(hipMemcpy(tb->table, table, (size_t)rows * tb->nx * sizeof(double), hipMemcpyHostToDevice));
+    HIP64(hipMemcpy(tb->xref_start, start, (size_t)tb->batch * sizeof(int), hipMemcpyHostToDevice));
+    tb->table_rows = rows;
+    tb->xwin_valid = false;
+    return 0;
+}
+
+int tiny_batch64_get_xref_start(TinyBatch64 *tb, int *start)
+{
+    CHECK64(tb && start, "NULL argument");
+    CHECK64(tb->table_rows > 0, "no window reference is set (tiny_batch64_set_xref_window)");
+    HIP64(hipSetDevice(tb->device));
+    HIP64(hipMemcpy(start, tb->xref_start, (size_t)tb->batch * sizeof(int), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int tiny_batch64_mpc_run_traj(TinyBatch64 *tb, int steps, int window_advance, double *u0_traj_host)
+{
+    CHECK64(tb, "NULL handle");
+    CHECK64(steps >= 1, "steps must be >= 1 (got %d)", steps);
+    CHECK64(window_advance >= 0, "window_advance must be >= 0 (got %d)", window_advance);
+    const bool window = tb->table_rows > 0;
+    const int adv = window ? window_advance : 0; // without a window there is nothing to slide
+    CHECK64((long long)steps * adv + tb->table_rows + tb->N < 0x7fffffffLL, "steps * window_advance = %lld overflows the window start", (long long)steps * adv);
+    const bool onchip = onchip64(tb);
+    Params64 P;
+    {
+        const int rc = prepare64(tb, P, !onchip);
+        if (rc < 0) return rc;
+    }
+    const size_t row_len = (size_t)tb->batch * tb->nu, need = u0_traj_host ? (size_t)steps * row_len : 0;
+    if (need > tb->u0_traj_cap)
+    {
+        (void)hipFree(tb->u0_traj); tb->u0_traj = nullptr; tb->u0_traj_cap = 0;
+        HIP64(hipMalloc((void **)&tb->u0_traj, need * sizeof(double)));
+        tb->u0_traj_cap = need;
+    }
+    double *const traj = u0_traj_host ? tb->u0_traj : nullptr;
+    int *const start = window ? tb->xref_start : nullptr;
+    const int nb = (tb->batch + 127) / 128;
+#define TINY_F64_PLANT_RUN(NX, NU)                                                                                                            \
+    if (tb->nx == NX && tb->nu == NU)                                                                                                         \
+        hipLaunchKernelGGL((plant64_run_kernel<NX, NU>), dim3(nb), dim3(128), 0, 0, tb->arr[TINY_ARR_X], tb->arr[TINY_ARR_U], tb->mats, tb->batch, \
+                           tb->bpad, traj ? traj + (size_t)k * row_len : nullptr, start, adv);
+    if (onchip)
+    {
+        // all solves and the plant steps between them in one launch; the last plant step, u.col(0) of the last solve and the last slide follow
+        const Mpc64 L{steps, adv, tb->table_rows, tb->table, tb->xref_start, traj};
+        HIP64(hipMemsetAsync(tb->n_unsolved, 0, sizeof(int), 0));
+        // y and g of the workspace are zero from the first solve on: the kernel starts from that without reading them
+        const int rc = launch_solve64(tb, P, &L);
+        if (rc < 0) return rc;
+        const int k = steps - 1;
+        TINY_FOR_EACH_F64DIMS(TINY_F64_PLANT_RUN)
+        HIP64(hipGetLastError());
+    }
+    else
+    {
+        for (int k = 0; k < steps; k++)
+        {
+            if (window)
+            {
+                const int rc = gather_window64(tb);
+                if (rc < 0) return rc;
+            }
+            HIP64(hipMemsetAsync(tb->arr[TINY_ARR_Y], 0, (size_t)(tb->N - 1) * tb->nu * tb->bpad * sizeof(double), 0));
+            HIP64(hipMemsetAsync(tb->arr[TINY_ARR_G], 0, (size_t)tb->N * tb->nx * tb->bpad * sizeof(double), 0));
+            HIP64(hipMemsetAsync(tb->n_unsolved, 0, sizeof(int), 0));
+            const int rc = launch_solve64(tb, P);
+            if (rc < 0) return rc;
+            TINY_FOR_EACH_F64DIMS(TINY_F64_PLANT_RUN)
+            HIP64(hipGetLastError());
+            if (adv) tb->xwin_valid = false;
+        }
+    }
+    if (adv) tb->xwin_valid = false;
+    int n = 0;
+    HIP64(hipMemcpy(&n, tb->n_unsolved, sizeof(int), hipMemcpyDeviceToHost)); // the only host synchronisation of the run
+    if (u0_traj_host) HIP64(hipMemcpy(u0_traj_host, tb->u0_traj, need * sizeof(double), hipMemcpyDeviceToHost));
+    return n > 0 ? 1 : 0;
+}
+
+int tiny_batch64_mpc_run(TinyBatch64 *tb, int steps, int window_advance) { return tiny_batch64_mpc_run_traj(tb, steps, window_advance, nullptr); }
 
 int tiny_batch64_get_first_columns(TinyBatch64 *tb, double *x0, double *u0)
 {
@@ -1232,6 +1517,16 @@ const char *tiny_batch64_kernel_name(TinyBatch64 *tb)
     if (rows && !rows_unrolled(tb->nx, tb->nu, tb->N)) snprintf(nm, sizeof nm, "rows64<%d,%d,n<=%d>", tb->nx, tb->nu, tb->N <= 32 ? 32 : 64);
     else if (rows) snprintf(nm, sizeof nm, "rows64<%d,%d,%d>", tb->nx, tb->nu, tb->N);
     else snprintf(nm, sizeof nm, "thread64<%d,%d>", tb->nx, tb->nu);
+    return nm;
+}
+
+const char *tiny_batch64_closed_loop_kernel_name(TinyBatch64 *tb)
+{
+    static thread_local char nm[64];
+    if (!tb) return "";
+    const char *solve = tiny_batch64_kernel_name(tb);
+    if (!onchip64(tb)) return solve;
+    snprintf(nm, sizeof nm, "%.*s,mpc>", (int)strlen(solve) - 1, solve); // rows64<12,4,10> -> rows64<12,4,10,mpc>
     return nm;
 }
 

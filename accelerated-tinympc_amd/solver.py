@@ -106,6 +106,8 @@ def load_library(build_if_missing: bool = False) -> C.CDLL:
         "tiny_batch64_select_kernel": [P, C.c_int], "tiny_batch64_mpc_step": [P], "tiny_batch64_get_first_columns": [P, D, D],
         "tiny_batch64_forward_pass": [P], "tiny_batch64_update_slack": [P], "tiny_batch64_update_dual": [P],
         "tiny_batch64_update_linear_cost": [P], "tiny_batch64_backward_pass_grad": [P], "tiny_batch64_termination_condition": [P, I],
+        "tiny_batch64_set_xref_window": [P, D, C.c_int, I], "tiny_batch64_get_xref_start": [P, I],
+        "tiny_batch64_mpc_run": [P, C.c_int, C.c_int], "tiny_batch64_mpc_run_traj": [P, C.c_int, C.c_int, D],
     }
     for name, args in sig64.items():
         fn = getattr(lib, name)
@@ -113,6 +115,7 @@ def load_library(build_if_missing: bool = False) -> C.CDLL:
     lib.tiny_batch64_destroy.argtypes, lib.tiny_batch64_destroy.restype = [P], None
     lib.tiny_batch64_last_error.argtypes, lib.tiny_batch64_last_error.restype = [], C.c_char_p
     lib.tiny_batch64_kernel_name.argtypes, lib.tiny_batch64_kernel_name.restype = [P], C.c_char_p
+    lib.tiny_batch64_closed_loop_kernel_name.argtypes, lib.tiny_batch64_closed_loop_kernel_name.restype = [P], C.c_char_p
     lib.tiny_batch_debug_guards.argtypes, lib.tiny_batch_debug_guards.restype = [C.c_int], C.c_int
     lib.tiny_batch_debug_check.argtypes, lib.tiny_batch_debug_check.restype = [], C.c_longlong
     lib.tiny_batch_debug_poke.argtypes, lib.tiny_batch_debug_poke.restype = [P, C.c_int], C.c_int
@@ -632,6 +635,30 @@ class TinyBatchSolver64:
     def mpc_step(self) -> int:
         """y = g = 0, tiny_solve, x.col(0) <- Adyn x.col(0) + Bdyn u.col(0) (quadrotor_hovering.cpp:95-111), on the device."""
         return self._check(self.lib.tiny_batch64_mpc_step(self._h))
+
+    def set_xref_window(self, table, start):
+        """tiny_batch64_set_xref_window: one [rows][nx] trajectory table and a window start per instance, both kept on the device."""
+        t = np.ascontiguousarray(table, np.float64); assert t.ndim == 2 and t.shape[1] == self.nx, t.shape
+        st = np.ascontiguousarray(start, np.int32); assert st.shape == (self.B,), st.shape
+        self._check(self.lib.tiny_batch64_set_xref_window(self._h, self._dp(t), t.shape[0], st.ctypes.data_as(C.POINTER(C.c_int))))
+
+    def xref_start(self) -> np.ndarray:
+        """the window starts as they stand on the device (a run slides them)"""
+        st = np.zeros(self.B, np.int32)
+        self._check(self.lib.tiny_batch64_get_xref_start(self._h, st.ctypes.data_as(C.POINTER(C.c_int))))
+        return st
+
+    def mpc_run(self, steps: int, window_advance: int = 0) -> int:
+        """`steps` closed-loop MPC steps without the host in between (one launch where closed_loop_kernel_name() ends in ",mpc>")."""
+        return self._check(self.lib.tiny_batch64_mpc_run(self._h, int(steps), int(window_advance)))
+
+    def mpc_run_traj(self, steps: int, window_advance: int = 0) -> np.ndarray:
+        """mpc_run that also returns u.col(0) of every step, shape (steps, B, nu)."""
+        out = np.zeros((max(int(steps), 0), self.B, self.nu), np.float64)
+        self._check(self.lib.tiny_batch64_mpc_run_traj(self._h, int(steps), int(window_advance), self._dp(out)))
+        return out
+
+    def closed_loop_kernel_name(self) -> str: return self.lib.tiny_batch64_closed_loop_kernel_name(self._h).decode()
 
     def first_columns(self):
         """(x.col(0), u.col(0)) as [B][nx], [B][nu]."""

@@ -13,7 +13,8 @@
  * reference's SSE2 Eigen build with 2-double packets; results are BITWISE equal to the compiled reference (all twelve
  * work arrays, the residuals, status, iter).
  *
- * Scope: tiny_solve, the six step functions, a closed-loop step and the wrapper-style accessors.  Problem classes with a compiled
+ * Scope: tiny_solve, the six step functions, the examples' closed loop (one step, or a whole run in one launch with a sliding reference window) and the
+ * wrapper-style accessors.  Problem classes with a compiled
  * instantiation: (nx, nu) = (12, 4), (4, 1), (8, 4), (12, 2), (4, 2), (4, 4), (16, 4), any horizon N (TINY_FOR_EACH_F64DIMS).
  * Two kernels with identical results: sixteen lanes per instance with the state on chip for the whole solve (nx + nu <= 16 and N <= 64: unrolled instantiations for the
  * reference's horizons, a launch-parameter horizon otherwise; the default where it applies) and one thread per instance with the state in HBM (any N).
@@ -71,6 +72,26 @@ extern "C"
      * plant update: the next x0) and u.col(0) (the control just computed) without moving the whole horizon; either may be NULL. */
     int tiny_batch64_mpc_step(TinyBatch64 *tb);
     int tiny_batch64_get_first_columns(TinyBatch64 *tb, double *x0, double *u0);
+
+    /* The tracking example's reference (quadrotor_tracking.cpp:101-102: Xref = Xref_total.block(0, k, nx, N)) without an upload per step: one
+     * trajectory table for the batch and a window start per instance, both kept on the device.  Xref_b row i is
+     * table[min(start[b] + i, rows - 1)]; needs rows >= N, 0 <= start[b] and start[b] + N <= rows.  tiny_batch64_solve, the six step
+     * functions and tiny_batch64_mpc_step (which advances by 0) read the window; a later tiny_batch64_set_xref returns to an array.
+     * tiny_batch64_get_xref_start reads the starts back after a run has slid them. */
+    int tiny_batch64_set_xref_window(TinyBatch64 *tb, const double *table /*[rows][nx]*/, int rows, const int *start /*[B]*/);
+    int tiny_batch64_get_xref_start(TinyBatch64 *tb, int *start /*[B]*/);
+
+    /* `steps` closed-loop steps without the host in between: steps x {y = g = 0; tiny_solve; x.col(0) <- Adyn * x.col(0) + Bdyn * u.col(0);
+     * start[b] += window_advance}, results identical to `steps` single steps (and, with an array reference, to `steps` calls of
+     * tiny_batch64_mpc_step).  Where the sixteen-lane kernel holds the whole workspace on chip (its unrolled instantiations and horizons <= 32) all
+     * solves run in ONE launch and nothing but u.col(0) leaves the chip between two of them; elsewhere the same steps are enqueued as a launch
+     * sequence with one read-back at the end.  tiny_batch64_closed_loop_kernel_name says which: the on-chip instantiation carries an ",mpc"
+     * suffix ("rows64<12,4,10,mpc>", "rows64<12,2,n<=32,mpc>"), otherwise it is the solve kernel's name.  Returns what the LAST step's
+     * tiny_batch64_solve would return; steps < 1 or window_advance < 0 is TINY_BATCH_EINVAL; window_advance without a window is ignored.
+     * _traj also records u.col(0) of every step. */
+    int tiny_batch64_mpc_run(TinyBatch64 *tb, int steps, int window_advance);
+    int tiny_batch64_mpc_run_traj(TinyBatch64 *tb, int steps, int window_advance, double *u0_traj_host /*[steps][B][nu]*/);
+    const char *tiny_batch64_closed_loop_kernel_name(TinyBatch64 *tb);
 
     /* Implementation: 0 = automatic (the second where (nx, nu, N) has an instantiation, else the first), 1 = one thread per
      * instance with the state in HBM (any N), 2 = sixteen lanes per instance with the state in registers for the whole solve
