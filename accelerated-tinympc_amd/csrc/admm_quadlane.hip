@@ -151,6 +151,7 @@ __global__ __launch_bounds__(WAVE) void admm_quadlane_kernel(const RowParams P)
     SolveFrame F(P, inst, valid);
     float pN = 0.f;
     bool ran_bwd = false;
+    const bool ties = P.exact_ties != 0;
     for (int ms = 0;; ++ms) // MPC steps of the closed-loop variant; an ordinary solve runs the body once
     {
     bool active = valid && (P.max_iter > 0);
@@ -172,7 +173,7 @@ __global__ __launch_bounds__(WAVE) void admm_quadlane_kernel(const RowParams P)
                     lqr(s, dd[i], un, xn);
                     const float2 lu = bnd[i * 16 + NX];
                     const float t0 = un + ay[i];                                         // admm.cpp:47
-                    const float tz = __builtin_amdgcn_fmed3f(rnd<H16>(t0), lu.x, lu.y); // admm.cpp:51-54
+                    const float tz = box_project<EXACT>(rnd<H16>(t0), lu.x, lu.y, ties); // admm.cpp:51-54
                     ay[i] = rnd<HD>(t0 - tz);                                           // admm.cpp:69
                     pru = fmaxf(pru, fabsf(un - tz));                                    // admm.cpp:97
                     duu = fmaxf(duu, fabsf(bz[i] - tz));                                 // admm.cpp:98
@@ -180,7 +181,7 @@ __global__ __launch_bounds__(WAVE) void admm_quadlane_kernel(const RowParams P)
                 }
                 const float2 lx = bnd[i * 16 + j];
                 const float t0 = s + ax[i];                                              // admm.cpp:48
-                const float tx = __builtin_amdgcn_fmed3f(rnd<H16>(t0), lx.x, lx.y);     // admm.cpp:57-60
+                const float tx = box_project<EXACT>(rnd<H16>(t0), lx.x, lx.y, ties);     // admm.cpp:57-60
                 ax[i] = rnd<HD>(t0 - tx);                                               // admm.cpp:70
                 prx = fmaxf(prx, fabsf(s - tx));                                         // admm.cpp:95
                 dux = fmaxf(dux, fabsf(bx[i] - tx));                                     // admm.cpp:96

@@ -183,8 +183,8 @@ __device__ __forceinline__ void rowlane_body(const RowParams &P, const ModelPara
                 else sv = is_x ? s : 0.f;
                 float t = rnd<H16>(sv + a[i]);             // admm.cpp:47-48
                 // admm.cpp:51-60: min(hi, max(lo, t)).  The host stores lo := min(lo, hi), which makes the median
-                // identical to that expression for every t (and +-inf where a bound is disabled).
-                t = __builtin_amdgcn_fmed3f(t, lh.x, lh.y);
+                // identical to that expression for every t (and +-inf where a bound is disabled) — in value: see box_project.
+                t = box_project<EXACT>(t, lh.x, lh.y);
                 a[i] = rnd<HD>((a[i] + sv) - t);          // admm.cpp:69-70
                 pri = fmaxf(pri, fabsf(sv - t));           // admm.cpp:95,97
                 dua = fmaxf(dua, fabsf(b_pref - t));       // admm.cpp:96,98

@@ -94,6 +94,7 @@ __device__ __forceinline__ void rowloop_body(const RowParams &P)
     SolveFrame F(P, inst, valid);
     float pN = 0.f;
     bool ran_bwd = false;
+    const bool ties = P.exact_ties != 0;
 
     bool active = valid && (P.max_iter > 0);
     for (int it = 0; it < P.max_iter; ++it)
@@ -114,7 +115,7 @@ __device__ __forceinline__ void rowloop_body(const RowParams &P)
             auto elementwise = [&](auto hi, int k, int i, int inext, float sv) {
                 v32f &av = hi ? ahi : a;
                 const float t0 = sv + av[k];                                       // admm.cpp:47-48 and the sum of :69-70
-                const float t = __builtin_amdgcn_fmed3f(rnd<H16>(t0), lh.x, lh.y); // admm.cpp:51-60 (lo := min(lo, hi) on the host)
+                const float t = box_project<EXACT>(rnd<H16>(t0), lh.x, lh.y, ties); // admm.cpp:51-60 (lo := min(lo, hi) on the host)
                 const float an = rnd<H16>(t0 - t);                                 // admm.cpp:69-70  (a + sv) - t
                 av[k] = an;
                 pri = max_abs(pri, sv - t);                                        // admm.cpp:95,97

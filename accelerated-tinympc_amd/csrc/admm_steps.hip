@@ -61,7 +61,7 @@ __global__ __launch_bounds__(WAVE) void admm_step_kernel(const RowParams P, cons
         {
             const float2 lh = ld_bounds<H16>(P.bounds, inst * (int)P.bounds_inst_stride + i * 16 + r16);
             const float t = ldw<H16>(P.xu, rowbase + i * 16) + ldw<H16>(P.gy, rowbase + i * 16);
-            if (valid) stw<H16>(P.vzn, rowbase + i * 16, __builtin_amdgcn_fmed3f(t, lh.x, lh.y));
+            if (valid) stw<H16>(P.vzn, rowbase + i * 16, box_project<EXACT>(t, lh.x, lh.y));
         }
     }
     else if (fn == STEP_UPDATE_DUAL) // admm.cpp:67-71  y += u - znew, g += x - vnew
@@ -178,7 +178,7 @@ __global__ __launch_bounds__(WAVE) void admm_rowstream_kernel(const RowParams P)
                 const float2 lh = ld_bounds<H16>(P.bounds, inst * (int)P.bounds_inst_stride + i * 16 + r16);
                 const float a = zero_duals ? 0.f : ldw<H16>(P.gy, o);
                 const float bprev = zero_state ? 0.f : ldw<H16>(P.vz, o);
-                const float t = __builtin_amdgcn_fmed3f(rnd<H16>(sv + a), lh.x, lh.y);
+                const float t = box_project<EXACT>(rnd<H16>(sv + a), lh.x, lh.y);
                 const float an = rnd<H16>((a + sv) - t);
                 pri = fmaxf(pri, fabsf(sv - t));
                 dua = fmaxf(dua, fabsf(bprev - t));

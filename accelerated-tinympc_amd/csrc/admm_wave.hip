@@ -81,7 +81,7 @@ __global__ __launch_bounds__(WAVE, WPS) void admm_wavestream_kernel(const RowPar
                 float sv, xn = 0.f;
                 if (i < N - 1) wave_lqr_step<NX, NU>(G, vec, lane, is_x, is_u, s, di, sv, xn);
                 else sv = is_x ? s : 0.f;
-                const float t = __builtin_amdgcn_fmed3f(sv + a, lh.x, lh.y); // admm.cpp:47-60 (lo := min(lo, hi) on the host)
+                const float t = box_project<true>(sv + a, lh.x, lh.y);      // admm.cpp:47-60 (lo := min(lo, hi) on the host)
                 const float an = (a + sv) - t;                               // admm.cpp:69-70
                 pri = fmaxf(pri, fabsf(sv - t));
                 dua = fmaxf(dua, fabsf(bprev - t));

@@ -99,6 +99,7 @@ __global__ __launch_bounds__(WAVE, 2) void admm_waveres_kernel(const RowParams P
         else pterm = -lane_fma_dot<0, NX>(0.f, xrN, PT, vec, lane);
     }
     SolveFrame F(P, inst, true);
+    const bool ties = P.exact_ties != 0;
     float pN = 0.f;
     bool ran_bwd = false;
 
@@ -148,7 +149,7 @@ __global__ __launch_bounds__(WAVE, 2) void admm_waveres_kernel(const RowParams P
                 else sv = is_x ? s : 0.f;
                 // ... and the slack / dual update of the step runs while it is in flight
                 const float t0 = sv + ai;                                   // admm.cpp:47-48 and the sum of :69-70
-                const float t = __builtin_amdgcn_fmed3f(t0, lh.x, lh.y);    // admm.cpp:51-60 (lo := min(lo, hi) on the host)
+                const float t = box_project<EXACT>(t0, lh.x, lh.y, ties);   // admm.cpp:51-60 (lo := min(lo, hi) on the host)
                 const float an = t0 - t;                                    // admm.cpp:69-70  (a + sv) - t
                 b[i * WAVE] = t;
                 if (i < N - 1) // x_{i+1} = Adyn x_i + Bdyn u_i (admm.cpp:35)

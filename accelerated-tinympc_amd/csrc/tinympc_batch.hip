@@ -346,11 +346,20 @@ __global__ void systems_to_models_kernel(const double *__restrict__ rho, const d
     }
 }
 
+// A stored {lo, hi} on which v_med3_f32 and the reference's compare-selects can break a tie between zeros differently (tinympc_internal.h: box_project):
+// lo = -0 under hi > 0 (t = +0), or hi = +0 over lo < 0 or lo = -0 (t = -0), as the table holds them — folded, rounded to the storage format.  Every other
+// pair with a zero in it gives the same bits either way — the box [+0, +0] of bounds never set among them — and a disabled bound is +-inf
+__host__ __device__ inline bool zero_tie_bound(float lo, float hi)
+{
+    const bool lo_neg0 = lo == 0.f && __builtin_signbit(lo), hi_pos0 = hi == 0.f && !__builtin_signbit(hi);
+    return (lo_neg0 && hi > 0.f) || (hi_pos0 && (lo < 0.f || lo_neg0));
+}
+
 // per-instance bounds table of the ROW layout: dst[b][step][r] = {min(lo, hi), hi}, +-inf where a bound is disabled or the
 // row carries nothing.  Sources are the canonical inputs ([B or 1][steps][dim], NULL = not set = 0).
 __global__ void bounds_table_kernel(const float *__restrict__ xmin, const float *__restrict__ xmax, const float *__restrict__ umin,
                                     const float *__restrict__ umax, int sh_x, int sh_u, float *__restrict__ dst, Geo g, int nb,
-                                    int en_state, int en_input, int h16)
+                                    int en_state, int en_input, int h16, int *__restrict__ zero_ties)
 {
     const long long total = (long long)nb * g.N * g.rw;
     const float inf = __builtin_inff();
@@ -375,8 +384,10 @@ __global__ void bounds_table_kernel(const float *__restrict__ xmin, const float 
         {
             reinterpret_cast<_Float16 *>(dst)[2 * e] = (_Float16)lo;
             reinterpret_cast<_Float16 *>(dst)[2 * e + 1] = (_Float16)hi;
+            lo = (float)(_Float16)lo; hi = (float)(_Float16)hi;
         }
         else { dst[2 * e] = lo; dst[2 * e + 1] = hi; }
+        if (zero_tie_bound(lo, hi)) *zero_ties = 1; // (every writer stores the same word)
     }
 }
 
@@ -498,6 +509,8 @@ struct TinyBatch
     size_t r_bounds_img_n = 0, r_xref_img_n = 0;
     int *rows_vary_dev = nullptr;                         // [2] rows_vary_kernel's answer for the per-instance ROW tables ...
     unsigned rows_vary = 3u;                              // ... bit 0: bounds, bit 1: reference (set = changes along the horizon)
+    int *zero_ties_dev = nullptr;                         // bounds_table_kernel's answer for the per-instance ROW table ...
+    bool zero_ties = false;                               // ... and the handle's flag: the ROW bounds table holds an enabled pair with such a zero (zero_tie_bound)
     size_t r_xref_n = 0, r_bounds_n = 0, r_uref_n = 0;    // their allocated sizes in floats (sized_buffer)
     int graph_captures = 0;                               // closed-loop graphs captured so far (tiny_batch_debug_graph_captures)
     int n_cu = 256;                                       // compute units of the handle's device
@@ -955,23 +968,32 @@ int prepare_inputs(TinyBatch *tb, int layout)
     else
     {
         // bounds table [N][16]{lo,hi}: +-inf where a bound is disabled or the row carries nothing; lo := min(lo, hi)
-        // (min(hi, max(lo, t)) == med3(t, min(lo,hi), hi) for every t, also for the infeasible lo > hi case)
+        // (min(hi, max(lo, t)) == med3(t, min(lo,hi), hi) for every t, also for the infeasible lo > hi case — as VALUES: the median breaks a tie between
+        //  zeros of opposite sign the other way, which zero_ties records for the exact kernels; the reference's two compare-selects on the folded table
+        //  return the reference's bits, lo > hi and lo = -0 under hi = +0 included)
         const float inf = std::numeric_limits<float>::infinity();
         const int RW = tb->rw;
         if (!bounds_all_shared(tb)) // per-instance bounds: [bpad4][N][rw]{lo,hi}, built on the device from the canonical inputs
         {
             const size_t nf = (size_t)tb->bpad4 * N * RW * 2;
             TRY(sized_buffer(&tb->r_bounds, &tb->r_bounds_n, tb->h16 ? (nf + 1) / 2 : nf));
+            if (!tb->zero_ties_dev) TRY(dev_alloc_zero((float **)&tb->zero_ties_dev, 1));
+            HIP_TRY(hipMemsetAsync(tb->zero_ties_dev, 0, sizeof(int), tb->stream));
             const InputArr *in = tb->in_bnd;
             hipLaunchKernelGGL(bounds_table_kernel, dim3(grid_for((long long)tb->batch * N * RW)), dim3(256), 0, tb->stream,
                                in[0].set ? in[0].dev : nullptr, in[1].set ? in[1].dev : nullptr, in[2].set ? in[2].dev : nullptr,
                                in[3].set ? in[3].dev : nullptr, (in[0].set ? in[0].shared : in[1].shared) ? 1 : 0,
                                (in[2].set ? in[2].shared : in[3].shared) ? 1 : 0, tb->r_bounds, geo(tb), tb->batch, tb->en_state_bound,
-                               tb->en_input_bound, tb->h16 ? 1 : 0);
+                               tb->en_input_bound, tb->h16 ? 1 : 0, tb->zero_ties_dev);
             HIP_TRY(hipGetLastError());
+            int h = 0;
+            HIP_TRY(hipMemcpyAsync(&h, tb->zero_ties_dev, sizeof h, hipMemcpyDeviceToHost, tb->stream));
+            HIP_TRY(hipStreamSynchronize(tb->stream));
+            tb->zero_ties = h != 0;
         }
         else
         {
+        tb->zero_ties = false;
         std::vector<float> tab((size_t)N * RW * 2);
         for (int i = 0; i < N; i++)
             for (int r = 0; r < RW; r++)
@@ -987,8 +1009,10 @@ int prepare_inputs(TinyBatch *tb, int layout)
                     lo = tb->in_bnd[2].set ? tb->in_bnd[2].host[(size_t)i * nu + (r - nx)] : 0.f;
                     hi = tb->in_bnd[3].set ? tb->in_bnd[3].host[(size_t)i * nu + (r - nx)] : 0.f;
                 }
-                tab[((size_t)i * RW + r) * 2 + 0] = lo < hi ? lo : hi;
+                lo = lo < hi ? lo : hi;
+                tab[((size_t)i * RW + r) * 2 + 0] = lo;
                 tab[((size_t)i * RW + r) * 2 + 1] = hi;
+                if (tb->h16 ? zero_tie_bound((float)(_Float16)lo, (float)(_Float16)hi) : zero_tie_bound(lo, hi)) tb->zero_ties = true;
             }
         if (tb->h16) // same table in binary16 (bounds round to nearest; +-inf stays +-inf); half the floats
         {
@@ -1113,9 +1137,13 @@ Tile16Pi tile16_pi_plan(const TinyBatch *tb)
 // automatic choice with per-instance tables: the same rule as with shared ones (65 536 tracking instances, longest first, kernel ms, tile16 pi against the 16-lane
 // kernel: bounds constant along the horizon 1.75 / 2.13, reference per step 1.81 / 1.96, both per step 1.95 / 2.15; in index order the rings lose, 2.45 / 2.22)
 bool tile16_pi_auto(const TinyBatch *tb) { return !tb->order_dev && tile16_auto_size(tb); }
+// The two matrix-core kernels keep v_med3_f32 in both arithmetic modes (tile16 sits at a register cliff, tile48's short-horizon body at 256 registers:
+// tests/test_isa.py): in exact arithmetic a handle whose bounds table holds a zero on which the median breaks a tie the other way (TinyBatch::zero_ties)
+// is handed over to the next exact family — the 16-lane kernels, the state-on-chip wave kernel — like every combination an instantiation does not serve
+bool zero_ties_hand_over(const TinyBatch *tb) { return tb->zero_ties && tb->variant != VAR_ROW_FAST; }
 bool tile16_applies(const TinyBatch *tb, bool closed_loop)
 {
-    if (!tb->tile16_ok || tb->h16) return false;
+    if (!tb->tile16_ok || tb->h16 || zero_ties_hand_over(tb)) return false;
     if (tile16_per_instance(tb)) return !closed_loop && tile16_pi_plan(tb).fits;
     if (tb->xref_mode == 1) return tb->table_rows <= tile16_max_table_rows();
     return true;
@@ -1155,7 +1183,7 @@ Kernel row_kernel_for(const TinyBatch *tb, bool closed_loop)
     if (tb->wave_ok)
     {
         if (forced == Kernel::Wavestream) return Kernel::Wavestream;
-        if (tb->tile48_ok && !tb->h16 && (forced == Kernel::Tile48 || (!forced && tile48_pays(tb->batch, tb->n_cu)))) return Kernel::Tile48;
+        if (tb->tile48_ok && !tb->h16 && !zero_ties_hand_over(tb) && (forced == Kernel::Tile48 || (!forced && tile48_pays(tb->batch, tb->n_cu)))) return Kernel::Tile48;
         return tb->waveres_ok ? Kernel::Waveres : Kernel::Wavestream;
     }
     // per-instance bounds: the unrolled register-resident kernel (fp32 storage) and the rolled-loop ones (N <= 64, either storage)
@@ -1329,6 +1357,7 @@ void fill_row_params(TinyBatch *tb, RowParams &P, bool exact)
     P.mpc_steps = 1; P.window_advance = 0; P.u0_traj = nullptr; P.x0buf = tb->x0buf;
     P.dual32 = (tb->h16 && tb->dual32) ? 1 : 0;
     P.inst_map = nullptr; // enqueue_dispatch_order sets it for the one launch that reads it
+    P.exact_ties = tb->zero_ties ? 1 : 0;
 }
 
 int check_optional_terms(const TinyBatch *tb)
@@ -1730,7 +1759,7 @@ void tiny_batch_destroy(TinyBatch *tb)
     (void)guarded_free(tb->in_uref.dev); (void)guarded_free(tb->r_uref);
     (void)guarded_free(tb->key_buf); (void)guarded_free(tb->order_buf); (void)guarded_free(tb->u0_stage);
     for (int k = 0; k < 4; k++) { (void)guarded_free(tb->in_bnd[k].dev); (void)guarded_free(tb->t_bnd[k]); }
-    (void)guarded_free(tb->t_xref); (void)guarded_free(tb->r_xref); (void)guarded_free(tb->r_bounds); (void)guarded_free((float *)tb->rows_vary_dev);
+    (void)guarded_free(tb->t_xref); (void)guarded_free(tb->r_xref); (void)guarded_free(tb->r_bounds); (void)guarded_free((float *)tb->rows_vary_dev); (void)guarded_free((float *)tb->zero_ties_dev);
     (void)guarded_free(tb->r_bounds_img); (void)guarded_free(tb->r_xref_img);
     (void)guarded_free(tb->tab_tile); (void)guarded_free(tb->tab_row); (void)guarded_free(tb->tab_row_h); (void)guarded_free(tb->xref_start); (void)guarded_free(tb->tile_map);
     (void)guarded_free(tb->res); (void)guarded_free(tb->status); (void)guarded_free(tb->iter); (void)guarded_free(tb->n_unsolved);
@@ -2444,13 +2473,13 @@ int tiny_batch_mpc_run_traj_async(TinyBatch *tb, int steps, int window_advance, 
     // dispatch order are in it — so setters that only change buffer CONTENTS no longer drop the graph: `set_xref; mpc_run(k)`
     // in a loop replays one captured graph instead of re-capturing it every step)
     char sig[560];
-    snprintf(sig, sizeof sig, "%p|%p|%p|%d|%d|%d|%s|%d|%d|%g|%g|%d|%d|%p|%p|%p|%d|%p|%p|%p|%p|%d%d|%a|%d%d%d|%d%d|%d|%p|%p|%p", (void *)tb->pm_src, (void *)tb->pm_row[0],
+    snprintf(sig, sizeof sig, "%p|%p|%p|%d|%d|%d|%s|%d|%d|%g|%g|%d|%d|%p|%p|%p|%d|%p|%p|%p|%p|%d%d|%a|%d%d%d|%d%d|%d|%p|%p|%p|%d", (void *)tb->pm_src, (void *)tb->pm_row[0],
              (void *)tb->pm_row[1], steps, window_advance, tb->variant, kernel_name(tb, pl).c_str(), tb->max_iter,
              tb->check_termination, (double)tb->abs_pri_tol, (double)tb->abs_dua_tol, tb->xref_mode, tb->table_rows, (void *)tb->pair[0],
              (void *)tb->arr[0], (void *)tb->r_bounds, (int)tb->h16, (void *)tb->stream, (void *)d_u0_traj, (void *)tb->r_xref,
              (void *)tb->r_uref, (int)tb->en_uref, (int)tb->en_d2p, (double)tb->rho, (int)bounds_all_shared(tb),
              (int)(tb->in_xref.set && tb->in_xref.shared), (int)(tb->in_uref.set && tb->in_uref.shared), tb->en_state_bound, tb->en_input_bound,
-             tb->dispatch_mode, (void *)tb->order_dev, (void *)tb->mats_exact, (void *)tb->xref_start);
+             tb->dispatch_mode, (void *)tb->order_dev, (void *)tb->mats_exact, (void *)tb->xref_start, (int)tb->zero_ties);
     if (!tb->graph_exec || tb->graph_sig != sig)
     {
         if (tb->graph_exec) { (void)hipGraphExecDestroy(tb->graph_exec); tb->graph_exec = nullptr; }
@@ -2538,7 +2567,9 @@ const char *tiny_batch_kernel_name(TinyBatch *tb)
     if (!tb) return "";
     // per-instance tables of the class admm_tile16_pi.hip serves: whether they change along the horizon (one resident row per instance, or rings)
     // is found when the derived tables are built, and the automatic choice depends on it — build them now, as the next solve would
-    if (tb->tile16_ok && !tb->h16 && tb->derived_dirty[LAYOUT_ROW] && tile16_per_instance(tb))
+    // ... and so is whether the bounds table holds a zero that hands an exact solve over from the matrix-core kernels (zero_ties_hand_over)
+    if (!tb->h16 && tb->derived_dirty[LAYOUT_ROW] &&
+        ((tb->tile16_ok && tile16_per_instance(tb)) || ((tb->tile16_ok || tb->tile48_ok) && (tb->variant == VAR_AUTO || tb->variant == VAR_ROW_EXACT))))
     {
         const std::string keep = g_err;
         KernelPlan pl;

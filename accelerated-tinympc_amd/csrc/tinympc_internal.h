@@ -118,7 +118,29 @@ struct RowParams
     const int *inst_map;         // NULL = identity, or [16 ceil(batch/16)]: column c of tile t serves instance inst_map[16 t + c]; an entry outside
                                  // [0, batch) is a padding column (dispatch_order.hip: instances grouped by window start).  Read by the cold-start
                                  // shared-table instantiations of admm_tile16.hip and by the tile key kernel only; NULL for every other launch
+    int exact_ties;              // the bounds table holds lo = -0 under hi > 0 or hi = +0 over lo <= -0 (prepare_inputs): the rolled-loop, quad and state-on-chip wave kernels
+                                 // then project by box_project's compare-selects instead of v_med3_f32 in exact arithmetic.  Appended: no other argument moves
 };
+
+// The box projection of the slack update, u_max.cwiseMin(u_min.cwiseMax(t)) (admm.cpp:51-60), on a {lo, hi} whose lo the host folded to min(lo, hi).
+// v_med3_f32 returns the VALUE of the reference's two compare-selects for every t, but it orders -0 below +0 where they compare the two equal and
+// keep the bound: for t = +0 on lo = -0 it returns +0 (reference -0), for t = -0 on hi = +0 it returns -0 (reference +0).  Exact arithmetic therefore
+// takes the compare-selects wherever such a bound can occur: always in the kernels that stream their state (the projection is nothing beside their
+// memory traffic) and in the unrolled 16-lane kernel (a branch per step cuts its sweep, one basic block, into 2 N and moved the pinned scratch
+// of a per-instance-model instantiation; three more VALU instructions per step do not), under the wave-uniform `ties` (RowParams::exact_ties) in
+// the rolled-loop, quad and state-on-chip wave kernels, whose median stays the straight path.  Fma arithmetic keeps the median, and so do the two
+// matrix-core kernels in both modes: an exact handle with such a bound never reaches them (tinympc_batch.hip: zero_ties_hand_over).
+template <bool EXACT>
+__device__ __forceinline__ float box_project(float t, float lo, float hi, bool ties = true)
+{
+    if constexpr (EXACT)
+        if (__builtin_expect(ties, false)) // the median stays the straight path
+        {
+            t = lo < t ? t : lo;
+            return t < hi ? t : hi;
+        }
+    return __builtin_amdgcn_fmed3f(t, lo, hi);
+}
 
 // Per-instance models (tiny_batch_set_models): a kernel argument of its own beside RowParams / SolveParams, whose layouts stay as they are.
 //   mats: [batch][mats_stride] — the rowlane kernel: pack_gains' rows 0 .. 3nx + 2nu (M1, M2, M3, M45, Q, PT; no optional-term rows) of

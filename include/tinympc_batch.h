@@ -237,7 +237,13 @@ extern "C"
      * falls back to the auto choice among the 16-lane kernels).  For 16 < nx + nu <= 64 (one wavefront per instance): 6 = wavestream (state in HBM, any
      * N), 7 = waveres (state in registers/LDS, N <= 50; the auto choice up to 2 048 and for 4 097 ... 6 144 instances), 8 = tile48 (nx = 32, nu = 16,
      * N <= 50, fp32 storage: sixteen instances per workgroup as the columns of 16x16 MFMA tiles, duals in LDS;
-     * the auto choice for 2 049 ... 4 096 and from 6 145 instances on (rounds of the launch)).  All of them compute identical results. */
+     * the auto choice for 2 049 ... 4 096 and from 6 145 instances on (rounds of the launch)).  All of them compute identical results.
+     * Zero bounds: the two matrix-core kernels (5, 8) project with v_med3_f32, which breaks a tie between zeros of opposite sign the other way than the
+     * reference's u_max.cwiseMin(u_min.cwiseMax(t)) does (t = +0 on a lower bound of -0, t = -0 on an upper bound of +0).  In exact arithmetic a handle
+     * whose stored bounds hold such a pair — a lower bound of -0 under a positive upper bound, an upper bound of +0 over a lower bound that is negative
+     * or -0; enabled, after min(lo, hi) and the rounding to the storage format — is
+     * therefore handed over, forced or automatic: 5 to the 16-lane kernels, 8 to waveres — tiny_batch_kernel_name() says so ("rowlane<12,4,30,exact>").
+     * Every other exact kernel projects by the reference's two compare-selects where such a bound can occur; fma arithmetic keeps the median. */
     int tiny_batch_set_row_kernel(TinyBatch *tb, int family);
     /* Storage precision of the per-instance horizon arrays (the twelve work arrays, Xref, bounds) in HBM:
      * 32 = fp32 like the reference (default); 16 = IEEE binary16 storage with fp32 arithmetic (BASELINE.json

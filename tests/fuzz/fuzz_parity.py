@@ -3,7 +3,7 @@
     python tests/fuzz/fuzz_parity.py [seconds] [seed]
 
 Every round draws a problem class with an exact kernel, a batch size, settings (iteration limits, termination stride,
-tolerances, bound switches), bounds (per step, some infeasible or infinite), a reference (shared / per instance / sliding
+tolerances, bound switches), bounds (per step, some infeasible, infinite, zero of either sign or pinned), a reference (shared / per instance / sliding
 window), a random warm workspace (with zeros and negative zeros) and a row-kernel family, runs a chain of solves and
 requires all twelve work arrays, the residuals, status and iter to equal the oracle's bit for bit.  One round in six also
 switches on the two terms the reference ships commented out (admm.cpp:20 coeff_d2p, :79 Uref), one in five runs under a
@@ -69,6 +69,13 @@ while time.time() < t_end:
         bnds = tuple((a[None] * rng.uniform(0.3, 1.0, size=(B,) + a.shape)).astype(np.float32) for a in bnds)
         if rng.random() < 0.4:   # ... that do not change along the horizon (admm_tile16_pi.hip keeps one resident row per instance then)
             bnds = tuple(np.repeat(a[:, :1], a.shape[1], axis=1).copy() for a in bnds)
+    if rng.random() < 0.2:   # the edges of the projection: bounds of +0 and -0 (a tie between zeros of opposite sign is broken by the bound) and lo == hi
+        for lo_, hi_ in ((bnds[0], bnds[1]), (bnds[2], bnds[3])):
+            for a in (lo_, hi_):
+                a[rng.random(a.shape) < 0.04] = 0.0
+                a[rng.random(a.shape) < 0.04] = -0.0
+            pin = rng.random(lo_.shape) < 0.04
+            lo_[pin] = hi_[pin]
     bnds_raw = bnds
     sol = T.TinyBatchSolver(prob, B, settings=settings)
     h16 = not wave and rng.random() < 0.3   # fp16 storage / fp32 arithmetic against the oracle's _h16 restatement

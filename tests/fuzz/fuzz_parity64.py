@@ -4,7 +4,7 @@ instantiation (test infrastructure; run on an MI355X):
     python tests/fuzz/fuzz_parity64.py [seconds] [seed]
 
 Every round draws one of the three instantiated classes with a random horizon and batch size, settings, bounds (shared or
-per instance, some infeasible or infinite), a reference (shared or per instance), a cold or random warm workspace (with
+per instance, some infeasible, infinite, zero of either sign or pinned), a reference (shared or per instance), a cold or random warm workspace (with
 zeros and negative zeros), runs a chain of solves and requires all twelve work arrays, the residuals, status and iter to
 equal the oracle's bit for bit."""
 import sys
@@ -43,6 +43,13 @@ while time.time() < t_end:
     bnds = (xmn, xmx, umn, umx)
     if rng.random() < 0.3:
         bnds = tuple(a[None] * rng.uniform(0.3, 1.0, size=(B,) + a.shape) for a in bnds)
+    if rng.random() < 0.2:   # the edges of the projection: bounds of +0 and -0 (a tie between zeros of opposite sign is broken by the bound) and lo == hi
+        for lo_, hi_ in ((bnds[0], bnds[1]), (bnds[2], bnds[3])):
+            for a in (lo_, hi_):
+                a[rng.random(a.shape) < 0.04] = 0.0
+                a[rng.random(a.shape) < 0.04] = -0.0
+            pin = rng.random(lo_.shape) < 0.04
+            lo_[pin] = hi_[pin]
     sol = T.TinyBatchSolver64(prob, B, settings=settings)
     if rng.random() < 0.4:
         sol.select_kernel(1)   # one thread per instance; otherwise automatic (sixteen lanes per instance where instantiated)

@@ -197,3 +197,175 @@ def closed_loop_case(pr, O, z, name):
         xr = z["dims837_xref"].astype(np.float32)
         fn = lambda k: xr
     return prob, z[f"{name}_x0"], fn, meta["steps"], meta["settings"], table, start
+
+
+# ---- the box projection at its edges, shared by tests/test_projection_host.py and tests/test_projection_gpu.py -----------------------------------------
+
+PROJ_CATS = ("slack", "bind_lo", "bind_hi", "tie_lo", "tie_hi", "pinned", "zlo_pos", "zlo_neg", "zhi_pos", "zhi_neg", "infeasible", "inf_lo", "inf_hi")
+PROJ_ZERO_CATS = tuple(PROJ_CATS.index(c) for c in ("zlo_pos", "zlo_neg", "zhi_pos", "zhi_neg"))
+PROJ_EXACT = dict(abs_pri_tol=0.0, abs_dua_tol=0.0, check_termination=1)
+
+
+def _beside(t, up, h16):
+    """the neighbour of t on the storage grid, above (up) or below; around zero the smallest step that stays clear of fp32 / fp64 subnormals (binary16
+    keeps its subnormals in storage, so there the plain neighbour)"""
+    if h16:
+        return np.nextafter(t.astype(np.float16), np.float16(np.inf if up else -np.inf)).astype(np.float32)
+    tiny = t.dtype.type(2.0 ** -60)
+    n = np.nextafter(t, t.dtype.type(np.inf if up else -np.inf))
+    return np.where(np.abs(t) < tiny, tiny if up else -tiny, n).astype(t.dtype)
+
+
+def _bounds_of_category(cat, t, lo0, hi0, h16):
+    """(lo, hi) of every entry from its category, the pre-projection value t it is crafted around and the class's stock box [lo0, hi0]"""
+    C = {c: cat == k for k, c in enumerate(PROJ_CATS)}
+    dt = t.dtype
+    lo, hi = np.full(t.shape, lo0, dt), np.full(t.shape, hi0, dt)
+    far = np.abs(t) + dt.type(1.0)
+    lo = np.where(C["bind_lo"], _beside(t, True, h16), lo);   hi = np.where(C["bind_lo"], np.maximum(hi, far), hi)
+    hi = np.where(C["bind_hi"], _beside(t, False, h16), hi);  lo = np.where(C["bind_hi"], np.minimum(lo, -far), lo)
+    lo = np.where(C["tie_lo"] | C["pinned"], t, lo);          hi = np.where(C["tie_lo"], np.maximum(hi, far), hi)
+    hi = np.where(C["tie_hi"] | C["pinned"], t, hi);          lo = np.where(C["tie_hi"], np.minimum(lo, -far), lo)
+    lo = np.where(C["zlo_pos"], dt.type(0.0), lo);            lo = np.where(C["zlo_neg"], dt.type(-0.0), lo)
+    hi = np.where(C["zhi_pos"], dt.type(0.0), hi);            hi = np.where(C["zhi_neg"], dt.type(-0.0), hi)
+    lo = np.where(C["infeasible"], dt.type(0.3) * abs(hi0), lo); hi = np.where(C["infeasible"], -dt.type(0.2) * abs(lo0), hi)
+    lo = np.where(C["inf_lo"], -np.inf, lo);                  hi = np.where(C["inf_hi"], np.inf, hi)
+    return lo.astype(dt), hi.astype(dt)
+
+
+def projection_case(O, prob, B, dtype, seed, per_instance):
+    """Inputs that put the slack update (admm.cpp:51-60) of ITERATION 1 on the edges of its box: see PROJ_CATS.  dtype: np.float32, np.float64 or
+    "h16" / "h16d" (float32 arrays on the binary16 grid, for the fp16-storage kernels).
+
+    The first Z = B // 2 instances are all zeros of random sign (work arrays and Xref; instance 0 all -0, instance 1 all +0, x.col(0) of instances 2 and 3 likewise, and g.col(0) carries the
+    sign of x.col(0), so that x + g is -0 wherever x.col(0) is); the rest a random warm state.  t = (x + g, u + y) of iteration 1 comes from the oracle with
+    both bounds disabled — it does not depend on the bounds.  Categories follow a cyclic pattern with drawn strides over (instance, step, row): thirteen
+    is prime, so every line of thirteen entries along a step, a row or the instances holds every category, the first and last step and row included.
+    Then the four zero bounds are laid over the entries where some zero instance has t = -0 (per-instance tables: in that instance's own table, and over
+    as many of its t = +0 entries; shared tables: over the entries where the zero instances are most evenly split between -0 and +0).
+    per_instance = "const": per-instance tables that do not change along the horizon, crafted around step 0.
+    A shared table without a line of thirteen ("dense") takes the nine other categories by turns over its entries instead, the first and last step and
+    row first; with fewer than twenty-six entries its four zero bounds have their other side infinite.
+    Ties use the instance's own t (per-instance tables) or, for a shared table, the t of a zero instance and of a warm instance by turns.
+    Returns dict(st0, xref, bnds = (x_min, x_max, u_min, u_max), t = (tx, tu), cat = (cat_x, cat_u), laid = (laid_x, laid_u), dense = (.., ..), Z)."""
+    nx, nu, N = prob["nx"], prob["nu"], prob["N"]
+    h16 = isinstance(dtype, str)
+    dt = np.dtype(np.float32 if h16 else dtype)
+    R = O.round_h16 if h16 else (lambda a: a)
+    rng = np.random.default_rng(seed)
+    Z = B // 2
+    assert Z >= 4
+    st0 = O.new_state(B, nx, nu, N, dt)
+    for k in STATE_ORDER:
+        st0[k][:] = R((rng.standard_normal(st0[k].shape) * 0.3).astype(dt))
+    for k in ("x", "d", "v", "z", "g", "y"):
+        st0[k][rng.random(st0[k].shape) < 0.1] = 0.0
+        st0[k][rng.random(st0[k].shape) < 0.1] = -0.0
+    xref = R((rng.standard_normal((B, N, nx)) * 0.2).astype(dt))
+    for k in STATE_ORDER:
+        st0[k][:Z] = np.copysign(0.0, rng.standard_normal(st0[k][:Z].shape))
+        st0[k][0], st0[k][1] = -0.0, 0.0
+    st0["x"][2, 0], st0["x"][3, 0] = -0.0, 0.0     # with instances 0 and 1: every state row has x.col(0) = -0 twice and +0 twice
+    st0["g"][:Z, 0] = st0["x"][:Z, 0]
+    xref[:Z] = np.copysign(0.0, rng.standard_normal(xref[:Z].shape))
+    xref[0], xref[1] = -0.0, 0.0
+
+    free = O.copy_state(st0)
+    stock = tuple(np.asarray(b, dt) for b in bounds_of(prob, dt))
+    O.Oracle(prob, dtype, dict(PROJ_EXACT, max_iter=1, en_state_bound=0, en_input_bound=0)).solve(free, *stock, xref)
+    t = (free["vnew"].copy(), free["znew"].copy())
+    assert all(np.all(a[:Z] == 0) for a in t), "a zero instance whose pre-projection values are not zeros"
+
+    strides = rng.integers(1, len(PROJ_CATS), size=3)
+    off = rng.integers(0, len(PROJ_CATS), size=2)
+    bnds, cats, laids, denses = [], [], [], []
+    for a, (tt, lo0, hi0) in enumerate(((t[0], prob["x_min"], prob["x_max"]), (t[1], prob["u_min"], prob["u_max"]))):
+        _, S, n = tt.shape
+        bi, si, ri = np.meshgrid(np.arange(B if per_instance else 1), np.arange(S), np.arange(n), indexing="ij")
+        cat = ((bi * strides[0] + si * strides[1] + ri * strides[2] + off[a]) % len(PROJ_CATS)).astype(np.int32)
+        laid, open_side, dense = np.zeros(cat.shape, bool), np.zeros(cat.shape, bool), False
+        neg = np.signbit(tt[:Z])
+        if per_instance:
+            src = tt
+            for b in range(Z):
+                for sel in (neg[b], ~neg[b]):
+                    idx = np.argwhere(sel)[:int(neg[b].sum())]
+                    for j, (i, r) in enumerate(idx):
+                        cat[b, i, r], laid[b, i, r] = PROJ_ZERO_CATS[(j + b) % 4], True
+        else:
+            dense = max(S, n) < len(PROJ_CATS)                               # no line of thirteen: the pattern need not reach every category
+            small = S * n < 2 * len(PROJ_CATS)                               # ... and not even room for all of them beside the zero bounds
+            split = np.minimum(neg.sum(axis=0), (~neg).sum(axis=0))          # how evenly an entry splits the zero instances
+            order = np.argsort(-split.ravel(), kind="stable")
+            left = 4 if dense and small else 8
+            for e in order[split.ravel()[order] >= 2]:
+                i, r = divmod(int(e), n)
+                if left and (dense or (cat == cat[0, i, r]).sum() > 1):      # never over the only entry of its category
+                    left -= 1
+                    cat[0, i, r], laid[0, i, r] = PROJ_ZERO_CATS[left % 4], True
+            # the source instance of every entry's ties: a zero instance and a warm one by turns
+            turn = (si[0] + ri[0]) % 2 == 0
+            if dense:   # the other nine categories by turns over the entries left: first step, last step, first row, last row, then the rest, each in a
+                        # drawn order; in a small table the zero bounds have their other side infinite
+                rank = np.select([si[0] == 0, si[0] == S - 1, ri[0] == 0, ri[0] == n - 1], [0, 1, 2, 3], 4).ravel() + rng.random(S * n)
+                rest = [e for e in np.argsort(rank) if not laid.ravel()[e]]
+                other = [k for k in range(len(PROJ_CATS)) if k not in PROJ_ZERO_CATS]
+                cat.ravel()[rest] = [other[(j + off[a]) % len(other)] for j in range(len(rest))]
+                open_side = laid & small
+                turn = cat[0] == PROJ_CATS.index("pinned")                    # one tie of each side away from zero, the pinned entry on a zero
+            inst = np.where(turn, (si[0] * n + ri[0]) % Z, Z + (si[0] * n + ri[0]) % (B - Z))
+            src = np.take_along_axis(tt, inst[None], axis=0)
+        if per_instance == "const":   # one row of bounds per instance, crafted around step 0 (where t can be -0) and held along the horizon
+            cat, laid = np.repeat(cat[:, :1], S, axis=1), np.repeat(laid[:, :1], S, axis=1)
+            src = np.repeat(src[:, :1], S, axis=1)
+        lo, hi = _bounds_of_category(cat, src, dt.type(lo0), dt.type(hi0), h16)
+        zlo = (cat == PROJ_ZERO_CATS[0]) | (cat == PROJ_ZERO_CATS[1])
+        lo, hi = np.where(open_side & ~zlo, -np.inf, lo).astype(dt), np.where(open_side & zlo, np.inf, hi).astype(dt)
+        if not per_instance:
+            lo, hi = lo[0], hi[0]
+        bnds += [R(lo), R(hi)]; cats.append(cat); laids.append(laid); denses.append(dense)
+    return dict(st0=st0, xref=xref, bnds=tuple(bnds), t=t, cat=tuple(cats), laid=tuple(laids), dense=tuple(denses), Z=Z)
+
+
+def med3_model(t, lo, hi):
+    """v_med3_f32 as the ISA manual states it, on (t, min(lo, hi), hi) — how the kernels call it: the median through max / min that order -0 below +0
+    (NaNs are out of scope).  med3(a, b, c) = max(min(a, b), min(max(a, b), c))."""
+    key = lambda v: np.where(v == 0, np.where(np.signbit(v), -1, 1) * np.finfo(v.dtype).tiny / 2, v)   # orders -0 < +0, changes no other comparison
+    mx = lambda a, b: np.where(key(a) >= key(b), a, b)
+    mn = lambda a, b: np.where(key(a) <= key(b), a, b)
+    lo = np.where(lo < hi, lo, hi)
+    return mx(mn(t, lo), mn(mx(t, lo), hi))
+
+
+def compare_select(t, lo, hi):
+    """the reference's projection, admm.cpp:51-60 (u_max.cwiseMin(u_min.cwiseMax(t))): (lo < t) ? t : lo, then (t < hi) ? t : hi"""
+    t = np.where(lo < t, t, lo)
+    return np.where(t < hi, t, hi)
+
+
+def projection_problem(pr, O, nx, nu, N):
+    """the model of a class, as tests/test_oracle.py builds it for the compiled reference of that class"""
+    if (nx, nu) == (12, 4):
+        return pr.quadrotor(20, N)
+    if (nx, nu) == (4, 1):
+        return pr.cartpole(N, riccati=O.riccati)
+    return pr.random_system(nx, nu, N, seed=nx * 100 + nu, riccati=O.riccati)
+
+
+# every input set of tests/test_projection_gpu.py: (nx, nu, N, B, dtype, per_instance); the seed is the position in this list
+PROJ_INPUTS = [(12, 4, 10, 21, np.float32, False), (12, 4, 10, 21, np.float32, True), (12, 4, 10, 21, np.float32, "const"), (8, 3, 7, 22, np.float32, False),
+               (4, 2, 8, 20, np.float32, False), (4, 2, 8, 20, np.float32, True), (8, 4, 9, 20, np.float32, False), (8, 4, 9, 20, np.float32, True),
+               (4, 1, 10, 28, np.float32, False), (16, 4, 10, 20, np.float32, False), (16, 4, 10, 20, np.float32, True),
+               (32, 16, 6, 19, np.float32, False), (32, 16, 6, 19, np.float32, True), (3, 2, 6, 20, np.float32, True), (8, 8, 6, 20, np.float32, False),
+               (12, 4, 10, 20, np.float64, False), (12, 4, 10, 20, np.float64, True), (4, 2, 8, 20, np.float64, False), (4, 2, 8, 20, np.float64, True),
+               (12, 4, 10, 20, "h16", False), (12, 4, 10, 20, "h16d", False)]
+_proj_cache = {}
+
+
+def projection_input(pr, O, key):
+    """(prob, case) of one entry of PROJ_INPUTS, built once and shared: callers copy what they change"""
+    if key not in _proj_cache:
+        nx, nu, N, B, dtype, mode = key
+        prob = projection_problem(pr, O, nx, nu, N)
+        _proj_cache[key] = (prob, projection_case(O, prob, B, dtype, PROJ_INPUTS.index(key), mode))
+    return _proj_cache[key]
