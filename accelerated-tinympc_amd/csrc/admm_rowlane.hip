@@ -46,9 +46,13 @@ constexpr int OPT_AHEAD = 4;
 // The body of both kernels below.  PM = true (per-instance models, tiny_batch_set_models): the gain rows and rho of a row come from
 // that instance's record, mats = M.mats + inst * M.mats_stride and M.rho[inst], instead of the one table the batch shares; the
 // plant step of the on-chip loop then uses the instance's own Adyn / Bdyn (the M1 / M2 rows) with no further change.
-template <int NX, int NU, int N, bool EXACT, bool H16, bool MPC, bool BPI, bool D32, bool OPT, bool PM>
-__device__ __forceinline__ void rowlane_body(const RowParams &P, const ModelParams &M)
+// SIM = true (with MPC; admm_rowsim.hip): the plant step between two solves of the on-chip loop uses the plant's own rows S.plant (one table or one per
+// instance; NULL: the model's), adds the disturbance row S.w and records the state in S.x_traj (tinympc_internal.h: SimParams).  The rows are loaded
+// once per MPC step into transient registers (L2 resident): nothing is held across the iteration loop.
+template <int NX, int NU, int N, bool EXACT, bool H16, bool MPC, bool BPI, bool D32, bool OPT, bool PM, bool SIM = false>
+__device__ __forceinline__ void rowlane_body(const RowParams &P, const ModelParams &M, [[maybe_unused]] const SimParams &S = SimParams{})
 {
+    static_assert(!SIM || (MPC && !H16 && !BPI && !D32 && !OPT), "the simulated loop is instantiated where the on-chip loop is: fp32 storage, shared bounds");
     static_assert(!OPT || (!H16 && !MPC && !BPI && !D32), "the optional terms are instantiated for fp32 storage, shared bounds, one solve per launch");
     static_assert(!PM || (!H16 && !D32 && !OPT), "per-instance models are instantiated for fp32 storage without the optional terms");
     constexpr bool HD = H16 && !D32; // storage precision of the duals (gy)
@@ -250,7 +254,32 @@ __device__ __forceinline__ void rowlane_body(const RowParams &P, const ModelPara
         float sv0, x1;
         lqr(x0, c[0], sv0, x1); // [x_0 ; u_0] of the solve that just finished, in the solver's own arithmetic
         if (P.u0_traj && valid && is_u) P.u0_traj[((long long)ms * P.batch + inst) * NU + (r16 - NX)] = sv0;
-        if constexpr (MPC) x0 = plant_step<NX, NU>(G, sv0); // x_1 = Adyn x0 + Bdyn u_0 (:110), the plant kernel's arithmetic
+        if constexpr (SIM)
+        {
+            // x_1 = (A_p x0 + B_p u_0) + w: the same DPP groups and sums with the plant's rows, then one separately rounded add.
+            // The lane offsets are remade here from `inst` (opaque to the compiler, which otherwise hoists three 64-bit lane addresses out of the MPC
+            // loop and carries them through every iteration loop) and go with scalar bases: batch * plant_row_floats and batch * NX stay below 2^31
+            // under the host's batch * N * 16 < 2^30
+            int ia = inst;
+            asm volatile("" : "+v"(ia));
+            ia = valid ? ia : P.batch - 1;
+            if (S.plant)
+            {
+                const float *pl = S.plant + (unsigned)(ia * (int)S.plant_stride + r16);
+                float Ar[NX], Br[NU];
+#pragma unroll
+                for (int k = 0; k < NX; k++) Ar[k] = pl[k * 16];
+#pragma unroll
+                for (int k = 0; k < NU; k++) Br[k] = pl[(NX + k) * 16];
+                x0 = plant_step<NX, NU>(Ar, Br, sv0);
+            }
+            else x0 = plant_step<NX, NU>(G, sv0);
+            const size_t row = (size_t)ms * P.batch * NX;                 // scalar: row ms of [steps][batch][nx]
+            const unsigned xo = (unsigned)(ia * NX + (is_x ? r16 : 0));
+            if (S.w && is_x) x0 = x0 + (S.w + row)[xo];
+            if (S.x_traj && valid && is_x) (S.x_traj + row)[xo] = x0;
+        }
+        else if constexpr (MPC) x0 = plant_step<NX, NU>(G, sv0); // x_1 = Adyn x0 + Bdyn u_0 (:110), the plant kernel's arithmetic
         xref.advance(P);
         const float qrow = mats[(2 * NX + 2 * NU) * 16 + r16];
 #pragma unroll
@@ -325,6 +354,41 @@ __global__ __launch_bounds__(WAVE, (N > 32 && EXACT) ? 1 : 2) void admm_rowlane_
     rowlane_body<NX, NU, N, EXACT, false, MPC, BPI, false, false, true>(P, M);
 }
 
+#ifdef TINY_ROWSIM_UNIT
+// The simulated closed loop: the SIM instantiations of the body and their launcher, compiled as admm_rowsim.hip (a translation unit of its own, so that
+// the kernels above keep their code).  fp32 storage and shared bounds, exactly where MPC is instantiated.
+template <int NX, int NU, int N, bool EXACT>
+__global__ __launch_bounds__(WAVE, (N > 32 && EXACT) ? 1 : 2) void admm_rowsim_kernel(const RowParams P, const SimParams S)
+{
+    rowlane_body<NX, NU, N, EXACT, false, true, false, false, false, false, true>(P, ModelParams{}, S);
+}
+template <int NX, int NU, int N, bool EXACT>
+__global__ __launch_bounds__(WAVE, (N > 32 && EXACT) ? 1 : 2) void admm_rowsim_pm_kernel(const RowParams P, const ModelParams M, const SimParams S)
+{
+    rowlane_body<NX, NU, N, EXACT, false, true, false, false, false, true, true>(P, M, S);
+}
+
+hipError_t launch_admm_rowsim(int nx, int nu, int N, bool exact, const RowParams &P, const ModelParams *M, const SimParams &S, hipStream_t stream)
+{
+    const int nblocks = (P.batch + 3) / 4;
+    if (P.mpc_steps <= 1 || P.bounds_inst_stride != 0 || P.dual32 || P.uref != nullptr || P.en_d2p || (M && (!M->mats || !M->rho))) return hipErrorInvalidValue;
+#define TINY_ROWSIM_LAUNCH(NX, NU, NN, EX)                                                                                               \
+    do                                                                                                                                   \
+    {                                                                                                                                    \
+        if (M) hipLaunchKernelGGL((admm_rowsim_pm_kernel<NX, NU, NN, EX>), dim3(nblocks), dim3(WAVE), 0, stream, P, *M, S);              \
+        else hipLaunchKernelGGL((admm_rowsim_kernel<NX, NU, NN, EX>), dim3(nblocks), dim3(WAVE), 0, stream, P, S);                       \
+    } while (0)
+#define TINY_ROWSIM_DISPATCH(NX, NU, NN)            \
+    if (nx == NX && nu == NU && N == NN)            \
+    {                                               \
+        if (exact) TINY_ROWSIM_LAUNCH(NX, NU, NN, true); \
+        else TINY_ROWSIM_LAUNCH(NX, NU, NN, false); \
+        return hipGetLastError();                   \
+    }
+    TINY_FOR_EACH_ROWLANE(TINY_ROWSIM_DISPATCH)
+    return hipErrorInvalidValue;
+}
+#else
 bool rowlane_supported(int nx, int nu, int N)
 {
 #define TINY_ROWLANE_CHECK(NX, NU, NN) \
@@ -392,5 +456,6 @@ hipError_t launch_admm_rowlane_pm(int nx, int nu, int N, bool exact, const RowPa
     TINY_FOR_EACH_ROWLANE(TINY_ROWLANE_PM_DISPATCH)
     return hipErrorInvalidValue;
 }
+#endif // TINY_ROWSIM_UNIT
 
 } // namespace tinympc

@@ -230,15 +230,16 @@ __device__ __forceinline__ void lqr_step(const RowGains<NX, NU> &G, bool is_x, b
 // "x1 = work.Adyn * x0 + work.Bdyn * work.u.col(0)" (pinned against that expression compiled from the reference, tests/test_oracle.py:
 // test_plant_step_bit_exact_vs_compiled_reference): a product whose rows and depth are both >= 8 goes through the column-major GEMV kernel, whose row
 // accumulator starts at +0 (visible in the sign of a zero result); otherwise the lazy product's plain sequential sum.
+// The overload with the two row arrays serves a plant that is not the model (tiny_batch_set_plant): Arow[k] = A_p(r, k), Brow[m] = B_p(r, m) on the x rows.
 template <int NX, int NU>
-__device__ __forceinline__ float plant_step(const RowGains<NX, NU> &G, float sv)
+__device__ __forceinline__ float plant_step(const float (&Arow)[NX], const float (&Brow)[NU], float sv)
 {
     using PL = RowPlans<NX, NU>;
     static_assert(PL::FWD_XA == PLAN_SEQ && PL::FWD_XB == PLAN_SEQ, "the plant kernel sums sequentially");
     static_assert(!(NX >= 8 && NU >= 8), "Bdyn*u would take the GEMV kernel too; not needed for nx + nu <= 16");
     float t[NX], t2[NU];
-    dpp_products<0, NX>(t, sv, G.M1);
-    dpp_products<NX, NU>(t2, sv, G.M2);
+    dpp_products<0, NX>(t, sv, Arow);
+    dpp_products<NX, NU>(t2, sv, Brow);
     float a = reduce<PLAN_SEQ>(t);
     if constexpr (NX >= 8)
     {
@@ -249,6 +250,11 @@ __device__ __forceinline__ float plant_step(const RowGains<NX, NU> &G, float sv)
         for (int k = 1; k < NX; k++) a = a + t[k];
     }
     return a + reduce<PLAN_SEQ>(t2);
+}
+template <int NX, int NU>
+__device__ __forceinline__ float plant_step(const RowGains<NX, NU> &G, float sv)
+{
+    return plant_step<NX, NU>(G.M1, G.M2, sv);
 }
 
 // backward_pass_grad step (admm.cpp:19-20): from p = p_{i+1} (x rows) and lin = [q_i ; r_i] compute

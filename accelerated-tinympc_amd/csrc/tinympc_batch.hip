@@ -219,7 +219,8 @@ __global__ void dual_width_kernel(const float *__restrict__ src, float *__restri
 // row count (eigen_orders.h: sequential for nx % 4 == 0, the halving tree for nx = 2, 3, the packet tree for nx = 1)
 __device__ __forceinline__ void plant_step_one(int b, float *__restrict__ x0buf, float *__restrict__ xarr, const float *__restrict__ uarr,
                                                const float *__restrict__ A, const float *__restrict__ Bm, int *__restrict__ wstart,
-                                               int window_advance, int layout, Geo g, int h16)
+                                               int window_advance, int layout, Geo g, int h16, const float *__restrict__ w = nullptr,
+                                               float *__restrict__ x_traj = nullptr)
 {
     const int nx = g.nx, nu = g.nu;
     const float *x0 = x0buf + (long long)b * nx;
@@ -242,10 +243,12 @@ __device__ __forceinline__ void plant_step_one(int b, float *__restrict__ x0buf,
         }
         else acc2 = gen_row_dot(Bm, nx, nu, i, u0, t);
         xn[i] = acc + acc2;
+        if (w) xn[i] = xn[i] + w[(long long)b * nx + i]; // the disturbance: one separately rounded add behind the product
     }
     for (int i = 0; i < nx; i++)
     {
         x0buf[(long long)b * nx + i] = xn[i];
+        if (x_traj) x_traj[(long long)b * nx + i] = xn[i];
         put_elem(xarr, idx_of(layout, g, 0, b, 0, i), xn[i], h16);
     }
     if (wstart && window_advance) wstart[b] += window_advance;
@@ -269,6 +272,29 @@ __global__ void plant_step_pm_kernel(float *__restrict__ x0buf, float *__restric
     const int nx = g.nx, nu = g.nu;
     const float *r = recs + (size_t)b * pm_gen_floats(nx, nu) + nu * nx + nx * nx + nu * nu + nx * nx;
     plant_step_one(b, x0buf, xarr, uarr, r, r + nx * nx, wstart, window_advance, layout, g, h16);
+}
+
+// ... of a simulated closed loop (tiny_batch_set_plant, tiny_batch_mpc_step_sim_async): A / Bm are the plant's matrices (one pair, or one per instance
+// a_stride / b_stride floats apart), the model record's where recs is set, else the shared model's; w and x_traj are this step's [batch][nx] rows or NULL
+__global__ void plant_step_sim_kernel(float *__restrict__ x0buf, float *__restrict__ xarr, const float *__restrict__ uarr, const float *__restrict__ A,
+                                      const float *__restrict__ Bm, unsigned a_stride, unsigned b_stride, const float *__restrict__ recs,
+                                      const float *__restrict__ w, float *__restrict__ x_traj, int *__restrict__ wstart, int window_advance, int batch,
+                                      int layout, Geo g, int h16)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= batch) return;
+    const int nx = g.nx, nu = g.nu;
+    if (recs)
+    {
+        A = recs + (size_t)b * pm_gen_floats(nx, nu) + nu * nx + nx * nx + nu * nu + nx * nx;
+        Bm = A + nx * nx;
+    }
+    else
+    {
+        A += (size_t)b * a_stride;
+        Bm += (size_t)b * b_stride;
+    }
+    plant_step_one(b, x0buf, xarr, uarr, A, Bm, wstart, window_advance, layout, g, h16, w, x_traj);
 }
 
 // Per-instance models (tiny_batch_set_models_device): the caller's eight [B] arrays into one record per instance in the run-time-dimension kernel's
@@ -546,6 +572,13 @@ struct TinyBatch
     bool pm = false;
     float *pm_src = nullptr, *pm_rho = nullptr, *pm_row[2] = {};
     bool pm_row_dirty[2] = {true, true};
+    // the simulated plant of the closed-loop calls (tiny_batch_set_plant): 0 the model's own Adyn / Bdyn, 1 one shared plant, 2 one per instance.  Column-major
+    // copies for the plant kernel ([1 or batch][nx*nx], [1 or batch][nx*nu]) and, where the class has a 16-lane kernel, the rows of [A | B] packed for its
+    // on-chip loop ([1 or batch][plant_row_floats]: SimParams)
+    int plant_mode = 0;
+    float *plant_A = nullptr, *plant_B = nullptr, *plant_rows = nullptr;
+    float *sim_stage[3] = {};      // tiny_batch_mpc_run_sim's device copies of w, u0_traj, x_traj: kept between calls (sized_buffer), so that their
+    size_t sim_stage_n[3] = {};    // addresses, which the captured graph bakes in, hold from call to call
     bool h16 = false; // ROW-layout arrays, Xref and bounds stored as IEEE binary16 (tiny_batch_set_storage)
     bool dual32 = false; // with h16: the duals pair gy IS fp32 right now (the state of the array)
     bool dual32_pref = false;   // tiny_batch_set_storage(tb, 16): fp32 duals wherever the kernel a call resolves to implements them, 16-bit duals elsewhere
@@ -1141,9 +1174,12 @@ bool tile16_pi_auto(const TinyBatch *tb) { return !tb->order_dev && tile16_auto_
 // tests/test_isa.py): in exact arithmetic a handle whose bounds table holds a zero on which the median breaks a tie the other way (TinyBatch::zero_ties)
 // is handed over to the next exact family — the 16-lane kernels, the state-on-chip wave kernel — like every combination an instantiation does not serve
 bool zero_ties_hand_over(const TinyBatch *tb) { return tb->zero_ties && tb->variant != VAR_ROW_FAST; }
-bool tile16_applies(const TinyBatch *tb, bool closed_loop)
+// A closed-loop run is simulated when a plant is set or the call passes a disturbance or asks for the state trajectory: its on-chip loop exists on the
+// 16-lane kernel only (admm_rowsim.hip), so tile16 hands such a run over as it does one with per-instance tables; the quad kernel's is replayed.
+// `sim` travels beside `closed_loop` from the call down to here (a question about the handle alone, such as the closed-loop kernel's name, knows the plant only)
+bool tile16_applies(const TinyBatch *tb, bool closed_loop, bool sim = false)
 {
-    if (!tb->tile16_ok || tb->h16 || zero_ties_hand_over(tb)) return false;
+    if (!tb->tile16_ok || tb->h16 || zero_ties_hand_over(tb) || (closed_loop && sim)) return false;
     if (tile16_per_instance(tb)) return !closed_loop && tile16_pi_plan(tb).fits;
     if (tb->xref_mode == 1) return tb->table_rows <= tile16_max_table_rows();
     return true;
@@ -1175,7 +1211,7 @@ struct KernelPlan
 };
 
 // the row / wave kernel a row variant launches for this handle (resolve_plan's second half; `forced`: tiny_batch_set_row_kernel)
-Kernel row_kernel_for(const TinyBatch *tb, bool closed_loop)
+Kernel row_kernel_for(const TinyBatch *tb, bool closed_loop, bool sim = false)
 {
     const std::optional<Kernel> forced = tb->row_family_forced;
     // one wavefront per instance: state on chip where the horizon fits (admm_waveres.hip), else streamed through HBM (admm_wave.hip)
@@ -1196,7 +1232,7 @@ Kernel row_kernel_for(const TinyBatch *tb, bool closed_loop)
     if (!bounds_all_shared(tb))
     {
         if (optional_terms) return Kernel::Rowstream;
-        if (tile16_applies(tb, closed_loop) && (forced == Kernel::Tile16 || (!forced && tile16_pi_auto(tb)))) return Kernel::Tile16;
+        if (tile16_applies(tb, closed_loop, sim) && (forced == Kernel::Tile16 || (!forced && tile16_pi_auto(tb)))) return Kernel::Tile16;
         const std::optional<Kernel> ff = forced == Kernel::Tile16 ? std::nullopt : forced; // tile16 asked for but not applicable (closed-loop run): like auto
         if (tb->row_dims_ok && !tb->h16 && (!ff || ff == Kernel::Rowlane)) return Kernel::Rowlane;
         if (tb->rowloop_ok && (!ff || ff == Kernel::Rowloop)) return Kernel::Rowloop; // one step ahead from global memory
@@ -1206,7 +1242,7 @@ Kernel row_kernel_for(const TinyBatch *tb, bool closed_loop)
     // sixteen instances per wave, products on the matrix cores (admm_tile16.hip): on request only; needs fp32 storage and
     // a reference it does not have to keep resident (window of a table, or one shared reference)
     if (forced == Kernel::Tile16)
-        return tile16_applies(tb, closed_loop) ? Kernel::Tile16 : (tb->row_dims_ok ? Kernel::Rowlane : (tb->rowloop_ok ? Kernel::Rowloop : Kernel::Rowstream));
+        return tile16_applies(tb, closed_loop, sim) ? Kernel::Tile16 : (tb->row_dims_ok ? Kernel::Rowlane : (tb->rowloop_ok ? Kernel::Rowloop : Kernel::Rowstream));
     if (forced) return *forced;
     if (tb->quad_ok) return Kernel::Quadlane; // four lanes per instance (admm_quadlane.hip): nx = 4, nu = 1
     // auto (round 3): sixteen instances per wave on the matrix cores where the launch is at least two rounds deep for its one
@@ -1217,7 +1253,7 @@ Kernel row_kernel_for(const TinyBatch *tb, bool closed_loop)
     // (round 4: tile16's MPC loop stays on chip too — tiny_batch_set_row_kernel(tb, 5) — but the warm-started solves of a closed loop are short and
     //  uneven, and sixteen instances in lock step lose more there than the matrix cores gain: measured 1.02 ms per MPC step of 65 536 tracking
     //  instances against 0.97 ms on the 16-lane kernel, so the automatic choice of a closed-loop run stays with the latter)
-    if (tile16_applies(tb, closed_loop) && !tb->order_dev && (closed_loop ? tile16_closed_loop_size(tb) : tile16_auto_size(tb))) return Kernel::Tile16;
+    if (tile16_applies(tb, closed_loop, sim) && !tb->order_dev && (closed_loop ? tile16_closed_loop_size(tb) : tile16_auto_size(tb))) return Kernel::Tile16;
     if (tb->row_dims_ok) return Kernel::Rowlane; // unrolled register-resident (fastest, one instantiation per (nx, nu, N))
     if (tb->rowloop_ok) return Kernel::Rowloop;  // rolled-loop register-resident (any N <= 64)
     return Kernel::Rowstream;                    // any N with the state in HBM
@@ -1236,7 +1272,7 @@ int plan_of(const TinyBatch *tb, int v, Kernel row, KernelPlan *out)
 
 // THE policy: which kernel serves this handle, in which arithmetic.  `closed_loop`: the call is a tiny_batch_mpc_run_*(steps > 1) — the automatic choice
 // then keeps the kernel with the on-chip MPC loop.  Reads the handle and changes nothing; the answer depends on rows_vary, which prepare_inputs() fills.
-int resolve_plan(const TinyBatch *tb, bool closed_loop, KernelPlan *out)
+int resolve_plan(const TinyBatch *tb, bool closed_loop, KernelPlan *out, bool sim = false)
 {
     int v = tb->variant;
     if (tb->pm)
@@ -1274,7 +1310,7 @@ int resolve_plan(const TinyBatch *tb, bool closed_loop, KernelPlan *out)
     // per-instance bounds: the streaming row kernel and the wave kernel read them per instance; the register-resident
     // kernels stage ONE table in LDS and need batch-shared bounds
     const bool row_ok = tb->row_dims_ok || tb->rowmath_ok || tb->wave_ok;
-    const Kernel row = row_kernel_for(tb, closed_loop);
+    const Kernel row = row_kernel_for(tb, closed_loop, sim);
     if (v == VAR_ROW_FAST && tb->wave_ok && row != Kernel::Waveres && row != Kernel::Tile48)
         return fail(TINY_BATCH_EUNSUPPORTED, "fma arithmetic for 16 < nx + nu <= 64 needs the state-on-chip wave kernel (N <= 50); beyond that it is the streaming MFMA kernel (variant 1)");
     if (v == VAR_AUTO)
@@ -1323,12 +1359,12 @@ std::string kernel_name(const TinyBatch *tb, const KernelPlan &pl)
 
 // the name of the kernel a lone solve (closed_loop = false) or a closed-loop run of several steps launches; "unsupported" where no kernel would run.
 // One buffer per question and handle: the pointer holds until the same question is asked of the same handle again
-const char *plan_name(TinyBatch *tb, bool closed_loop)
+const char *plan_name(TinyBatch *tb, bool closed_loop, bool sim = false)
 {
     std::string &name = tb->name_buf[closed_loop ? 1 : 0];
     const std::string keep = g_err;
     KernelPlan pl;
-    name = resolve_plan(tb, closed_loop, &pl) ? "unsupported" : kernel_name(tb, pl);
+    name = resolve_plan(tb, closed_loop, &pl, sim) ? "unsupported" : kernel_name(tb, pl);
     g_err = keep;
     return name.c_str();
 }
@@ -1455,7 +1491,7 @@ int ensure_tile_map(TinyBatch *tb, const KernelPlan &pl)
 }
 
 // everything a solve needs that may allocate, copy or synchronise (not capturable in a hipGraph); *plan: what the solve launches
-int prepare_solve(TinyBatch *tb, bool closed_loop, KernelPlan *plan)
+int prepare_solve(TinyBatch *tb, bool closed_loop, KernelPlan *plan, bool sim = false)
 {
     if (!(tb->pm || (tb->have_cache && tb->have_dyn)) || !tb->have_settings)
         return fail(TINY_BATCH_ENOTREADY, "tiny_batch_solve: set_cache, set_dynamics (or set_models) and set_settings must be called first");
@@ -1472,7 +1508,7 @@ int prepare_solve(TinyBatch *tb, bool closed_loop, KernelPlan *plan)
     // differ only between tile16 and another kernel of the ROW layout, in the same arithmetic, under fp32 storage (rows_vary enters through the pi
     // tables' LDS fit alone, and fp16 storage excludes tile16), where settle_dual_width does nothing
     KernelPlan pl;
-    TRY(resolve_plan(tb, closed_loop, &pl));
+    TRY(resolve_plan(tb, closed_loop, &pl, sim));
     if (tb->pm) TRY(pack_models(tb, pl));
     else if (tb->gains_dirty) TRY(pack_gains(tb));
     // (whatever the mode says NOW: a launch sequence enqueued after one prepare_solve — the captured graph of tiny_batch_mpc_run_async — gains a history with its
@@ -1493,7 +1529,7 @@ int prepare_solve(TinyBatch *tb, bool closed_loop, KernelPlan *plan)
     // reset_workspace() is folded into the launch by every fused kernel: the register-resident ones start from zero registers,
     // the streaming ones (MFMA, rowstream, wavestream) read zeros in their first iteration and zero-fill p, d, v, z of such an
     // instance in their epilogue
-    if (inputs_rebuilt) TRY(resolve_plan(tb, closed_loop, plan));
+    if (inputs_rebuilt) TRY(resolve_plan(tb, closed_loop, plan, sim));
     else *plan = pl; // rows_vary did not move: the provisional plan is the final one
     return closed_loop ? 0 : ensure_tile_map(tb, *plan);
 }
@@ -1565,12 +1601,19 @@ int enqueue_dispatch_order(TinyBatch *tb, const KernelPlan &pl, int run_steps, b
 }
 
 // the ONE place that launches a solve kernel.  P: the row-layout arguments (the two TILE-layout kernels take theirs from fill_solve_params)
-hipError_t launch_kernel(const TinyBatch *tb, const KernelPlan &pl, RowParams &P)
+// S: the on-chip loop of a simulated run (16-lane kernel only)
+hipError_t launch_kernel(const TinyBatch *tb, const KernelPlan &pl, RowParams &P, const SimParams *S = nullptr)
 {
     const int nx = tb->nx, nu = tb->nu, N = tb->N;
+    if (S && pl.kernel != Kernel::Rowlane) return hipErrorInvalidValue;
     switch (pl.kernel)
     {
     case Kernel::Rowlane:
+        if (S)
+        {
+            const ModelParams M = pl.pm ? model_params(tb, pl) : ModelParams{};
+            return launch_admm_rowsim(nx, nu, N, pl.exact, P, pl.pm ? &M : nullptr, *S, tb->stream);
+        }
         return pl.pm ? launch_admm_rowlane_pm(nx, nu, N, pl.exact, P, model_params(tb, pl), tb->stream) : launch_admm_rowlane(nx, nu, N, pl.exact, tb->h16, P, tb->stream);
     case Kernel::Rowloop: return launch_admm_rowloop(nx, nu, pl.exact, tb->h16, P, tb->stream);
     case Kernel::Rowstream: return launch_admm_rowstream(nx, nu, pl.exact, tb->h16, P, tb->stream);
@@ -1642,9 +1685,21 @@ int enqueue_solve(TinyBatch *tb, const KernelPlan &pl, bool record_events)
     return 0;
 }
 
-int enqueue_plant_step(TinyBatch *tb, int window_advance)
+// d_w / d_x_traj: this step's [batch][nx] rows (NULL: no disturbance / not recorded).  With neither and no plant set: the launch it has always been
+int enqueue_plant_step(TinyBatch *tb, int window_advance, const float *d_w = nullptr, float *d_x_traj = nullptr)
 {
     if (tb->xref_mode == 1 && window_advance) tb->tile_map_dirty = true; // the kernel slides xref_start[]
+    if (tb->plant_mode || d_w || d_x_traj)
+    {
+        // priority: the plant, then the per-instance model record, then the shared model
+        const bool per = tb->plant_mode == 2;
+        const float *A = tb->plant_mode ? tb->plant_A : tb->dA, *Bm = tb->plant_mode ? tb->plant_B : tb->dB;
+        hipLaunchKernelGGL(plant_step_sim_kernel, dim3((tb->batch + 127) / 128), dim3(128), 0, tb->stream, tb->x0buf, work_ptr(tb, TINY_ARR_X), work_ptr(tb, TINY_ARR_U),
+                           A, Bm, per ? (unsigned)(tb->nx * tb->nx) : 0u, per ? (unsigned)(tb->nx * tb->nu) : 0u, (!tb->plant_mode && tb->pm) ? tb->pm_src : nullptr,
+                           d_w, d_x_traj, tb->xref_mode == 1 ? tb->xref_start : nullptr, window_advance, tb->batch, tb->layout, geo(tb), h16_of(tb, tb->layout));
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
     if (tb->pm)
     {
         hipLaunchKernelGGL(plant_step_pm_kernel, dim3((tb->batch + 127) / 128), dim3(128), 0, tb->stream, tb->x0buf, work_ptr(tb, TINY_ARR_X), work_ptr(tb, TINY_ARR_U),
@@ -1765,6 +1820,8 @@ void tiny_batch_destroy(TinyBatch *tb)
     (void)guarded_free(tb->res); (void)guarded_free(tb->status); (void)guarded_free(tb->iter); (void)guarded_free(tb->n_unsolved);
     (void)guarded_free(tb->opnd); (void)guarded_free(tb->qvec); (void)guarded_free(tb->gen_mats); (void)guarded_free(tb->mats_exact); (void)guarded_free(tb->mats_fast);
     (void)guarded_free(tb->pm_src); (void)guarded_free(tb->pm_rho); (void)guarded_free(tb->pm_row[0]); (void)guarded_free(tb->pm_row[1]);
+    (void)guarded_free(tb->plant_A); (void)guarded_free(tb->plant_B); (void)guarded_free(tb->plant_rows);
+    for (float *p : tb->sim_stage) (void)guarded_free(p);
     (void)guarded_free(tb->dA); (void)guarded_free(tb->dB); (void)guarded_free(tb->x0buf); (void)guarded_free(tb->staging); (void)guarded_free(tb->conv_dev);
     if (tb->graph_exec) (void)hipGraphExecDestroy(tb->graph_exec);
     if (tb->own_stream) (void)hipStreamDestroy(tb->own_stream);
@@ -1901,6 +1958,59 @@ int tiny_batch_models_per_instance(TinyBatch *tb)
 {
     CHECK_TB(tb);
     return tb->pm ? 1 : 0;
+}
+
+int tiny_batch_clear_plant(TinyBatch *tb)
+{
+    CHECK_TB(tb);
+    if (!tb->plant_mode) return 0;
+    TRY(set_device(tb));
+    invalidate_graph(tb);
+    HIP_TRY(hipStreamSynchronize(tb->stream)); // a launch still reading the plant may be in flight
+    for (float **p : {&tb->plant_A, &tb->plant_B, &tb->plant_rows})
+    {
+        (void)guarded_free(*p);
+        *p = nullptr;
+    }
+    tb->plant_mode = 0;
+    return 0;
+}
+
+int tiny_batch_set_plant(TinyBatch *tb, const float *A, const float *Bm, int shared)
+{
+    CHECK_TB(tb); CHECK_PTR(A); CHECK_PTR(Bm);
+    if (tb->nx > 64) return fail(TINY_BATCH_EUNSUPPORTED, "tiny_batch_set_plant: the closed-loop calls support nx <= 64");
+    TRY(set_device(tb)); // the copies below belong on the handle's device, whatever device the calling thread last selected
+    TRY(tiny_batch_clear_plant(tb)); // releases the previous copies
+    invalidate_graph(tb);            // (also where there was no plant before: the captured plant launches read the model's matrices)
+    const size_t cnt = shared ? 1 : (size_t)tb->batch, nx = tb->nx, nu = tb->nu;
+    const bool rows = nx + nu <= 16; // the 16-lane mapping: the on-chip loop reads the rows of [A | B] in the gain rows' layout, zeros on the input lanes
+    const size_t rf = (size_t)plant_row_floats(tb->nx, tb->nu);
+    std::vector<float> packed(rows ? cnt * rf : 0, 0.f);
+    for (size_t b = 0; rows && b < cnt; b++)
+        for (size_t r = 0; r < nx; r++)
+        {
+            for (size_t k = 0; k < nx; k++) packed[b * rf + k * 16 + r] = A[b * nx * nx + k * nx + r];
+            for (size_t m = 0; m < nu; m++) packed[b * rf + (nx + m) * 16 + r] = Bm[b * nx * nu + m * nx + r];
+        }
+    int rc = 0;
+    auto up = [&](float **dst, const float *src, size_t n)
+    {
+        if (rc == 0 && guarded_malloc((void **)dst, n * sizeof(float)) != hipSuccess) rc = fail(TINY_BATCH_EHIP, "tiny_batch_set_plant: device allocation failed");
+        if (rc == 0 && hipMemcpy(*dst, src, n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) rc = fail(TINY_BATCH_EHIP, "tiny_batch_set_plant: hipMemcpy failed");
+    };
+    up(&tb->plant_A, A, cnt * nx * nx);
+    up(&tb->plant_B, Bm, cnt * nx * nu);
+    if (rows) up(&tb->plant_rows, packed.data(), cnt * rf);
+    tb->plant_mode = shared ? 1 : 2;
+    if (rc) (void)tiny_batch_clear_plant(tb);
+    return rc;
+}
+
+int tiny_batch_plant_mode(TinyBatch *tb)
+{
+    CHECK_TB(tb);
+    return tb->plant_mode;
 }
 
 int tiny_batch_riccati_device(int nx, int nu, int count, const double *d_A, const double *d_B, const double *d_Q, const double *d_R, const double *d_rho,
@@ -2411,15 +2521,30 @@ int tiny_batch_get_u0_device(TinyBatch *tb, float *d_u0)
     return launch_unpack(tb, work_ptr(tb, TINY_ARR_U), d_u0, tb->layout, 1, tb->batch, 0, 1);
 }
 
-int tiny_batch_mpc_step_async(TinyBatch *tb, int window_advance)
+namespace
 {
-    CHECK_TB(tb);
+// who: the public call, for its messages
+int mpc_step_sim(TinyBatch *tb, const char *who, int window_advance, const float *d_w)
+{
     if (tb->nx > 64) return fail(TINY_BATCH_EUNSUPPORTED, "mpc_step supports nx <= 64");
-    if (window_advance < 0) return fail(TINY_BATCH_EINVAL, "tiny_batch_mpc_step_async: window_advance must be >= 0 (got %d): the window gather clamps at the last table row only", window_advance);
+    if (window_advance < 0) return fail(TINY_BATCH_EINVAL, "%s: window_advance must be >= 0 (got %d): the window gather clamps at the last table row only", who, window_advance);
     // x.col(0) already holds x0 (set_x0 / previous plant step); reset duals, solve, then simulate forward.
     tb->duals_zero_pending = true;
     TRY(tiny_batch_solve_async(tb));
-    return enqueue_plant_step(tb, window_advance);
+    return enqueue_plant_step(tb, window_advance, d_w);
+}
+} // namespace
+
+int tiny_batch_mpc_step_sim_async(TinyBatch *tb, int window_advance, const float *d_w)
+{
+    CHECK_TB(tb);
+    return mpc_step_sim(tb, "tiny_batch_mpc_step_sim_async", window_advance, d_w);
+}
+
+int tiny_batch_mpc_step_async(TinyBatch *tb, int window_advance)
+{
+    CHECK_TB(tb);
+    return mpc_step_sim(tb, "tiny_batch_mpc_step_async", window_advance, nullptr);
 }
 
 // `steps` closed-loop MPC steps back to back; d_u0_traj (device, [steps][B][nu], may be NULL) receives u.col(0) of every
@@ -2428,35 +2553,64 @@ int tiny_batch_mpc_step_async(TinyBatch *tb, int window_advance)
 //    between solves (admm_rowlane.hip, MPC = true); the host only adds the plant step of the last solve;
 //  * otherwise the launch sequence (counter reset, solve kernel, plant kernel) x steps is captured ONCE into a hipGraph and
 //    replayed, which removes the per-launch overhead that dominates small batches with short warm-started solves.
+namespace
+{
+int mpc_run_sim(TinyBatch *tb, const char *who, int steps, int window_advance, const float *d_w, float *d_u0_traj, float *d_x_traj);
+}
+
+// ... against the plant of tiny_batch_set_plant, with a disturbance d_w and the state trajectory d_x_traj (both DEVICE [steps][B][nx], may be NULL).  A run
+// is simulated when a plant is set or either pointer is: on the 16-lane kernel it takes the SIM instantiations of the on-chip loop (admm_rowsim.hip),
+// every other kernel replays solve + plant kernel per step with the rows of step k baked into the graph.
+int tiny_batch_mpc_run_sim_async(TinyBatch *tb, int steps, int window_advance, const float *d_w, float *d_u0_traj, float *d_x_traj)
+{
+    CHECK_TB(tb);
+    return mpc_run_sim(tb, "tiny_batch_mpc_run_sim_async", steps, window_advance, d_w, d_u0_traj, d_x_traj);
+}
+
 int tiny_batch_mpc_run_traj_async(TinyBatch *tb, int steps, int window_advance, float *d_u0_traj)
 {
     CHECK_TB(tb);
-    if (steps < 1) return fail(TINY_BATCH_EINVAL, "tiny_batch_mpc_run_async: steps must be >= 1");
-    if (window_advance < 0) return fail(TINY_BATCH_EINVAL, "tiny_batch_mpc_run_async: window_advance must be >= 0 (got %d): the window gather clamps at the last table row only", window_advance);
+    return mpc_run_sim(tb, "tiny_batch_mpc_run_async", steps, window_advance, nullptr, d_u0_traj, nullptr);
+}
+
+namespace
+{
+// who: the public call, for its messages
+int mpc_run_sim(TinyBatch *tb, const char *who, int steps, int window_advance, const float *d_w, float *d_u0_traj, float *d_x_traj)
+{
+    if (steps < 1) return fail(TINY_BATCH_EINVAL, "%s: steps must be >= 1", who);
+    if (window_advance < 0) return fail(TINY_BATCH_EINVAL, "%s: window_advance must be >= 0 (got %d): the window gather clamps at the last table row only", who, window_advance);
     if (tb->nx > 64) return fail(TINY_BATCH_EUNSUPPORTED, "mpc_run supports nx <= 64");
-    if (tb->max_iter <= 0) return fail(TINY_BATCH_EINVAL, "tiny_batch_mpc_run_async needs max_iter > 0");
+    if (tb->max_iter <= 0) return fail(TINY_BATCH_EINVAL, "%s needs max_iter > 0", who);
     TRY(set_device(tb));
     if (tb->xref_mode == 1 && window_advance) tb->tile_map_dirty = true; // every path below slides xref_start[] (the on-chip loop writes it back)
     const bool from_reset = tb->cold_pending; // (flush_pending materialises the zeros and clears the flag: the run's first solve is the cold one all the same)
     TRY(flush_pending(tb)); // every solve of the run starts from "duals reset, workspace warm"
     tb->duals_zero_pending = true;
+    const bool sim = tb->plant_mode != 0 || d_w != nullptr || d_x_traj != nullptr; // the run is simulated
     KernelPlan pl;
-    TRY(prepare_solve(tb, steps > 1, &pl));
-    const size_t u0n = (size_t)tb->batch * tb->nu;
-    if (traits(pl.kernel).onchip_mpc && !tb->h16 && steps > 1 && bounds_all_shared(tb))
+    TRY(prepare_solve(tb, steps > 1, &pl, sim));
+    const size_t u0n = (size_t)tb->batch * tb->nu, x0n = (size_t)tb->batch * tb->nx;
+    // the rows of MPC step k
+    auto w_at = [&](int k) { return d_w ? d_w + (size_t)k * x0n : nullptr; };
+    auto xt_at = [&](int k) { return d_x_traj ? d_x_traj + (size_t)k * x0n : nullptr; };
+    if (traits(pl.kernel).onchip_mpc && !tb->h16 && steps > 1 && bounds_all_shared(tb) && (!sim || pl.kernel == Kernel::Rowlane))
     {
         RowParams P;
         fill_row_params(tb, P, pl.exact);
         P.mpc_steps = steps; P.window_advance = window_advance; P.u0_traj = d_u0_traj;
+        SimParams S;
+        if (tb->plant_mode) { S.plant = tb->plant_rows; S.plant_stride = tb->plant_mode == 2 ? (unsigned)plant_row_floats(tb->nx, tb->nu) : 0u; }
+        S.w = d_w; S.x_traj = d_x_traj;
         const int applied = enqueue_dispatch_order(tb, pl, steps, from_reset, P);
         if (applied < 0) return applied;
         tb->last_dispatch = applied;
         tb->last_grouped = false;
         // (tile16 gets tb->tile_queue like a lone solve: its two-ended queue is off whenever mpc_steps > 1 — t16_tail_stride returns 0 — so the setting changes nothing here)
-        const hipError_t e = launch_kernel(tb, pl, P);
+        const hipError_t e = launch_kernel(tb, pl, P, sim ? &S : nullptr);
         if (e != hipSuccess) return fail(TINY_BATCH_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
         if (d_u0_traj) TRY(launch_unpack(tb, work_ptr(tb, TINY_ARR_U), d_u0_traj + (size_t)(steps - 1) * u0n, tb->layout, 1, tb->batch, 0, 1));
-        TRY(enqueue_plant_step(tb, window_advance));
+        TRY(enqueue_plant_step(tb, window_advance, w_at(steps - 1), xt_at(steps - 1))); // the last step's plant step is the host's: the same plant, its own rows
         tb->duals_zero_pending = tb->cold_pending = false;
         tb->iter_history = true; // iter[] = the counts of the run's last solve
         tb->ev_valid = false;
@@ -2472,8 +2626,9 @@ int tiny_batch_mpc_run_traj_async(TinyBatch *tb, int steps, int window_advance, 
     // (round 3: the signature is complete — rho, the shared / per-instance modes that set the strides, the bound flags and the
     // dispatch order are in it — so setters that only change buffer CONTENTS no longer drop the graph: `set_xref; mpc_run(k)`
     // in a loop replays one captured graph instead of re-capturing it every step)
-    char sig[560];
-    snprintf(sig, sizeof sig, "%p|%p|%p|%d|%d|%d|%s|%d|%d|%g|%g|%d|%d|%p|%p|%p|%d|%p|%p|%p|%p|%d%d|%a|%d%d%d|%d%d|%d|%p|%p|%p|%d", (void *)tb->pm_src, (void *)tb->pm_row[0],
+    char sig[680];
+    snprintf(sig, sizeof sig, "%d|%p|%p|%p|%p|%p|%p|%p|%d|%d|%d|%s|%d|%d|%g|%g|%d|%d|%p|%p|%p|%d|%p|%p|%p|%p|%d%d|%a|%d%d%d|%d%d|%d|%p|%p|%p|%d", tb->plant_mode, (void *)tb->plant_A,
+             (void *)tb->plant_B, (const void *)d_w, (void *)d_x_traj, (void *)tb->pm_src, (void *)tb->pm_row[0],
              (void *)tb->pm_row[1], steps, window_advance, tb->variant, kernel_name(tb, pl).c_str(), tb->max_iter,
              tb->check_termination, (double)tb->abs_pri_tol, (double)tb->abs_dua_tol, tb->xref_mode, tb->table_rows, (void *)tb->pair[0],
              (void *)tb->arr[0], (void *)tb->r_bounds, (int)tb->h16, (void *)tb->stream, (void *)d_u0_traj, (void *)tb->r_xref,
@@ -2491,7 +2646,7 @@ int tiny_batch_mpc_run_traj_async(TinyBatch *tb, int steps, int window_advance, 
             tb->duals_zero_pending = true;
             rc = enqueue_solve(tb, pl, false);
             if (rc == 0 && d_u0_traj) rc = launch_unpack(tb, work_ptr(tb, TINY_ARR_U), d_u0_traj + (size_t)k * u0n, tb->layout, 1, tb->batch, 0, 1);
-            if (rc == 0) rc = enqueue_plant_step(tb, window_advance);
+            if (rc == 0) rc = enqueue_plant_step(tb, window_advance, w_at(k), xt_at(k));
         }
         hipError_t ec = hipStreamEndCapture(tb->stream, &graph);
         if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
@@ -2507,6 +2662,7 @@ int tiny_batch_mpc_run_traj_async(TinyBatch *tb, int steps, int window_advance, 
     tb->ev_valid = false;
     return 0;
 }
+} // namespace
 
 int tiny_batch_mpc_run_async(TinyBatch *tb, int steps, int window_advance)
 {
@@ -2532,6 +2688,33 @@ int tiny_batch_mpc_run_traj(TinyBatch *tb, int steps, int window_advance, float 
     }
     (void)guarded_free(d);
     return rc;
+}
+
+// host-array variant of tiny_batch_mpc_run_sim_async (any of the three may be NULL): the device buffers live on the HANDLE's device for the call
+int tiny_batch_mpc_run_sim(TinyBatch *tb, int steps, int window_advance, const float *w, float *u0_traj, float *x_traj)
+{
+    CHECK_TB(tb);
+    if (steps < 1) return fail(TINY_BATCH_EINVAL, "tiny_batch_mpc_run_sim: steps must be >= 1");
+    TRY(set_device(tb));
+    // device copies kept on the handle and re-allocated only when their size changes: on the replayed paths the captured graph bakes their addresses
+    // in (they are in its signature), and a loop of equal calls must replay one graph
+    const size_t nxf = (size_t)steps * tb->batch * tb->nx, nuf = (size_t)steps * tb->batch * tb->nu;
+    const void *host[3] = {w, u0_traj, x_traj};
+    const size_t nf[3] = {nxf, nuf, nxf};
+    float *dev[3] = {};
+    for (int k = 0; k < 3; k++)
+        if (host[k])
+        {
+            if (tb->sim_stage[k] && tb->sim_stage_n[k] != nf[k]) HIP_TRY(hipStreamSynchronize(tb->stream)); // a run still using the old buffer may be in flight
+            TRY(sized_buffer(&tb->sim_stage[k], &tb->sim_stage_n[k], nf[k]));
+            dev[k] = tb->sim_stage[k];
+        }
+    if (w) HIP_TRY(hipMemcpy(dev[0], w, nxf * sizeof(float), hipMemcpyHostToDevice));
+    TRY(mpc_run_sim(tb, "tiny_batch_mpc_run_sim", steps, window_advance, dev[0], dev[1], dev[2]));
+    HIP_TRY(hipStreamSynchronize(tb->stream));
+    if (u0_traj) HIP_TRY(hipMemcpy(u0_traj, dev[1], nuf * sizeof(float), hipMemcpyDeviceToHost));
+    if (x_traj) HIP_TRY(hipMemcpy(x_traj, dev[2], nxf * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
 }
 
 int tiny_batch_get_x0(TinyBatch *tb, float *x0)
@@ -2642,7 +2825,7 @@ int tiny_batch_arithmetic(TinyBatch *tb)
 const char *tiny_batch_closed_loop_kernel_name(TinyBatch *tb)
 {
     if (!tb) return "";
-    return plan_name(tb, true);
+    return plan_name(tb, true, tb->plant_mode != 0); // (a run that passes d_w or d_x_traj without a plant is simulated too: only the call knows)
 }
 
 int tiny_batch_set_row_kernel(TinyBatch *tb, int family)

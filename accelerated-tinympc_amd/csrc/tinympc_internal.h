@@ -152,6 +152,21 @@ struct ModelParams
     unsigned mats_stride = 0; // floats between instances
     const float *rho = nullptr;
 };
+// The simulated closed loop (tiny_batch_set_plant, tiny_batch_mpc_run_sim_async): a third kernel argument of the on-chip loop's SIM instantiations
+// (admm_rowsim.hip), beside RowParams / ModelParams, whose layouts stay as they are.
+//   plant:  the rows of [A_p | B_p] in the gain rows' layout, entry (k, r) at k*16 + r: k < nx holds A_p(r, k), nx <= k < nx + nu holds B_p(r, k - nx), the
+//           input lanes (r >= nx) hold zeros.  One table, or one per instance plant_stride = plant_row_floats(nx, nu) floats apart.  NULL: the model's own
+//           Adyn / Bdyn (the M1 / M2 gain rows)
+//   w:      [mpc_steps][batch][nx] additive disturbance, NULL = no addition        x_traj: [mpc_steps][batch][nx] x0 after every plant step, NULL = not recorded
+//           (the kernel reads / writes rows 0 .. mpc_steps - 2; the last plant step of a run is the host's)
+struct SimParams
+{
+    const float *plant = nullptr;
+    unsigned plant_stride = 0; // floats between instances (0 = one plant for the batch)
+    const float *w = nullptr;
+    float *x_traj = nullptr;
+};
+__host__ __device__ inline int plant_row_floats(int nx, int nu) { return (nx + nu) * 16; }
 // floats of one instance's record in the two forms
 __host__ __device__ inline int pm_row_floats(int nx, int nu) { return (3 * nx + 2 * nu + 1) * 16; }
 __host__ __device__ inline int pm_gen_floats(int nx, int nu) { return nu * nx + nx * nx + nu * nu + nx * nx + nx * nx + nx * nu + nx; }
@@ -186,6 +201,9 @@ hipError_t launch_admm_rowlane(int nx, int nu, int N, bool exact, bool h16, cons
 // the same kernel with per-instance models (admm_rowlane_pm_kernel): fp32 storage, no optional terms; shared or per-instance bounds for one solve,
 // shared bounds for the on-chip closed loop (P.mpc_steps > 1)
 hipError_t launch_admm_rowlane_pm(int nx, int nu, int N, bool exact, const RowParams &P, const ModelParams &M, hipStream_t stream);
+// the on-chip closed loop (P.mpc_steps > 1) against a separate plant, with a disturbance and the state trajectory (admm_rowsim.hip: the SIM instantiations
+// of the same body): fp32 storage, shared bounds; M = NULL: the batch-shared model, else per-instance models
+hipError_t launch_admm_rowsim(int nx, int nu, int N, bool exact, const RowParams &P, const ModelParams *M, const SimParams &S, hipStream_t stream);
 bool rowdims_supported(int nx, int nu);
 hipError_t launch_admm_rowstream(int nx, int nu, bool exact, bool h16, const RowParams &P, hipStream_t stream);
 hipError_t launch_admm_step(int nx, int nu, bool exact, bool h16, int fn, const RowParams &P, int *conv_out, hipStream_t stream);

@@ -88,6 +88,9 @@ def load_library(build_if_missing: bool = False) -> C.CDLL:
         "tiny_batch_clear_models": [P], "tiny_batch_models_per_instance": [P],
         "tiny_batch_riccati_device": [C.c_int, C.c_int, C.c_int, P, P, P, P, P, P, P, P, P, P, P, P],
         "tiny_batch_set_systems": [P, D, D, D, D, D, I],
+        "tiny_batch_set_plant": [P, F, F, C.c_int], "tiny_batch_clear_plant": [P], "tiny_batch_plant_mode": [P],
+        "tiny_batch_mpc_step_sim_async": [P, C.c_int, P], "tiny_batch_mpc_run_sim_async": [P, C.c_int, C.c_int, P, P, P],
+        "tiny_batch_mpc_run_sim": [P, C.c_int, C.c_int, F, F, F],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)
@@ -295,6 +298,27 @@ class TinyBatchSolver:
     def models_per_instance(self) -> bool:
         return bool(self._check(self.lib.tiny_batch_models_per_instance(self._h)))
 
+    # -- the simulated plant of the closed-loop calls (tiny_batch_set_plant) ------------------------
+    def set_plant(self, A, B):
+        """The plant the closed-loop calls simulate, in place of the model's Adyn / Bdyn: (nx, nx) / (nx, nu) for one plant shared by the batch,
+        (B, nx, nx) / (B, nx, nu) for one per instance (logical orientation, converted as set_models does).  The solver never reads it."""
+        a, b = np.asarray(A, np.float32), np.asarray(B, np.float32)
+        if a.ndim == 2:
+            assert a.shape == (self.nx, self.nx) and b.shape == (self.nx, self.nu), (a.shape, b.shape)
+            ca, cb, shared = _colmajor(a), _colmajor(b), 1
+        else:
+            assert a.shape == (self.B, self.nx, self.nx) and b.shape == (self.B, self.nx, self.nu), (a.shape, b.shape)
+            ca, cb, shared = _colmajor_batch(a), _colmajor_batch(b), 0
+        self._check(self.lib.tiny_batch_set_plant(self._h, _fp(ca), _fp(cb), shared))
+
+    def clear_plant(self):
+        """Back to the model's own Adyn / Bdyn."""
+        self._check(self.lib.tiny_batch_clear_plant(self._h))
+
+    def plant_mode(self) -> int:
+        """0 the model, 1 one shared plant, 2 one plant per instance"""
+        return self._check(self.lib.tiny_batch_plant_mode(self._h))
+
     # -- plumbing ---------------------------------------------------------------------------
     def _check(self, rc):
         if rc < 0:
@@ -305,6 +329,9 @@ class TinyBatchSolver:
         if getattr(self, "_h", None) and self._h.value:
             self.lib.tiny_batch_destroy(self._h)
             self._h = C.c_void_p()
+        if getattr(self, "_w_dev", None):
+            _hip().hipFree(self._w_dev)
+            self._w_dev = None
 
     def __del__(self):
         try:
@@ -454,6 +481,36 @@ class TinyBatchSolver:
         out = np.zeros((steps, self.B, self.nu), np.float32)
         self._check(self.lib.tiny_batch_mpc_run_traj(self._h, steps, window_advance, _fp(out)))
         return out
+
+    def mpc_step_sim(self, window_advance: int = 0, w=None):
+        """tiny_batch_mpc_step_sim_async: one MPC step against the plant of set_plant (the model's without one), x0 <- (A x0 + B u.col(0)) + w with
+        w (B, nx) or None (no addition).  The disturbance row is staged in a device buffer of this object, so the call waits for the step before it."""
+        dw = None
+        if w is not None:
+            a = _f32(w); assert a.shape == (self.B, self.nx), a.shape
+            hip = _hip()
+            self.synchronize()  # the previous step's plant kernel may still read the buffer
+            if getattr(self, "_w_dev", None) is None:
+                p = C.c_void_p()
+                if hip.hipMalloc(C.byref(p), a.nbytes) != 0:
+                    raise TinyBatchError("hipMalloc failed")
+                self._w_dev = p
+            if hip.hipMemcpy(self._w_dev, a.ctypes.data, a.nbytes, 1) != 0:  # hipMemcpyHostToDevice
+                raise TinyBatchError("hipMemcpy failed")
+            dw = self._w_dev
+        self._check(self.lib.tiny_batch_mpc_step_sim_async(self._h, window_advance, dw))
+
+    def mpc_run_sim(self, steps: int, window_advance: int = 0, w=None, record_x: bool = True):
+        """tiny_batch_mpc_run_sim: `steps` closed-loop MPC steps against the plant of set_plant with the disturbance w (steps, B, nx) or None.
+        Returns (u0_traj (steps, B, nu), x_traj (steps, B, nx) or None): row k of x_traj is the state after step k's plant step."""
+        n = max(int(steps), 0)
+        a = None
+        if w is not None:
+            a = _f32(w); assert a.shape == (n, self.B, self.nx), a.shape
+        u0 = np.zeros((n, self.B, self.nu), np.float32)
+        xt = np.zeros((n, self.B, self.nx), np.float32) if record_x else None
+        self._check(self.lib.tiny_batch_mpc_run_sim(self._h, int(steps), window_advance, None if a is None else _fp(a), _fp(u0), None if xt is None else _fp(xt)))
+        return u0, xt
 
     def get_x0(self):
         out = np.empty((self.B, self.nx), np.float32)

@@ -182,6 +182,38 @@ extern "C"
     int tiny_batch_mpc_run_traj(TinyBatch *tb, int steps, int window_advance, float *u0_traj_host);
     int tiny_batch_get_x0(TinyBatch *tb, float *x0 /*[B][nx]*/);
 
+    /* ---- closed loop against a separate plant (Monte-Carlo studies: one controller, perturbed plants, disturbances) ------
+     * The simulated plant of the closed-loop calls: x0 <- A*x0 + B*u.col(0) with these matrices instead of the model's Adyn / Bdyn (batch-shared or
+     * per-instance models alike).  Column-major; shared != 0: one A [nx*nx], one B [nx*nu]; else [batch][nx*nx], [batch][nx*nu].  The solver itself
+     * never reads them.  The product keeps the order of the plant step (Eigen's for Adyn*x0 + Bdyn*u.col(0): the column-major GEMV accumulator starting
+     * at +0 where rows and depth are both >= 8, the lazy product's order below that), in exact and fma arithmetic and under fp16 storage alike; x0 stays
+     * fp32.  A plant set on the handle is honoured by EVERY closed-loop call (tiny_batch_mpc_step_async and tiny_batch_mpc_run_* included); with none
+     * set those calls are what they were.  set_plant and clear_plant drop a captured closed-loop graph; the plant is independent of
+     * tiny_batch_set_models / tiny_batch_clear_models. */
+    int tiny_batch_set_plant(TinyBatch *tb, const float *A, const float *Bm, int shared);
+    int tiny_batch_clear_plant(TinyBatch *tb);          /* back to the model's own Adyn / Bdyn; releases the device copies */
+    int tiny_batch_plant_mode(TinyBatch *tb);           /* 0 the model, 1 one shared plant, 2 one plant per instance */
+    /* mpc_step / mpc_run with a disturbance and the state trajectory:
+     *   x0 <- (A*x0 + B*u.col(0)) + w_k      w: DEVICE [steps][batch][nx] (step form: [batch][nx]); NULL = no addition at all
+     *   d_x_traj: DEVICE [steps][batch][nx], row k = x0 after step k's plant step (the state the next solve starts from); may be NULL
+     *   d_u0_traj as in tiny_batch_mpc_run_traj_async; may be NULL
+     * "+ w_k" is one separately rounded fp32 add per state behind the product.  NULL means the add is not executed: NULL and an array of +0 differ in
+     * the sign of a zero result ((-0) + (+0) = +0), an array of -0 does not.
+     * tiny_batch_mpc_step_async equals ..._step_sim_async(.., NULL), tiny_batch_mpc_run_* equals ..._run_sim_async with d_w = d_x_traj = NULL.
+     * A run is "simulated" when a plant is set or d_w / d_x_traj is passed.  On the 16-lane kernel a simulated run of steps > 1 (fp32 storage, shared
+     * bounds) stays ONE launch; the matrix-core kernel hands a simulated run over to the 16-lane kernel (tiny_batch_closed_loop_kernel_name() says
+     * so while a plant is set: the name reflects the handle, so for a run that passes d_w or d_x_traj WITHOUT a plant it still names the kernel of
+     * the nominal run, although that run is handed over as well); the quad-lane kernel and every other family replay solve + plant kernel per
+     * step from a captured hipGraph, which bakes the rows of step k in (the graph is re-captured when d_w or d_x_traj changes).
+     * Out of scope: the fp64 library (tinympc_batch64.h), the wrapper and native-name libraries, a _device form of set_plant, and on-chip
+     * simulated loops of the quad-lane and tile16 kernels. */
+    int tiny_batch_mpc_step_sim_async(TinyBatch *tb, int window_advance, const float *d_w);
+    int tiny_batch_mpc_run_sim_async(TinyBatch *tb, int steps, int window_advance, const float *d_w, float *d_u0_traj, float *d_x_traj);
+    /* blocking, HOST arrays (any of the three may be NULL); device buffers on the handle's own device, as tiny_batch_mpc_run_traj.  The handle keeps
+     * them between calls and re-allocates one only when its size (steps) changes, so a loop of equal calls on a replayed kernel replays ONE
+     * captured graph; alternating step counts re-captures it. */
+    int tiny_batch_mpc_run_sim(TinyBatch *tb, int steps, int window_advance, const float *w, float *u0_traj, float *x_traj);
+
     /* ---- measurement ------------------------------------------------------------------------- */
     /* When enabled, every solve records hipEvents around its kernel launches on the stream. */
     int tiny_batch_enable_timing(TinyBatch *tb, int on);
