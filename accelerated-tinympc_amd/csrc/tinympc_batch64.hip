@@ -12,6 +12,9 @@
 // halving tree for coefficient-evaluated ones, packet tree + s0 + s1 for vectorised reductions.  Results are bitwise equal
 // to the compiled reference (tests/test_parity_gpu.py: golden vectors of the as-shipped fp64 N = 10 hovering run).
 // There is no CPU fallback.
+//
+// The file is compiled twice: as itself, and under TINY_F64SIM_UNIT as tinympc_batch64_sim.hip (the closed loop against a separate plant: the SIM
+// instantiations of the sixteen-lane kernel, the simulated plant kernel and their launchers; none of the C-ABI).
 #include "../../include/tinympc_batch64.h"
 
 #include <hip/hip_runtime.h>
@@ -113,8 +116,49 @@ struct Mpc64
     int *xref_start;                           // [batch], read at live-in and written back after the last solve
     double *u0_traj;                           // [mpc_steps][batch][nu] or NULL; the kernel stores every step but the last
 };
+} // namespace
+
+// What the two translation units of the fp64 library share — this file, and this file again as tinympc_batch64_sim.hip (TINY_F64SIM_UNIT: the SIM
+// instantiations of the sixteen-lane kernel, the simulated plant kernel and their launchers).  Params64 and Mpc64 stay where they are: they are part
+// of the existing kernels' names, and the layout of this unit's code object moves with the names in it.  Both units compile the definitions above, so
+// the launcher takes the two as untyped pointers.
+namespace tinympc64
+{
+// closed loop against a separate plant (tiny_batch64_set_plant, tiny_batch64_mpc_run_sim): the further argument of the SIM instantiations
+struct Sim64
+{
+    const double *plant;  // the rows of [A_p | B_p] packed for the sixteen lanes, entry (k, r) at k * 16 + r (input lanes hold zeros); NULL: the model's rows
+    size_t plant_stride;  // doubles from one instance's table to the next, (nx + nu) * 16; 0: one table for the batch
+    const double *w;      // [mpc_steps][batch][nx] or NULL: no addition
+    double *x_traj;       // [mpc_steps][batch][nx] or NULL; the kernel stores every step but the last
+};
+// arguments of plant64_sim_kernel: the plant step of one MPC step on the workspace's x.col(0) / u.col(0)
+struct PlantSim64
+{
+    double *X;
+    const double *U, *A, *B;     // A, B column-major: the plant's, or the model's Adyn / Bdyn
+    size_t stride_a, stride_b;   // doubles from one instance's matrix to the next; 0: one pair for the batch
+    int batch, bpad;
+    const double *w;             // this step's [batch][nx] row or NULL: no addition
+    double *x_traj, *u0_row;     // this step's [batch][nx] / [batch][nu] rows or NULL: not recorded
+    int *start;                  // the window starts or NULL
+    int window_advance;
+};
+// mpc_steps > 1 solves of the SIM instantiation for (nx, nu, N) in one launch on the null stream; hipErrorInvalidValue where there is none
+hipError_t launch_rows64_sim(int nx, int nu, int N, const void *params /*Params64*/, const double *gains, const void *mpc /*Mpc64*/, const Sim64 &S);
+hipError_t launch_plant64_sim(int nx, int nu, const PlantSim64 &a);
+} // namespace tinympc64
+
+namespace
+{
+using namespace tinympc64;
+
 __device__ __forceinline__ Mpc64 loop_args() { return Mpc64{}; }
 __device__ __forceinline__ Mpc64 loop_args(const Mpc64 &l) { return l; }
+__device__ __forceinline__ Mpc64 loop_args(const Mpc64 &l, const Sim64 &) { return l; }
+__device__ __forceinline__ Sim64 sim_args(const Mpc64 &, const Sim64 &s) { return s; }
+template <class... T>
+__device__ __forceinline__ Sim64 sim_args(const T &...) { return Sim64{}; }
 
 template <int NX, int NU>
 __global__ __launch_bounds__(WAVE64) void admm_f64_kernel(const Params64 P)
@@ -358,10 +402,33 @@ __device__ __forceinline__ double lazy_sum(const double (&t)[CNT])
     else return novec_sum(t);
 }
 
+// One row of the plant step A*x + B*u on the sixteen lanes: Ar / Br are this lane's row of A and B, x and u the lane's element of [x ; u].  The order is
+// plant64_step's: a product whose rows and depth are both >= 8 is the GEMV accumulator from +0, anything smaller the lazy product's sequential sum.
+template <int NX, int NU>
+__device__ __forceinline__ double plant_row(const double (&Ar)[NX], const double (&Br)[NU], double x, double u)
+{
+    double t[NX], t2[NU];
+    row_products<0, NX>(t, x, Ar);
+    double ax;
+    if constexpr (NX >= 8)
+    {
+        double c = 0.0;
+#pragma unroll
+        for (int j = 0; j < NX; j++) c = t[j] + c;
+        ax = c * 1.0 + 0.0;
+    }
+    else ax = lazy_sum<NX>(t);
+    row_products<NX, NU>(t2, u, Br);
+    return ax + lazy_sum<NX>(t2);
+}
+
 // problem classes of the fp64 library (the thread-per-instance kernels; any N).  nx and nu must each be <= 2 or even (the
 // reference's order for other sizes depends on alignment, see row_dot) and not both >= 8 (Eigen's GEMV kernel is not restated here)
 #define TINY_FOR_EACH_F64DIMS(X) X(12, 4) X(4, 1) X(8, 4) X(12, 2) X(4, 2) X(4, 4) X(16, 4)
 #define TINY_FOR_EACH_F64ROWS(X) X(12, 4, 10) X(12, 4, 30) X(12, 4, 20) X(4, 1, 10) X(8, 4, 9)
+// classes of the sixteen-lane kernel with a runtime horizon (any N <= 64): the unrolled body has a capacity of 32 or 64 steps
+#define TINY_FOR_EACH_F64ROWS_RT(X) X(12, 4) X(4, 1) X(8, 4) X(12, 2) X(4, 2) X(4, 4)
+constexpr int F64ROWS_RT_MAX_N = 64;
 constexpr int F64_AHEAD = 4; // bounds are fetched this many steps ahead of their use
 
 // RT = false: the horizon is the template parameter N.  RT = true ("any horizon", round 3): N is the CAPACITY of the unrolled body
@@ -372,11 +439,18 @@ constexpr int F64_AHEAD = 4; // bounds are fetched this many steps ahead of thei
 // MPC = true (instantiated separately, so that the one-solve kernels keep their code): the examples' closed loop on chip.  L.mpc_steps times
 // {y = g = 0; tiny_solve; x.col(0) = Adyn x.col(0) + Bdyn u.col(0); start += window_advance} with the whole workspace staying in registers / LDS
 // between two solves; the plant step after the last solve is the host's (plant64_run_kernel).  Only where [p ; d] is held in registers.
+//
+// SIM = true (with MPC; instantiated in tinympc_batch64_sim.hip): the plant step between two solves takes the plant's own rows (S.plant: one table or
+// one per instance; NULL the model's), adds the disturbance row with one separately rounded add and stores the state trajectory.  The flag is the
+// second trailing argument, a Sim64 behind the Mpc64 (not a template parameter of its own: the existing instantiations keep their names).
 template <int NX, int NU, int N, bool RT = false, bool MPC = false, class... LOOP>
 __global__ __launch_bounds__(WAVE64, (N <= 12 ? 2 : 1)) void admm_f64_rows_kernel(const Params64 P, const double *__restrict__ gains, const LOOP... loop)
 {
-    static_assert(sizeof...(LOOP) == (MPC ? 1 : 0), "the closed-loop instantiations take one further argument, an Mpc64; the one-solve kernels none");
+    constexpr bool SIM = sizeof...(LOOP) == 2;
+    static_assert(sizeof...(LOOP) == (MPC ? (SIM ? 2 : 1) : 0), "the closed-loop instantiations take one further argument, an Mpc64, the simulated ones a Sim64 behind it; the one-solve kernels none");
+    static_assert(!SIM || MPC, "the simulated loop is the on-chip loop's");
     [[maybe_unused]] const Mpc64 L = loop_args(loop...);
+    [[maybe_unused]] const Sim64 S = sim_args(loop...);
     static_assert(!MPC || !(RT && N > 32), "the on-chip loop takes the workspace's d from the registers of [p ; d]");
     static_assert(NX + NU <= 16 && !(NX >= 8 && NU >= 8), "16-lane mapping; both dims >= 8 would take Eigen's GEMV kernel");
     static_assert(!RT || N > 20, "the runtime-horizon variant indexes the slack by the horizon: it keeps it in LDS");
@@ -590,18 +664,44 @@ next_solve: // (a label, not a loop around the solve: the one-solve instantiatio
         const double acc = is_x ? lazy_sum<NX>(t) : lazy_sum<NU>(t);
         const double u0 = -acc - C_(0); // [. ; u_0] of the solve that just finished: step 0 of the forward recursion (admm.cpp:31)
         if (L.u0_traj && valid && is_u) L.u0_traj[((size_t)ms * P.batch + inst) * NU + row] = u0;
-        // x.col(0) = Adyn * x.col(0) + Bdyn * u.col(0) in plant64_kernel's order: rows and depth >= 8 is the GEMV accumulator from +0
-        double ax;
-        if constexpr (NX >= 8)
+        if constexpr (SIM)
         {
-            double c = 0.0;
+            // x.col(0) = (A_p * x.col(0) + B_p * u.col(0)) + w: the products and sums below with the plant's rows, then one separately rounded add.
+            // The lane offsets are remade here from `inst`, opaque to the compiler (as the gains and the bounds: it otherwise carries the 64-bit
+            // lane addresses through every iteration loop); an out-of-range row reads the last instance's and stores nothing.
+            int ia = inst;
+            asm volatile("" : "+v"(ia));
+            ia = valid ? ia : P.batch - 1;
+            if (S.plant)
+            {
+                const double *const pl = S.plant + ((size_t)ia * S.plant_stride + r16);
+                double Ar[NX], Br[NU]; // transient: this lane's row of [A_p | B_p]
 #pragma unroll
-            for (int j = 0; j < NX; j++) c = t[j] + c;
-            ax = c * 1.0 + 0.0;
+                for (int k = 0; k < NX; k++) Ar[k] = pl[k * 16];
+#pragma unroll
+                for (int m = 0; m < NU; m++) Br[m] = pl[(NX + m) * 16];
+                x0 = plant_row<NX, NU>(Ar, Br, x0, u0);
+            }
+            else x0 = plant_row<NX, NU>(M1, M2, x0, u0);
+            const size_t xo = ((size_t)ms * P.batch + ia) * NX + (is_x ? r16 : 0);
+            if (S.w && is_x) x0 = x0 + S.w[xo];
+            if (S.x_traj && valid && is_x) S.x_traj[xo] = x0;
         }
-        else ax = lazy_sum<NX>(t);
-        row_products<NX, NU>(t2, u0, M2);
-        x0 = ax + lazy_sum<NX>(t2); // (x rows; the other lanes' value is never read as a state)
+        else
+        {
+            // x.col(0) = Adyn * x.col(0) + Bdyn * u.col(0) in plant64_kernel's order: rows and depth >= 8 is the GEMV accumulator from +0
+            double ax;
+            if constexpr (NX >= 8)
+            {
+                double c = 0.0;
+#pragma unroll
+                for (int j = 0; j < NX; j++) c = t[j] + c;
+                ax = c * 1.0 + 0.0;
+            }
+            else ax = lazy_sum<NX>(t);
+            row_products<NX, NU>(t2, u0, M2);
+            x0 = ax + lazy_sum<NX>(t2); // (x rows; the other lanes' value is never read as a state)
+        }
         if (window) wstart += L.window_advance;
         // the gains through an offset the compiler cannot see through (as the bounds above): otherwise it keeps Q and the NX registers of
         // Pinf's row from live-in alive through every solve instead of loading them again here
@@ -859,6 +959,7 @@ __global__ __launch_bounds__(WAVE64) void admm_f64_step_kernel(const Params64 P,
     }
 }
 
+#ifndef TINY_F64SIM_UNIT // (not templates: the unit of the simulated loop would emit them a second time)
 // host layout [cnt][steps][dim] (cnt = 1: shared, stored once with stride 1)  <->  device [steps][dim][stride]
 __global__ void pack64_kernel(const double *__restrict__ src, double *__restrict__ dst, int nb, int steps, int dim, int stride, int step0, int nsteps)
 {
@@ -882,6 +983,7 @@ __global__ void unpack64_kernel(const double *__restrict__ src, double *__restri
         dst[((long long)b * steps + s) * dim + row] = src[((long long)s * dim + row) * stride + b];
     }
 }
+#endif
 
 // Plant step of the examples' closed loop (quadrotor_hovering.cpp:110-111): x.col(0) <- Adyn * x.col(0) + Bdyn * u.col(0), in
 // Eigen's order for that expression over tiny_VectorNx: a product whose rows and depth are both >= 8 runs through the
@@ -943,6 +1045,98 @@ __global__ void plant64_run_kernel(double *__restrict__ X, const double *__restr
     plant64_step<NX, NU>(X, u, mats, b, bpad);
     if (start) start[b] += window_advance;
 }
+
+#ifdef TINY_F64SIM_UNIT
+// ---------------------------------------------------------------------------------------------------------------------
+// The simulated closed loop (tiny_batch64_set_plant, tiny_batch64_mpc_run_sim), compiled as tinympc_batch64_sim.hip: the SIM instantiations of the
+// sixteen-lane kernel, the plant kernel of the launch sequence and of a run's last step, and their launchers — a translation unit of its own, so
+// that every kernel of this file keeps its code.
+// ---------------------------------------------------------------------------------------------------------------------
+// plant64_run_kernel against a separate plant: x.col(0) <- (A_p * x.col(0) + B_p * u.col(0)) + w in plant64_step's order, then one separately
+// rounded add (none without w).  The matrices are the plant's (one pair, or instance b's at + b * stride) or the model's; it records u.col(0) and
+// x.col(0) in this step's rows of the trajectories and slides the window, each where asked to.
+template <int NX, int NU>
+__global__ void plant64_sim_kernel(const PlantSim64 a)
+{
+    static_assert(!(NX >= 8 && NU >= 8), "Bdyn*u would take the GEMV kernel too");
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= a.batch) return;
+    const double *const A = a.A + (size_t)b * a.stride_a, *const Bm = a.B + (size_t)b * a.stride_b;
+    double u[NU], x[NX], xn[NX];
+#pragma unroll
+    for (int j = 0; j < NU; j++) u[j] = a.U[(size_t)j * a.bpad + b];
+    if (a.u0_row)
+    {
+#pragma unroll
+        for (int j = 0; j < NU; j++) a.u0_row[(size_t)b * NU + j] = u[j];
+    }
+#pragma unroll
+    for (int j = 0; j < NX; j++) x[j] = a.X[(size_t)j * a.bpad + b];
+#pragma unroll
+    for (int i = 0; i < NX; i++)
+    {
+        double ax;
+        if constexpr (NX >= 8)
+        {
+            double c = 0.0;
+#pragma unroll
+            for (int j = 0; j < NX; j++) c = A[j * NX + i] * x[j] + c;
+            ax = c * 1.0 + 0.0;
+        }
+        else ax = row_dot<NX, NX>(A, i, x);
+        xn[i] = ax + row_dot<NX, NU>(Bm, i, u);
+        if (a.w) xn[i] = xn[i] + a.w[(size_t)b * NX + i];
+    }
+#pragma unroll
+    for (int i = 0; i < NX; i++)
+    {
+        a.X[(size_t)i * a.bpad + b] = xn[i];
+        if (a.x_traj) a.x_traj[(size_t)b * NX + i] = xn[i];
+    }
+    if (a.start) a.start[b] += a.window_advance;
+}
+
+} // namespace
+
+namespace tinympc64
+{
+hipError_t launch_plant64_sim(int nx, int nu, const PlantSim64 &a)
+{
+#define TINY_F64_PLANT_SIM(NX, NU)                                                                           \
+    if (nx == NX && nu == NU)                                                                                \
+    {                                                                                                        \
+        hipLaunchKernelGGL((plant64_sim_kernel<NX, NU>), dim3((a.batch + 127) / 128), dim3(128), 0, 0, a);   \
+        return hipGetLastError();                                                                            \
+    }
+    TINY_FOR_EACH_F64DIMS(TINY_F64_PLANT_SIM)
+    return hipErrorInvalidValue;
+}
+
+// a SIM instantiation wherever there is an MPC one: the unrolled horizons and the capacity-32 body of every sixteen-lane class
+hipError_t launch_rows64_sim(int nx, int nu, int N, const void *params, const double *gains, const void *mpc, const Sim64 &S)
+{
+    const Params64 &P = *static_cast<const Params64 *>(params);
+    const Mpc64 &L = *static_cast<const Mpc64 *>(mpc);
+    if (L.mpc_steps <= 1 || P.max_iter < 1) return hipErrorInvalidValue;
+    const int nrow_blocks = (P.batch + 3) / 4;
+#define TINY_F64ROWS_SIM_LAUNCH(NX, NU, NN)                                                                                                        \
+    if (nx == NX && nu == NU && N == NN)                                                                                                           \
+    {                                                                                                                                              \
+        hipLaunchKernelGGL((admm_f64_rows_kernel<NX, NU, NN, false, true, Mpc64, Sim64>), dim3(nrow_blocks), dim3(WAVE64), 0, 0, P, gains, L, S); \
+        return hipGetLastError();                                                                                                                  \
+    }
+    TINY_FOR_EACH_F64ROWS(TINY_F64ROWS_SIM_LAUNCH)
+#define TINY_F64ROWS_RT_SIM_LAUNCH(NX, NU)                                                                                                         \
+    if (nx == NX && nu == NU && N >= 2 && N <= 32)                                                                                                 \
+    {                                                                                                                                              \
+        hipLaunchKernelGGL((admm_f64_rows_kernel<NX, NU, 32, true, true, Mpc64, Sim64>), dim3(nrow_blocks), dim3(WAVE64), 0, 0, P, gains, L, S); \
+        return hipGetLastError();                                                                                                                  \
+    }
+    TINY_FOR_EACH_F64ROWS_RT(TINY_F64ROWS_RT_SIM_LAUNCH)
+    return hipErrorInvalidValue;
+}
+} // namespace tinympc64
+#else // TINY_F64SIM_UNIT
 // a window reference as the per-instance array the one-solve kernels read: row i of instance b is table[min(start[b] + i, rows - 1)]
 __global__ void gather_window64_kernel(const double *__restrict__ table, const int *__restrict__ start, double *__restrict__ dst, int rows, int N, int nx,
                                        int batch, int bpad)
@@ -1005,6 +1199,12 @@ struct TinyBatch64
     int table_rows = 0;      // > 0: the reference is the window
     bool xwin_valid = false;
     size_t u0_traj_cap = 0;  // doubles
+    // the simulated plant of the closed-loop calls (tiny_batch64_set_plant): 0 the model's own Adyn / Bdyn, 1 one shared plant, 2 one per instance.
+    // Column-major copies for the plant kernel ([1 or batch][nx*nx], [1 or batch][nx*nu]) and, where nx + nu <= 16, the rows of [A | B] packed for the
+    // sixteen lanes ([1 or batch][(nx + nu) * 16]: Sim64).  sim_w / sim_x: the device copies of a call's w and x_traj; like u0_traj they grow only
+    int plant_mode = 0;
+    double *plant_A = nullptr, *plant_B = nullptr, *plant_rows = nullptr, *sim_w = nullptr, *sim_x = nullptr;
+    size_t sim_w_cap = 0, sim_x_cap = 0;
     std::vector<double> hm; // host copy of the packed matrices
     bool have_cache = false, have_dyn = false, have_settings = false, mats_dirty = true;
     double rho = 0, abs_pri_tol = 0, abs_dua_tol = 0;
@@ -1023,9 +1223,6 @@ size_t mat_off(const TinyBatch64 *tb, int which) // Kinf, Pinf, Quu_inv, AmBKt, 
     for (int k = 0; k < which; k++) o += sz[k];
     return o;
 }
-// classes of the sixteen-lane kernel with a runtime horizon (any N <= 64): the unrolled body has a capacity of 32 or 64 steps
-#define TINY_FOR_EACH_F64ROWS_RT(X) X(12, 4) X(4, 1) X(8, 4) X(12, 2) X(4, 2) X(4, 4)
-constexpr int F64ROWS_RT_MAX_N = 64;
 bool rows_unrolled(int nx, int nu, int N)
 {
 #define TINY_F64ROWS_CHECK(NX, NU, NN) \
@@ -1210,6 +1407,25 @@ int launch_solve64(TinyBatch64 *tb, const Params64 &P, const Mpc64 *L = nullptr)
     return 0;
 }
 
+// a device buffer kept on the handle between calls: re-allocated only when it has to grow
+int grow64(double **buf, size_t *cap, size_t need)
+{
+    if (need <= *cap) return 0;
+    (void)hipFree(*buf); *buf = nullptr; *cap = 0;
+    HIP64(hipMalloc((void **)buf, need * sizeof(double)));
+    *cap = need;
+    return 0;
+}
+// The plant step of one MPC step against the handle's plant (the model's matrices without one): d_w / d_x / d_u0 are this step's device rows or NULL
+int enqueue_plant_sim64(TinyBatch64 *tb, const double *d_w, double *d_x, double *d_u0, int *start, int adv)
+{
+    const bool per = tb->plant_mode == 2;
+    const double *A = tb->plant_mode ? tb->plant_A : tb->mats + mat_off(tb, 4), *Bm = tb->plant_mode ? tb->plant_B : tb->mats + mat_off(tb, 5);
+    const PlantSim64 a{tb->arr[TINY_ARR_X], tb->arr[TINY_ARR_U], A, Bm, per ? (size_t)tb->nx * tb->nx : 0, per ? (size_t)tb->nx * tb->nu : 0,
+                       tb->batch, tb->bpad, d_w, d_x, d_u0, start, adv};
+    HIP64(launch_plant64_sim(tb->nx, tb->nu, a));
+    return 0;
+}
 } // namespace
 
 extern "C"
@@ -1265,6 +1481,7 @@ void tiny_batch64_destroy(TinyBatch64 *tb)
     (void)hipFree(tb->mats); (void)hipFree(tb->res); (void)hipFree(tb->staging); (void)hipFree(tb->row_gains);
     (void)hipFree(tb->status); (void)hipFree(tb->iter); (void)hipFree(tb->n_unsolved);
     (void)hipFree(tb->table); (void)hipFree(tb->xwin); (void)hipFree(tb->u0_traj); (void)hipFree(tb->xref_start);
+    (void)hipFree(tb->plant_A); (void)hipFree(tb->plant_B); (void)hipFree(tb->plant_rows); (void)hipFree(tb->sim_w); (void)hipFree(tb->sim_x);
     delete tb;
 }
 
@@ -1367,13 +1584,27 @@ int tiny_batch64_solve(TinyBatch64 *tb)
     return n > 0 ? 1 : 0;
 }
 
-int tiny_batch64_mpc_step(TinyBatch64 *tb)
+// tiny_batch64_mpc_step / _mpc_step_sim: with no plant and no disturbance the launches tiny_batch64_mpc_step has always made.  (Defined here, where
+// tiny_batch64_mpc_step has been: the kernels of this unit are emitted in the order of their first launch in this file, and its code object with them.)
+static int mpc_step64(TinyBatch64 *tb, const double *w)
 {
     CHECK64(tb, "NULL handle");
     int rc = tiny_batch64_reset_dual_variables(tb); // quadrotor_hovering.cpp:100-101
     if (rc < 0) return rc;
     rc = tiny_batch64_solve(tb);                    // :104
     if (rc < 0) return rc;
+    if (tb->plant_mode || w)
+    {
+        const size_t row = (size_t)tb->batch * tb->nx;
+        if (w)
+        {
+            const int rg = grow64(&tb->sim_w, &tb->sim_w_cap, row);
+            if (rg < 0) return rg;
+            HIP64(hipMemcpy(tb->sim_w, w, row * sizeof(double), hipMemcpyHostToDevice));
+        }
+        const int rp = enqueue_plant_sim64(tb, w ? tb->sim_w : nullptr, nullptr, nullptr, nullptr, 0);
+        return rp < 0 ? rp : rc;
+    }
     const int nb = (tb->batch + 127) / 128;          // :110-111
 #define TINY_F64_PLANT(NX, NU)                                                                                                       \
     if (tb->nx == NX && tb->nu == NU)                                                                                                \
@@ -1381,6 +1612,63 @@ int tiny_batch64_mpc_step(TinyBatch64 *tb)
     TINY_FOR_EACH_F64DIMS(TINY_F64_PLANT)
     HIP64(hipGetLastError());
     return rc;
+}
+int tiny_batch64_mpc_step(TinyBatch64 *tb) { return mpc_step64(tb, nullptr); }
+int tiny_batch64_mpc_step_sim(TinyBatch64 *tb, const double *w) { return mpc_step64(tb, w); }
+
+int tiny_batch64_clear_plant(TinyBatch64 *tb)
+{
+    CHECK64(tb, "NULL handle");
+    if (!tb->plant_mode) return 0;
+    HIP64(hipSetDevice(tb->device));
+    HIP64(hipDeviceSynchronize()); // a plant kernel still reading the matrices may be in flight
+    for (double **p : {&tb->plant_A, &tb->plant_B, &tb->plant_rows})
+    {
+        (void)hipFree(*p);
+        *p = nullptr;
+    }
+    tb->plant_mode = 0;
+    return 0;
+}
+
+int tiny_batch64_set_plant(TinyBatch64 *tb, const double *A, const double *B, int shared)
+{
+    CHECK64(tb && A && B, "NULL argument");
+    HIP64(hipSetDevice(tb->device));
+    {
+        const int rc = tiny_batch64_clear_plant(tb); // releases the previous copies
+        if (rc < 0) return rc;
+    }
+    const size_t nx = tb->nx, nu = tb->nu, cnt = shared ? 1 : (size_t)tb->batch, rl = (nx + nu) * 16;
+    // the sixteen-lane kernel's form: entry (k, r) of [A | B] at k * 16 + r, lane r of a row reads 128 contiguous bytes per column with its row
+    std::vector<double> packed;
+    if (nx + nu <= 16)
+    {
+        packed.assign(cnt * rl, 0.0);
+        for (size_t c = 0; c < cnt; c++)
+            for (size_t r = 0; r < nx; r++)
+            {
+                for (size_t k = 0; k < nx; k++) packed[c * rl + k * 16 + r] = A[c * nx * nx + k * nx + r];
+                for (size_t m = 0; m < nu; m++) packed[c * rl + (nx + m) * 16 + r] = B[c * nx * nu + m * nx + r];
+            }
+    }
+    int rc = 0;
+    auto up = [&](double **dst, const double *src, size_t n) {
+        if (rc == 0 && hipMalloc((void **)dst, n * sizeof(double)) != hipSuccess) rc = fail64(TINY_BATCH_EHIP, "tiny_batch64_set_plant: device allocation failed");
+        if (rc == 0 && hipMemcpy(*dst, src, n * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) rc = fail64(TINY_BATCH_EHIP, "tiny_batch64_set_plant: hipMemcpy failed");
+    };
+    up(&tb->plant_A, A, cnt * nx * nx);
+    up(&tb->plant_B, B, cnt * nx * nu);
+    if (!packed.empty()) up(&tb->plant_rows, packed.data(), packed.size());
+    tb->plant_mode = shared ? 1 : 2;
+    if (rc) (void)tiny_batch64_clear_plant(tb);
+    return rc;
+}
+
+int tiny_batch64_plant_mode(TinyBatch64 *tb)
+{
+    CHECK64(tb, "NULL handle");
+    return tb->plant_mode;
 }
 
 int tiny_batch64_set_xref_window(TinyBatch64 *tb, const double *table, int rows, const int *start)
@@ -1414,7 +1702,7 @@ int tiny_batch64_get_xref_start(TinyBatch64 *tb, int *start)
     return 0;
 }
 
-int tiny_batch64_mpc_run_traj(TinyBatch64 *tb, int steps, int window_advance, double *u0_traj_host)
+int tiny_batch64_mpc_run_sim(TinyBatch64 *tb, int steps, int window_advance, const double *w_host, double *u0_traj_host, double *x_traj_host)
 {
     CHECK64(tb, "NULL handle");
     CHECK64(steps >= 1, "steps must be >= 1 (got %d)", steps);
@@ -1429,13 +1717,20 @@ int tiny_batch64_mpc_run_traj(TinyBatch64 *tb, int steps, int window_advance, do
         if (rc < 0) return rc;
     }
     const size_t row_len = (size_t)tb->batch * tb->nu, need = u0_traj_host ? (size_t)steps * row_len : 0;
-    if (need > tb->u0_traj_cap)
-    {
-        (void)hipFree(tb->u0_traj); tb->u0_traj = nullptr; tb->u0_traj_cap = 0;
-        HIP64(hipMalloc((void **)&tb->u0_traj, need * sizeof(double)));
-        tb->u0_traj_cap = need;
-    }
+    // a run is simulated when a plant is set or the call passes a disturbance or asks for the state trajectory; any other run enqueues what it always has
+    const bool sim = tb->plant_mode != 0 || w_host != nullptr || x_traj_host != nullptr;
+    const size_t xrow = (size_t)tb->batch * tb->nx, need_w = w_host ? (size_t)steps * xrow : 0, need_x = x_traj_host ? (size_t)steps * xrow : 0;
+    for (const int rg : {grow64(&tb->u0_traj, &tb->u0_traj_cap, need), grow64(&tb->sim_w, &tb->sim_w_cap, need_w), grow64(&tb->sim_x, &tb->sim_x_cap, need_x)})
+        if (rg < 0) return rg;
+    if (w_host) HIP64(hipMemcpy(tb->sim_w, w_host, need_w * sizeof(double), hipMemcpyHostToDevice));
     double *const traj = u0_traj_host ? tb->u0_traj : nullptr;
+    const double *const d_w = w_host ? tb->sim_w : nullptr;
+    double *const d_x = x_traj_host ? tb->sim_x : nullptr;
+    // step k's plant step against the handle's plant, with its rows of w and the two trajectories
+    auto plant_sim = [&](int k) {
+        return enqueue_plant_sim64(tb, d_w ? d_w + (size_t)k * xrow : nullptr, d_x ? d_x + (size_t)k * xrow : nullptr, traj ? traj + (size_t)k * row_len : nullptr,
+                                   window ? tb->xref_start : nullptr, adv);
+    };
     int *const start = window ? tb->xref_start : nullptr;
     const int nb = (tb->batch + 127) / 128;
 #define TINY_F64_PLANT_RUN(NX, NU)                                                                                                            \
@@ -1448,11 +1743,30 @@ int tiny_batch64_mpc_run_traj(TinyBatch64 *tb, int steps, int window_advance, do
         const Mpc64 L{steps, adv, tb->table_rows, tb->table, tb->xref_start, traj};
         HIP64(hipMemsetAsync(tb->n_unsolved, 0, sizeof(int), 0));
         // y and g of the workspace are zero from the first solve on: the kernel starts from that without reading them
-        const int rc = launch_solve64(tb, P, &L);
-        if (rc < 0) return rc;
         const int k = steps - 1;
-        TINY_FOR_EACH_F64DIMS(TINY_F64_PLANT_RUN)
-        HIP64(hipGetLastError());
+        if (sim)
+        {
+            // (one step never reaches the kernel's plant step: the MPC instantiation serves it)
+            if (steps > 1)
+            {
+                const Sim64 S{tb->plant_mode ? tb->plant_rows : nullptr, tb->plant_mode == 2 ? (size_t)(tb->nx + tb->nu) * 16 : 0, d_w, d_x};
+                HIP64(launch_rows64_sim(tb->nx, tb->nu, tb->N, &P, tb->row_gains, &L, S));
+            }
+            else
+            {
+                const int rc = launch_solve64(tb, P, &L);
+                if (rc < 0) return rc;
+            }
+            const int rc = plant_sim(k); // the last plant step is the host's: the same plant, its own rows of w and x_traj
+            if (rc < 0) return rc;
+        }
+        else
+        {
+            const int rc = launch_solve64(tb, P, &L);
+            if (rc < 0) return rc;
+            TINY_FOR_EACH_F64DIMS(TINY_F64_PLANT_RUN)
+            HIP64(hipGetLastError());
+        }
     }
     else
     {
@@ -1468,8 +1782,16 @@ int tiny_batch64_mpc_run_traj(TinyBatch64 *tb, int steps, int window_advance, do
             HIP64(hipMemsetAsync(tb->n_unsolved, 0, sizeof(int), 0));
             const int rc = launch_solve64(tb, P);
             if (rc < 0) return rc;
-            TINY_FOR_EACH_F64DIMS(TINY_F64_PLANT_RUN)
-            HIP64(hipGetLastError());
+            if (sim)
+            {
+                const int rp = plant_sim(k);
+                if (rp < 0) return rp;
+            }
+            else
+            {
+                TINY_FOR_EACH_F64DIMS(TINY_F64_PLANT_RUN)
+                HIP64(hipGetLastError());
+            }
             if (adv) tb->xwin_valid = false;
         }
     }
@@ -1477,10 +1799,15 @@ int tiny_batch64_mpc_run_traj(TinyBatch64 *tb, int steps, int window_advance, do
     int n = 0;
     HIP64(hipMemcpy(&n, tb->n_unsolved, sizeof(int), hipMemcpyDeviceToHost)); // the only host synchronisation of the run
     if (u0_traj_host) HIP64(hipMemcpy(u0_traj_host, tb->u0_traj, need * sizeof(double), hipMemcpyDeviceToHost));
+    if (x_traj_host) HIP64(hipMemcpy(x_traj_host, tb->sim_x, need_x * sizeof(double), hipMemcpyDeviceToHost));
     return n > 0 ? 1 : 0;
 }
 
-int tiny_batch64_mpc_run(TinyBatch64 *tb, int steps, int window_advance) { return tiny_batch64_mpc_run_traj(tb, steps, window_advance, nullptr); }
+int tiny_batch64_mpc_run_traj(TinyBatch64 *tb, int steps, int window_advance, double *u0_traj_host)
+{
+    return tiny_batch64_mpc_run_sim(tb, steps, window_advance, nullptr, u0_traj_host, nullptr);
+}
+int tiny_batch64_mpc_run(TinyBatch64 *tb, int steps, int window_advance) { return tiny_batch64_mpc_run_sim(tb, steps, window_advance, nullptr, nullptr, nullptr); }
 
 int tiny_batch64_get_first_columns(TinyBatch64 *tb, double *x0, double *u0)
 {
@@ -1526,7 +1853,8 @@ const char *tiny_batch64_closed_loop_kernel_name(TinyBatch64 *tb)
     if (!tb) return "";
     const char *solve = tiny_batch64_kernel_name(tb);
     if (!onchip64(tb)) return solve;
-    snprintf(nm, sizeof nm, "%.*s,mpc>", (int)strlen(solve) - 1, solve); // rows64<12,4,10> -> rows64<12,4,10,mpc>
+    // rows64<12,4,10> -> rows64<12,4,10,mpc>; while a plant is set ,sim> (a run that passes w or x_traj without one is simulated too: only the call knows)
+    snprintf(nm, sizeof nm, "%.*s,%s>", (int)strlen(solve) - 1, solve, tb->plant_mode ? "sim" : "mpc");
     return nm;
 }
 
@@ -1592,3 +1920,4 @@ int tiny_batch64_set_status(TinyBatch64 *tb, const int *iter, const int *status,
 const char *tiny_batch64_last_error(void) { return g_err64.c_str(); }
 
 } // extern "C"
+#endif // TINY_F64SIM_UNIT

@@ -111,6 +111,8 @@ def load_library(build_if_missing: bool = False) -> C.CDLL:
         "tiny_batch64_update_linear_cost": [P], "tiny_batch64_backward_pass_grad": [P], "tiny_batch64_termination_condition": [P, I],
         "tiny_batch64_set_xref_window": [P, D, C.c_int, I], "tiny_batch64_get_xref_start": [P, I],
         "tiny_batch64_mpc_run": [P, C.c_int, C.c_int], "tiny_batch64_mpc_run_traj": [P, C.c_int, C.c_int, D],
+        "tiny_batch64_set_plant": [P, D, D, C.c_int], "tiny_batch64_clear_plant": [P], "tiny_batch64_plant_mode": [P],
+        "tiny_batch64_mpc_step_sim": [P, D], "tiny_batch64_mpc_run_sim": [P, C.c_int, C.c_int, D, D, D],
     }
     for name, args in sig64.items():
         fn = getattr(lib, name)
@@ -716,6 +718,49 @@ class TinyBatchSolver64:
         return out
 
     def closed_loop_kernel_name(self) -> str: return self.lib.tiny_batch64_closed_loop_kernel_name(self._h).decode()
+
+    # -- the simulated plant of the closed-loop calls (tiny_batch64_set_plant) --------------------------
+    def set_plant(self, A, B):
+        """The plant the closed-loop calls simulate, in place of the model's Adyn / Bdyn: (nx, nx) / (nx, nu) for one plant shared by the batch,
+        (B, nx, nx) / (B, nx, nu) for one per instance (logical orientation).  The solver never reads it."""
+        a, b = np.asarray(A, np.float64), np.asarray(B, np.float64)
+        if a.ndim == 2:
+            assert a.shape == (self.nx, self.nx) and b.shape == (self.nx, self.nu), (a.shape, b.shape)
+            ca, cb, shared = np.ascontiguousarray(a.T).ravel(), np.ascontiguousarray(b.T).ravel(), 1
+        else:
+            assert a.shape == (self.B, self.nx, self.nx) and b.shape == (self.B, self.nx, self.nu), (a.shape, b.shape)
+            ca, cb, shared = _colmajor_batch(a, np.float64), _colmajor_batch(b, np.float64), 0
+        self._check(self.lib.tiny_batch64_set_plant(self._h, self._dp(ca), self._dp(cb), shared))
+
+    def clear_plant(self):
+        """Back to the model's own Adyn / Bdyn."""
+        self._check(self.lib.tiny_batch64_clear_plant(self._h))
+
+    def plant_mode(self) -> int:
+        """0 the model, 1 one shared plant, 2 one plant per instance"""
+        return self._check(self.lib.tiny_batch64_plant_mode(self._h))
+
+    def mpc_step_sim(self, w=None) -> int:
+        """mpc_step against the plant of set_plant (the model's without one): x.col(0) <- (A x.col(0) + B u.col(0)) + w with w (B, nx) or None
+        (no addition)."""
+        a = None
+        if w is not None:
+            a = np.ascontiguousarray(w, np.float64); assert a.shape == (self.B, self.nx), a.shape
+        return self._check(self.lib.tiny_batch64_mpc_step_sim(self._h, None if a is None else self._dp(a)))
+
+    def mpc_run_sim(self, steps: int, window_advance: int = 0, w=None, record_x: bool = True):
+        """`steps` closed-loop MPC steps against the plant of set_plant with the disturbance w (steps, B, nx) or None (one launch where
+        closed_loop_kernel_name() ends in ",sim>" or ",mpc>").  Returns (u0_traj (steps, B, nu), x_traj (steps, B, nx) or None): row k of x_traj
+        is x.col(0) after step k's plant step."""
+        n = max(int(steps), 0)
+        a = None
+        if w is not None:
+            a = np.ascontiguousarray(w, np.float64); assert a.shape == (n, self.B, self.nx), a.shape
+        u0 = np.zeros((n, self.B, self.nu), np.float64)
+        xt = np.zeros((n, self.B, self.nx), np.float64) if record_x else None
+        self._check(self.lib.tiny_batch64_mpc_run_sim(self._h, int(steps), int(window_advance), None if a is None else self._dp(a), self._dp(u0),
+                                                      None if xt is None else self._dp(xt)))
+        return u0, xt
 
     def first_columns(self):
         """(x.col(0), u.col(0)) as [B][nx], [B][nu]."""

@@ -13,7 +13,8 @@
  * reference's SSE2 Eigen build with 2-double packets; results are BITWISE equal to the compiled reference (all twelve
  * work arrays, the residuals, status, iter).
  *
- * Scope: tiny_solve, the six step functions, the examples' closed loop (one step, or a whole run in one launch with a sliding reference window) and the
+ * Scope: tiny_solve, the six step functions, the examples' closed loop (one step, or a whole run in one launch with a sliding reference window),
+ * the same loop against a separate plant with a disturbance per step (tiny_batch64_set_plant, tiny_batch64_mpc_run_sim) and the
  * wrapper-style accessors.  Problem classes with a compiled
  * instantiation: (nx, nu) = (12, 4), (4, 1), (8, 4), (12, 2), (4, 2), (4, 4), (16, 4), any horizon N (TINY_FOR_EACH_F64DIMS).
  * Two kernels with identical results: sixteen lanes per instance with the state on chip for the whole solve (nx + nu <= 16 and N <= 64: unrolled instantiations for the
@@ -92,6 +93,26 @@ extern "C"
     int tiny_batch64_mpc_run(TinyBatch64 *tb, int steps, int window_advance);
     int tiny_batch64_mpc_run_traj(TinyBatch64 *tb, int steps, int window_advance, double *u0_traj_host /*[steps][B][nu]*/);
     const char *tiny_batch64_closed_loop_kernel_name(TinyBatch64 *tb);
+
+    /* The closed loop against a plant that is not the model (the float library's tiny_batch_set_plant family, in double): one controller, one
+     * plant shared by the batch or one per instance, a disturbance per step, the state trajectory as an output.  A, B are column-major,
+     * [1 or batch][nx*nx] and [1 or batch][nx*nu] (`shared` != 0: one pair); the solver never reads them.  tiny_batch64_plant_mode: 0 the model's
+     * own Adyn / Bdyn, 1 one shared plant, 2 one plant per instance.  A plant set on the handle is honoured by EVERY closed-loop call
+     * (tiny_batch64_mpc_step, _mpc_run and _mpc_run_traj included); with none set those calls enqueue exactly what they did before.
+     * The plant step is x.col(0) <- (A_p * x.col(0) + B_p * u.col(0)) + w_k: the product in the plant update's order above, then ONE separately
+     * rounded addition; with w == NULL no addition is executed.  tiny_batch64_mpc_step_sim is tiny_batch64_mpc_step with this step's [batch][nx]
+     * disturbance; tiny_batch64_mpc_run_sim is tiny_batch64_mpc_run_traj (its return value and argument checks) with w [steps][batch][nx],
+     * u0_traj [steps][batch][nu] and x_traj [steps][batch][nx], each of which may be NULL: row k of x_traj is x.col(0) after step k's plant step.
+     * A run is simulated when a plant is set or w / x_traj is passed.  Where the loop is on chip a simulated run of steps > 1 is ONE launch of the
+     * ",sim" instantiation; elsewhere it is the launch sequence with the simulated plant kernel per step.  While a plant is set
+     * tiny_batch64_closed_loop_kernel_name carries ",sim" in place of ",mpc" ("rows64<12,4,10,sim>"); a run that only passes w / x_traj takes the
+     * same instantiation although the name, which knows the handle alone, says ",mpc". */
+    int tiny_batch64_set_plant(TinyBatch64 *tb, const double *A, const double *B, int shared);
+    int tiny_batch64_clear_plant(TinyBatch64 *tb);
+    int tiny_batch64_plant_mode(TinyBatch64 *tb);
+    int tiny_batch64_mpc_step_sim(TinyBatch64 *tb, const double *w /*[batch][nx] or NULL*/);
+    int tiny_batch64_mpc_run_sim(TinyBatch64 *tb, int steps, int window_advance, const double *w /*[steps][batch][nx] or NULL*/,
+                                 double *u0_traj /*[steps][batch][nu] or NULL*/, double *x_traj /*[steps][batch][nx] or NULL*/);
 
     /* Implementation: 0 = automatic (the second where (nx, nu, N) has an instantiation, else the first), 1 = one thread per
      * instance with the state in HBM (any N), 2 = sixteen lanes per instance with the state in registers for the whole solve
