@@ -17,9 +17,9 @@ CSRC = PKG / "csrc"
 LIB = PKG / "lib" / "libtinympc_hip.so"
 WRAPPER_LIB = PKG / "lib" / "libtinympc_wrapper.so"  # same-name twin of the reference's generated wrapper library
 WRAPPER64_LIB = PKG / "lib" / "libtinympc_wrapper64.so"  # the native names (tiny_solve, forward_pass, ...) for tinytype = double
-SOURCES = ["tinympc_batch.hip", "tinympc_batch64.hip", "tinympc_batch64_sim.hip", "admm_stream.hip", "admm_generic.hip", "admm_rowlane.hip", "admm_rowsim.hip", "admm_rowloop.hip", "admm_quadlane.hip", "admm_tile16.hip", "admm_tile16_pi.hip", "admm_wave.hip", "admm_waveres.hip", "admm_tile48.hip", "admm_steps.hip", "dispatch_order.hip", "riccati.cpp", "riccati_batch.hip"]
+SOURCES = ["tinympc_batch.hip", "tinympc_batch64.hip", "admm_f64_thread.hip", "admm_f64_rows.hip", "admm_f64_rowsim.hip", "admm_f64_plant.hip", "admm_stream.hip", "admm_generic.hip", "admm_rowlane.hip", "admm_rowsim.hip", "admm_rowloop.hip", "admm_quadlane.hip", "admm_tile16.hip", "admm_tile16_pi.hip", "admm_wave.hip", "admm_waveres.hip", "admm_tile48.hip", "admm_steps.hip", "dispatch_order.hip", "riccati.cpp", "riccati_batch.hip"]
 WRAPPER_SRCS = [CSRC / "wrapper_compat.cpp", CSRC / "admm_compat.cpp"]
-HEADERS = [CSRC / "tinympc_internal.h", CSRC / "eigen_orders.h", CSRC / "rowlane_math.h", CSRC / "tile_math.h", CSRC / "wave_math.h", CSRC / "dpp_ops_gen.h", PKG.parent / "include" / "tinympc_batch.h", PKG.parent / "include" / "tinympc_batch64.h"]
+HEADERS = [CSRC / "tinympc_internal.h", CSRC / "eigen_orders.h", CSRC / "rowlane_math.h", CSRC / "tile_math.h", CSRC / "wave_math.h", CSRC / "dpp_ops_gen.h", CSRC / "f64_internal.h", CSRC / "f64_math.h", PKG.parent / "include" / "tinympc_batch.h", PKG.parent / "include" / "tinympc_batch64.h"]
 # -ffp-contract=off : exact arithmetic must not fuse a*b+c; the fast paths call fma explicitly
 # -fno-slp-vectorize: hipcc otherwise pairs scalar fp32 adds into v_pk_add_f32 (+ v_mov to build the pairs), which on
 #                     gfx950 is slower than two plain v_add_f32 (measured, tools/micro/*.hip)
@@ -34,7 +34,7 @@ EXTRA_FLAGS = {"admm_tile16.hip": _T16_FLAGS, "admm_tile16_pi.hip": _T16_FLAGS,
                "admm_waveres.hip": os.environ.get("TINYMPC_WAVERES_FLAGS", "").split(),
                "admm_tile48.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"] + os.environ.get("TINYMPC_T48_FLAGS", "").split()}
 # translation units that #include another kernel source: rebuilt with it
-INCLUDED_SOURCES = {"admm_tile16_pi.hip": ["admm_tile16.hip"], "admm_rowsim.hip": ["admm_rowlane.hip"], "tinympc_batch64_sim.hip": ["tinympc_batch64.hip"]}
+INCLUDED_SOURCES = {"admm_tile16_pi.hip": ["admm_tile16.hip"], "admm_rowsim.hip": ["admm_rowlane.hip"], "admm_f64_rowsim.hip": ["admm_f64_rows.hip"]}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-slp-vectorize", "-fno-gpu-rdc"]
 
 
@@ -106,7 +106,7 @@ def device_asm(source: str) -> Path:
 # kernel family (the name tiny_batch_kernel_name() reports, up to the '<') -> the translation unit that holds its device code
 KERNEL_SOURCES = {"rowlane": "admm_rowlane.hip", "rowloop": "admm_rowloop.hip", "rowstream": "admm_steps.hip", "quadlane": "admm_quadlane.hip",
                   "tile16": "admm_tile16.hip", "tile48": "admm_tile48.hip", "waveres": "admm_waveres.hip", "wavestream": "admm_wave.hip",
-                  "stream": "admm_stream.hip", "generic": "admm_generic.hip", "rows64": "tinympc_batch64.hip", "thread64": "tinympc_batch64.hip"}
+                  "stream": "admm_stream.hip", "generic": "admm_generic.hip", "rows64": "admm_f64_rows.hip", "thread64": "admm_f64_thread.hip"}
 
 
 def _elf_sections(b: bytes, base: int = 0) -> dict:
@@ -160,8 +160,8 @@ def kernel_isa_sha(kernel_name: str) -> str | None:
     src = KERNEL_SOURCES.get(kernel_name.split("<", 1)[0])
     if src == "admm_tile16.hip" and kernel_name.endswith(",pi>"):
         src = "admm_tile16_pi.hip"  # the per-instance instantiations are a translation unit of their own
-    if src == "tinympc_batch64.hip" and kernel_name.endswith(",sim>"):
-        src = "tinympc_batch64_sim.hip"  # as are the simulated closed loop's
+    if src == "admm_f64_rows.hip" and kernel_name.endswith(",sim>"):
+        src = "admm_f64_rowsim.hip"  # as are the fp64 simulated closed loop's
     try:
         return device_isa_sha(src) if src else None
     except (OSError, AssertionError, KeyError):

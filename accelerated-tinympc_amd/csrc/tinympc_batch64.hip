@@ -1,23 +1,15 @@
 // tinympc_batch64.hip — the batched TinyMPC ADMM solver for `typedef double tinytype` (the reference as shipped,
-// src/tinympc/glob_opts.hpp:3): C-ABI of include/tinympc_batch64.h, device workspace, and the kernel.
+// src/tinympc/glob_opts.hpp:3): the handle, the device workspace, the choice of kernel and the C-ABI of include/tinympc_batch64.h.
 //
-// One thread per instance, state in HBM.  Every per-instance array is stored instance-minor — element (step, row) of
-// instance b at ((step * dim + row) * Bpad + b) — so that the 64 instances of a wavefront read and write 512 contiguous
-// bytes per element.  One launch runs all ADMM iterations; a converged instance stops storing exactly where the reference
-// returns (admm.cpp:135-137: before the v/z copy and the backward pass).
+// Host code, and three helper kernels that move arrays between the host's layout and the workspace's.  Every solve, step and plant kernel lives
+// in a translation unit of its own (admm_f64_thread.hip, admm_f64_rows.hip, admm_f64_rowsim.hip, admm_f64_plant.hip) and is reached through
+// the typed launchers of f64_internal.h, so nothing in this file — not the order of its functions, not a name in it — has a bearing on
+// their device code.
 //
-// Arithmetic: tiny_solve() of the reference (admm.cpp:15-152) statement by statement, every product and sum a separately
-// rounded fp64 operation (the library is built with -ffp-contract=off), summed in the order of the reference's SSE2 Eigen
-// build, whose packets hold PS = 2 doubles: sequential for packet-evaluated lazy products (result rows a multiple of 2),
-// halving tree for coefficient-evaluated ones, packet tree + s0 + s1 for vectorised reductions.  Results are bitwise equal
-// to the compiled reference (tests/test_parity_gpu.py: golden vectors of the as-shipped fp64 N = 10 hovering run).
+// Every per-instance array is stored instance-minor — element (step, row) of instance b at ((step * dim + row) * Bpad + b).  Results are
+// bitwise equal to the compiled reference (tests/test_parity_gpu.py: golden vectors of the as-shipped fp64 N = 10 hovering run).
 // There is no CPU fallback.
-//
-// The file is compiled twice: as itself, and under TINY_F64SIM_UNIT as tinympc_batch64_sim.hip (the closed loop against a separate plant: the SIM
-// instantiations of the sixteen-lane kernel, the simulated plant kernel and their launchers; none of the C-ABI).
-#include "../../include/tinympc_batch64.h"
-
-#include <hip/hip_runtime.h>
+#include "f64_internal.h"
 
 #include <cstdarg>
 #include <cstdio>
@@ -28,938 +20,8 @@
 
 namespace
 {
-
-constexpr int PS = 2; // doubles per SSE2 packet
-constexpr int WAVE64 = 64;
-constexpr int ST_SOLVED = 1, ST_UNSOLVED = 11; // admm.cpp:136, :114
-
-// ---- reductions in the reference's orders (Eigen 3.4.90: redux_novec_unroller, redux_vec_unroller, etor_product_packet_impl) ----
-template <int LO, int CNT, int NN>
-__device__ __forceinline__ double tree_sum(const double (&t)[NN])
-{
-    if constexpr (CNT == 1) return t[LO];
-    else
-    {
-        constexpr int H = CNT / 2;
-        return tree_sum<LO, H>(t) + tree_sum<LO + H, CNT - H>(t);
-    }
-}
-template <int PLO, int PCNT, int L, int NN>
-__device__ __forceinline__ double ptree_sum(const double (&t)[NN]) // lane L of the packets [PLO, PLO + PCNT)
-{
-    if constexpr (PCNT == 1) return t[PS * PLO + L];
-    else
-    {
-        constexpr int H = PCNT / 2;
-        return ptree_sum<PLO, H, L>(t) + ptree_sum<PLO + H, PCNT - H, L>(t);
-    }
-}
-template <int NN>
-__device__ __forceinline__ double seq_sum(const double (&t)[NN])
-{
-    double acc = t[0];
-#pragma unroll
-    for (int k = 1; k < NN; k++) acc = acc + t[k];
-    return acc;
-}
-template <int NN>
-__device__ __forceinline__ double novec_sum(const double (&t)[NN])
-{
-    if constexpr (NN == 1) return t[0];
-    else if constexpr (3 * NN - 1 <= 110) return tree_sum<0, NN>(t);
-    else return seq_sum(t);
-}
-template <int NN>
-__device__ __forceinline__ double vec_sum(const double (&t)[NN])
-{
-    static_assert(3 * NN - 1 <= 110 * PS, "beyond Eigen's unrolling limit the order is not restated");
-    if constexpr (NN < PS) return novec_sum(t);
-    else
-    {
-        constexpr int NPK = NN / PS;
-        double res = ptree_sum<0, NPK, 0>(t) + ptree_sum<0, NPK, 1>(t); // predux of a 2-double packet
-        if constexpr (NN % PS != 0) res = res + tree_sum<PS * NPK, NN - PS * NPK>(t);
-        return res;
-    }
-}
-// (row i of a column-major ROWS x COLS matrix) . xin, as a lazy product whose result has ROWS rows
-template <int ROWS, int COLS>
-__device__ __forceinline__ double row_dot(const double *M, int i, const double (&xin)[COLS])
-{
-    static_assert(ROWS <= PS || ROWS % PS == 0, "results with rows > 2 and odd: the reference's order depends on alignment");
-    double t[COLS];
-#pragma unroll
-    for (int k = 0; k < COLS; k++) t[k] = M[k * ROWS + i] * xin[k];
-    if constexpr (ROWS > 1 && ROWS % PS == 0) return seq_sum(t);
-    else if constexpr (ROWS == 1) return vec_sum(t);
-    else return novec_sum(t);
-}
-
-struct Params64
-{
-    int nx, nu, N, batch, bpad;
-    double rho, abs_pri_tol, abs_dua_tol;
-    int max_iter, check_termination, en_state_bound, en_input_bound;
-    double *arr[TINY_ARR_COUNT];
-    const double *xref, *xmin, *xmax, *umin, *umax; // [steps][dim][stride]; stride = bpad (per instance) or 1 (shared)
-    int xref_stride, xb_stride, ub_stride;
-    const double *mats; // Kinf | Pinf | Quu_inv | AmBKt | Adyn | Bdyn | Q, column-major
-    double *res;        // [4][bpad]
-    int *status, *iter, *n_unsolved;
-};
-// closed loop on chip: the further arguments of the MPC instantiations of the sixteen-lane kernel (a struct of their own: the one-solve kernels
-// keep their kernel arguments, and with them their code)
-struct Mpc64
-{
-    int mpc_steps, window_advance, table_rows; // table_rows > 0: the reference is a window into `table`
-    const double *table;                       // [table_rows][nx]
-    int *xref_start;                           // [batch], read at live-in and written back after the last solve
-    double *u0_traj;                           // [mpc_steps][batch][nu] or NULL; the kernel stores every step but the last
-};
-} // namespace
-
-// What the two translation units of the fp64 library share — this file, and this file again as tinympc_batch64_sim.hip (TINY_F64SIM_UNIT: the SIM
-// instantiations of the sixteen-lane kernel, the simulated plant kernel and their launchers).  Params64 and Mpc64 stay where they are: they are part
-// of the existing kernels' names, and the layout of this unit's code object moves with the names in it.  Both units compile the definitions above, so
-// the launcher takes the two as untyped pointers.
-namespace tinympc64
-{
-// closed loop against a separate plant (tiny_batch64_set_plant, tiny_batch64_mpc_run_sim): the further argument of the SIM instantiations
-struct Sim64
-{
-    const double *plant;  // the rows of [A_p | B_p] packed for the sixteen lanes, entry (k, r) at k * 16 + r (input lanes hold zeros); NULL: the model's rows
-    size_t plant_stride;  // doubles from one instance's table to the next, (nx + nu) * 16; 0: one table for the batch
-    const double *w;      // [mpc_steps][batch][nx] or NULL: no addition
-    double *x_traj;       // [mpc_steps][batch][nx] or NULL; the kernel stores every step but the last
-};
-// arguments of plant64_sim_kernel: the plant step of one MPC step on the workspace's x.col(0) / u.col(0)
-struct PlantSim64
-{
-    double *X;
-    const double *U, *A, *B;     // A, B column-major: the plant's, or the model's Adyn / Bdyn
-    size_t stride_a, stride_b;   // doubles from one instance's matrix to the next; 0: one pair for the batch
-    int batch, bpad;
-    const double *w;             // this step's [batch][nx] row or NULL: no addition
-    double *x_traj, *u0_row;     // this step's [batch][nx] / [batch][nu] rows or NULL: not recorded
-    int *start;                  // the window starts or NULL
-    int window_advance;
-};
-// mpc_steps > 1 solves of the SIM instantiation for (nx, nu, N) in one launch on the null stream; hipErrorInvalidValue where there is none
-hipError_t launch_rows64_sim(int nx, int nu, int N, const void *params /*Params64*/, const double *gains, const void *mpc /*Mpc64*/, const Sim64 &S);
-hipError_t launch_plant64_sim(int nx, int nu, const PlantSim64 &a);
-} // namespace tinympc64
-
-namespace
-{
 using namespace tinympc64;
 
-__device__ __forceinline__ Mpc64 loop_args() { return Mpc64{}; }
-__device__ __forceinline__ Mpc64 loop_args(const Mpc64 &l) { return l; }
-__device__ __forceinline__ Mpc64 loop_args(const Mpc64 &l, const Sim64 &) { return l; }
-__device__ __forceinline__ Sim64 sim_args(const Mpc64 &, const Sim64 &s) { return s; }
-template <class... T>
-__device__ __forceinline__ Sim64 sim_args(const T &...) { return Sim64{}; }
-
-template <int NX, int NU>
-__global__ __launch_bounds__(WAVE64) void admm_f64_kernel(const Params64 P)
-{
-    static_assert(!(NX >= 8 && NU >= 8), "both dims >= 8: Eigen switches to its GEMV kernel, not restated here");
-    constexpr int NMAT = NU * NX + NX * NX + NU * NU + NX * NX + NX * NX + NX * NU + NX;
-    __shared__ double mats[NMAT];
-    for (int e = threadIdx.x; e < NMAT; e += WAVE64) mats[e] = P.mats[e];
-    __syncthreads();
-    const double *K = mats, *Pinf = K + NU * NX, *Quu = Pinf + NX * NX, *Am = Quu + NU * NU, *A = Am + NX * NX, *Bm = A + NX * NX,
-                 *Q = Bm + NX * NU;
-
-    const int b = blockIdx.x * WAVE64 + threadIdx.x;
-    const bool valid = b < P.batch;
-    const int N = P.N;
-    const size_t bp = (size_t)P.bpad;
-    const double rho = P.rho;
-    auto at = [&](int id, int step, int row, int dim) -> double & { return P.arr[id][((size_t)step * dim + row) * bp + b]; };
-    auto in = [&](const double *base, int stride, int step, int row, int dim) {
-        return base[((size_t)step * dim + row) * (size_t)stride + (stride > 1 ? b : 0)];
-    };
-
-    if (P.max_iter <= 0) // tiny_solve only sets status and iter (admm.cpp:114-117,151)
-    {
-        if (valid)
-        {
-            P.status[b] = ST_UNSOLVED; P.iter[b] = 1;
-            atomicAdd(P.n_unsolved, 1);
-        }
-        return;
-    }
-    double x0[NX];
-#pragma unroll
-    for (int j = 0; j < NX; j++) x0[j] = valid ? at(TINY_ARR_X, 0, j, NX) : 0.0;
-    double r_ps = 0, r_pi = 0, r_ds = 0, r_di = 0;
-    if (valid)
-    {
-        r_ps = P.res[0 * bp + b]; r_pi = P.res[1 * bp + b]; r_ds = P.res[2 * bp + b]; r_di = P.res[3 * bp + b];
-    }
-    int st = ST_UNSOLVED, itn = 1; // admm.cpp:114-115
-    bool active = valid;
-    for (int it = 0; it < P.max_iter; ++it)
-    {
-        if (!__any(active)) break;
-        if (active)
-        {
-            itn = it + 1; // admm.cpp:120
-            // ---- forward_pass (:27-37) + update_slack (:45-61) + update_dual (:67-71) + update_linear_cost (:77-85) + residuals (:95-98) ----
-            double x[NX], pN[NX];
-#pragma unroll
-            for (int j = 0; j < NX; j++) x[j] = x0[j];
-            double pri_x = 0, dua_x = 0, pri_u = 0, dua_u = 0;
-            for (int i = 0; i < N; i++)
-            {
-                double u[NU], xn[NX];
-                if (i < N - 1)
-                {
-#pragma unroll
-                    for (int j = 0; j < NU; j++) u[j] = -row_dot<NU, NX>(K, j, x) - at(TINY_ARR_D, i, j, NU);           // :31
-#pragma unroll
-                    for (int j = 0; j < NX; j++) xn[j] = row_dot<NX, NX>(A, j, x) + row_dot<NX, NU>(Bm, j, u);           // :35
-#pragma unroll
-                    for (int j = 0; j < NU; j++)
-                    {
-                        const double y = at(TINY_ARR_Y, i, j, NU);
-                        double zn = u[j] + y;                                                                             // :47
-                        if (P.en_input_bound)                                                                             // :51-54
-                        {
-                            const double lo = in(P.umin, P.ub_stride, i, j, NU), hi = in(P.umax, P.ub_stride, i, j, NU);
-                            zn = (lo < zn) ? zn : lo;
-                            zn = (zn < hi) ? zn : hi;
-                        }
-                        const double yn = y + u[j] - zn;                                                                  // :69
-                        const double pu = fabs(u[j] - zn), du = fabs(at(TINY_ARR_Z, i, j, NU) - zn);                      // :97-98
-                        pri_u = (i == 0 && j == 0) ? pu : (pu > pri_u ? pu : pri_u);
-                        dua_u = (i == 0 && j == 0) ? du : (du > dua_u ? du : dua_u);
-                        at(TINY_ARR_U, i, j, NU) = u[j];
-                        at(TINY_ARR_ZNEW, i, j, NU) = zn;
-                        at(TINY_ARR_Y, i, j, NU) = yn;
-                        at(TINY_ARR_R, i, j, NU) = -rho * (zn - yn);                                                      // :80
-                    }
-                }
-#pragma unroll
-                for (int j = 0; j < NX; j++)
-                {
-                    const double g = at(TINY_ARR_G, i, j, NX);
-                    double vn = x[j] + g;                                                                                 // :48
-                    if (P.en_state_bound)                                                                                 // :57-60
-                    {
-                        const double lo = in(P.xmin, P.xb_stride, i, j, NX), hi = in(P.xmax, P.xb_stride, i, j, NX);
-                        vn = (lo < vn) ? vn : lo;
-                        vn = (vn < hi) ? vn : hi;
-                    }
-                    const double gn = g + x[j] - vn;                                                                      // :70
-                    const double px = fabs(x[j] - vn), dx = fabs(at(TINY_ARR_V, i, j, NX) - vn);                          // :95-96
-                    pri_x = (i == 0 && j == 0) ? px : (px > pri_x ? px : pri_x);
-                    dua_x = (i == 0 && j == 0) ? dx : (dx > dua_x ? dx : dua_x);
-                    at(TINY_ARR_X, i, j, NX) = x[j];
-                    at(TINY_ARR_VNEW, i, j, NX) = vn;
-                    at(TINY_ARR_G, i, j, NX) = gn;
-                    double q = -(in(P.xref, P.xref_stride, i, j, NX) * Q[j]);                                             // :81
-                    q = q - rho * (vn - gn);                                                                              // :82
-                    at(TINY_ARR_Q, i, j, NX) = q;
-                    if (i == N - 1) pN[j] = rho * (vn - gn); // second half of :84, applied below
-                }
-                if (i < N - 1)
-                {
-#pragma unroll
-                    for (int j = 0; j < NX; j++) x[j] = xn[j];
-                }
-            }
-            {
-                // p.col(N-1) = -(Xref.col(N-1)^T * Pinf)  (:83), then -= rho * (vnew - g)  (:84)
-                double xr[NX];
-#pragma unroll
-                for (int k = 0; k < NX; k++) xr[k] = in(P.xref, P.xref_stride, N - 1, k, NX);
-#pragma unroll
-                for (int j = 0; j < NX; j++)
-                {
-                    double t[NX];
-#pragma unroll
-                    for (int k = 0; k < NX; k++) t[k] = xr[k] * Pinf[j * NX + k];
-                    const double pt = -vec_sum(t);
-                    pN[j] = pt - pN[j];
-                    at(TINY_ARR_P, N - 1, j, NX) = pN[j];
-                }
-            }
-            // ---- termination_condition (:91-109) ----
-            bool conv = false;
-            if ((it + 1) % P.check_termination == 0)
-            {
-                r_ps = pri_x; r_ds = dua_x * rho; r_pi = pri_u; r_di = dua_u * rho;
-                conv = (r_ps < P.abs_pri_tol) && (r_pi < P.abs_pri_tol) && (r_ds < P.abs_dua_tol) && (r_di < P.abs_dua_tol);
-            }
-            if (conv)
-            {
-                st = ST_SOLVED; // :136, returns before the v/z copy and the backward pass
-                active = false;
-            }
-            else
-            {
-                // ---- v = vnew, z = znew (:141-142) + backward_pass_grad (:15-22) ----
-#pragma unroll
-                for (int j = 0; j < NX; j++) at(TINY_ARR_V, N - 1, j, NX) = at(TINY_ARR_VNEW, N - 1, j, NX);
-                double pn[NX];
-#pragma unroll
-                for (int j = 0; j < NX; j++) pn[j] = pN[j];
-                for (int i = N - 2; i >= 0; i--)
-                {
-                    double r[NU], tmp[NU], dn[NU], pi[NX];
-#pragma unroll
-                    for (int j = 0; j < NU; j++)
-                    {
-                        at(TINY_ARR_Z, i, j, NU) = at(TINY_ARR_ZNEW, i, j, NU);
-                        r[j] = at(TINY_ARR_R, i, j, NU);
-                    }
-#pragma unroll
-                    for (int j = 0; j < NU; j++) // Bdyn^T p_{i+1} + r_i: column j of Bdyn is contiguous -> vectorised reduction
-                    {
-                        double t[NX];
-#pragma unroll
-                        for (int k = 0; k < NX; k++) t[k] = Bm[j * NX + k] * pn[k];
-                        tmp[j] = vec_sum(t) + r[j];
-                    }
-#pragma unroll
-                    for (int j = 0; j < NU; j++) dn[j] = row_dot<NU, NU>(Quu, j, tmp);                                    // :19
-#pragma unroll
-                    for (int j = 0; j < NX; j++)
-                    {
-                        at(TINY_ARR_V, i, j, NX) = at(TINY_ARR_VNEW, i, j, NX);
-                        double t[NX], tk[NU];
-#pragma unroll
-                        for (int k = 0; k < NX; k++) t[k] = Am[k * NX + j] * pn[k];
-                        const double a = (NU == 1 && NX % PS == 0) ? seq_sum(t) : novec_sum(t);
-#pragma unroll
-                        for (int m = 0; m < NU; m++) tk[m] = K[j * NU + m] * r[m]; // Kinf^T r: column j of Kinf is contiguous
-                        pi[j] = at(TINY_ARR_Q, i, j, NX) + a - vec_sum(tk);                                               // :20
-                    }
-#pragma unroll
-                    for (int j = 0; j < NU; j++) at(TINY_ARR_D, i, j, NU) = dn[j];
-#pragma unroll
-                    for (int j = 0; j < NX; j++)
-                    {
-                        at(TINY_ARR_P, i, j, NX) = pi[j];
-                        pn[j] = pi[j];
-                    }
-                }
-            }
-        }
-    }
-    if (valid)
-    {
-        P.res[0 * bp + b] = r_ps; P.res[1 * bp + b] = r_pi; P.res[2 * bp + b] = r_ds; P.res[3 * bp + b] = r_di;
-        P.status[b] = st;
-        P.iter[b] = itn;
-        if (st != ST_SOLVED) atomicAdd(P.n_unsolved, 1);
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// admm_f64_rows_kernel<NX,NU,N>: the 16-lanes-per-instance mapping of admm_rowlane.hip in double.  Lane r of a DPP row owns
-// row r of the stacked vector [x ; u] (nx + nu <= 16), four instances per wavefront, the horizon unrolled, and the whole
-// loop-carried state of the solve in registers: per step a = [g;y], c = [-(Xref.*Q) ; d], pd = [p;d] of the last backward
-// sweep, b = [v;z], sn = [vnew;znew] (five doubles per lane and step; one wave per SIMD owns the 512-entry register file).
-// The workspace arrays are read once before the first and written once after the last iteration — the thread-per-instance
-// kernel above moves every array through HBM in every iteration (3.7 GB per iteration of 65 536 quadrotor instances).
-// A state element is broadcast within its row by two v_mov_b32_dpp row_newbcast (low and high word), products and sums
-// are separately rounded v_mul_f64 / v_add_f64 in the same orders as above.  Results are bitwise equal to the
-// thread-per-instance kernel and to the compiled fp64 reference.
-// ---------------------------------------------------------------------------------------------------------------------
-template <int CTRL>
-__device__ __forceinline__ double dpp64(double v)
-{
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xf, 0xf, true);
-    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xf, 0xf, true);
-    return __hiloint2double(hi, lo);
-}
-// t[k] = M[k] * s[K0 + k], s[j] = the value lane j of this lane's row holds (row_newbcast:j = 0x150 + j)
-template <int K0, int CNT, int K = 0>
-__device__ __forceinline__ void row_products(double (&t)[CNT], double s, const double (&M)[CNT])
-{
-    if constexpr (K < CNT)
-    {
-        t[K] = M[K] * dpp64<0x150 + K0 + K>(s);
-        row_products<K0, CNT, K + 1>(t, s, M);
-    }
-}
-__device__ __forceinline__ double row_max(double v) // max over the 16 lanes of a row, every lane gets it
-{
-    v = fmax(v, dpp64<0x128>(v)); v = fmax(v, dpp64<0x124>(v)); v = fmax(v, dpp64<0x122>(v)); v = fmax(v, dpp64<0x121>(v));
-    return v;
-}
-// the reference's order for a lazy product whose result has ROWS rows (see row_dot above)
-template <int ROWS, int CNT>
-__device__ __forceinline__ double lazy_sum(const double (&t)[CNT])
-{
-    static_assert(ROWS <= PS || ROWS % PS == 0, "results with rows > 2 and odd: the reference's order depends on alignment");
-    if constexpr (ROWS > 1 && ROWS % PS == 0) return seq_sum(t);
-    else if constexpr (ROWS == 1) return vec_sum(t);
-    else return novec_sum(t);
-}
-
-// One row of the plant step A*x + B*u on the sixteen lanes: Ar / Br are this lane's row of A and B, x and u the lane's element of [x ; u].  The order is
-// plant64_step's: a product whose rows and depth are both >= 8 is the GEMV accumulator from +0, anything smaller the lazy product's sequential sum.
-template <int NX, int NU>
-__device__ __forceinline__ double plant_row(const double (&Ar)[NX], const double (&Br)[NU], double x, double u)
-{
-    double t[NX], t2[NU];
-    row_products<0, NX>(t, x, Ar);
-    double ax;
-    if constexpr (NX >= 8)
-    {
-        double c = 0.0;
-#pragma unroll
-        for (int j = 0; j < NX; j++) c = t[j] + c;
-        ax = c * 1.0 + 0.0;
-    }
-    else ax = lazy_sum<NX>(t);
-    row_products<NX, NU>(t2, u, Br);
-    return ax + lazy_sum<NX>(t2);
-}
-
-// problem classes of the fp64 library (the thread-per-instance kernels; any N).  nx and nu must each be <= 2 or even (the
-// reference's order for other sizes depends on alignment, see row_dot) and not both >= 8 (Eigen's GEMV kernel is not restated here)
-#define TINY_FOR_EACH_F64DIMS(X) X(12, 4) X(4, 1) X(8, 4) X(12, 2) X(4, 2) X(4, 4) X(16, 4)
-#define TINY_FOR_EACH_F64ROWS(X) X(12, 4, 10) X(12, 4, 30) X(12, 4, 20) X(4, 1, 10) X(8, 4, 9)
-// classes of the sixteen-lane kernel with a runtime horizon (any N <= 64): the unrolled body has a capacity of 32 or 64 steps
-#define TINY_FOR_EACH_F64ROWS_RT(X) X(12, 4) X(4, 1) X(8, 4) X(12, 2) X(4, 2) X(4, 4)
-constexpr int F64ROWS_RT_MAX_N = 64;
-constexpr int F64_AHEAD = 4; // bounds are fetched this many steps ahead of their use
-
-// RT = false: the horizon is the template parameter N.  RT = true ("any horizon", round 3): N is the CAPACITY of the unrolled body
-// (32 or 64 steps: registers are indexed statically, so the body stays unrolled) and the horizon n = P.N <= N is a launch parameter;
-// the steps past it are skipped by wave-uniform branches.  With a capacity of 64 the backward sweep's [p ; d] (live-out only) is
-// written through to its arrays instead of being held in 2 x 64 registers.
-//
-// MPC = true (instantiated separately, so that the one-solve kernels keep their code): the examples' closed loop on chip.  L.mpc_steps times
-// {y = g = 0; tiny_solve; x.col(0) = Adyn x.col(0) + Bdyn u.col(0); start += window_advance} with the whole workspace staying in registers / LDS
-// between two solves; the plant step after the last solve is the host's (plant64_run_kernel).  Only where [p ; d] is held in registers.
-//
-// SIM = true (with MPC; instantiated in tinympc_batch64_sim.hip): the plant step between two solves takes the plant's own rows (S.plant: one table or
-// one per instance; NULL the model's), adds the disturbance row with one separately rounded add and stores the state trajectory.  The flag is the
-// second trailing argument, a Sim64 behind the Mpc64 (not a template parameter of its own: the existing instantiations keep their names).
-template <int NX, int NU, int N, bool RT = false, bool MPC = false, class... LOOP>
-__global__ __launch_bounds__(WAVE64, (N <= 12 ? 2 : 1)) void admm_f64_rows_kernel(const Params64 P, const double *__restrict__ gains, const LOOP... loop)
-{
-    constexpr bool SIM = sizeof...(LOOP) == 2;
-    static_assert(sizeof...(LOOP) == (MPC ? (SIM ? 2 : 1) : 0), "the closed-loop instantiations take one further argument, an Mpc64, the simulated ones a Sim64 behind it; the one-solve kernels none");
-    static_assert(!SIM || MPC, "the simulated loop is the on-chip loop's");
-    [[maybe_unused]] const Mpc64 L = loop_args(loop...);
-    [[maybe_unused]] const Sim64 S = sim_args(loop...);
-    static_assert(!MPC || !(RT && N > 32), "the on-chip loop takes the workspace's d from the registers of [p ; d]");
-    static_assert(NX + NU <= 16 && !(NX >= 8 && NU >= 8), "16-lane mapping; both dims >= 8 would take Eigen's GEMV kernel");
-    static_assert(!RT || N > 20, "the runtime-horizon variant indexes the slack by the horizon: it keeps it in LDS");
-    const int n = RT ? P.N : N; // the horizon
-    constexpr bool PD_REG = !(RT && N > 32);
-    const int lane = threadIdx.x, r16 = lane & 15;
-    const int inst = blockIdx.x * 4 + (lane >> 4);
-    const bool valid = inst < P.batch;
-    const size_t b = valid ? inst : P.batch - 1; // loads of an out-of-range row address the last instance; it stores nothing
-    const bool is_x = r16 < NX, is_u = r16 >= NX && r16 < NX + NU;
-    const int row = is_x ? r16 : (is_u ? r16 - NX : 0);
-    const size_t bp = (size_t)P.bpad;
-    const double rho = P.rho;
-    // element (step, this lane's row) of the pair [x-type array ; u-type array]; u-type arrays have N - 1 steps
-    auto ld = [&](int idx, int idu, int i) -> double {
-        if (is_x) return P.arr[idx][((size_t)i * NX + row) * bp + b];
-        if (is_u && i < n - 1) return P.arr[idu][((size_t)i * NU + row) * bp + b];
-        return 0.0;
-    };
-    auto st = [&](int idx, int idu, int i, double v) {
-        if (!valid) return;
-        if (is_x) P.arr[idx][((size_t)i * NX + row) * bp + b] = v;
-        else if (is_u && i < n - 1) P.arr[idu][((size_t)i * NU + row) * bp + b] = v;
-    };
-    const bool en_b = is_x ? (P.en_state_bound != 0) : (is_u && P.en_input_bound != 0);
-    // this lane's bounds of step i sit at pl0[i * bstep], ph0[i * bstep] (u rows have N - 1 steps; the other lanes read x row 0, unused)
-    const size_t bstr = is_u ? (size_t)P.ub_stride : (size_t)P.xb_stride;
-    const size_t boff = (size_t)row * bstr + (bstr > 1 ? b : 0);
-    const double *const pl0 = (is_u ? P.umin : P.xmin) + boff, *const ph0 = (is_u ? P.umax : P.xmax) + boff;
-    const size_t bstep = (is_u ? NU : NX) * bstr;
-    if (P.max_iter <= 0) // tiny_solve only sets status and iter (admm.cpp:114-117,151)
-    {
-        if (valid && r16 == 0)
-        {
-            P.status[inst] = ST_UNSOLVED; P.iter[inst] = 1;
-            atomicAdd(P.n_unsolved, 1);
-        }
-        return;
-    }
-    // gains, one register per matrix column: [reg][16] doubles (pack_row_gains on the host)
-    double M1[NX], M2[NU], M3[NX], M45[NU];
-#pragma unroll
-    for (int k = 0; k < NX; k++) { M1[k] = gains[k * 16 + r16]; M3[k] = gains[(NX + NU + k) * 16 + r16]; }
-#pragma unroll
-    for (int m = 0; m < NU; m++) { M2[m] = gains[(NX + m) * 16 + r16]; M45[m] = gains[(2 * NX + NU + m) * 16 + r16]; }
-    const double qrow = gains[(2 * NX + 2 * NU) * 16 + r16];
-
-    // ---- live-in ----
-    // long horizons keep the two slack words of a step in LDS (lane-linear, 1 KB per step and wave), short ones in registers
-    constexpr bool LDS_SLACK = N > 20;
-    constexpr int NREG = LDS_SLACK ? 1 : N;
-    __shared__ double slack_lds[LDS_SLACK ? 2 * N * WAVE64 : 1];
-    // (two halves: hipcc leaves a statically indexed array of more than 32 doubles in scratch memory)
-    constexpr int NLO = N < 32 ? N : 32, NHI = N > 32 ? N - 32 : 1;
-    double a_lo[NLO], a_hi[NHI], c_lo[NLO], c_hi[NHI], pd[PD_REG ? N : 1], bb_r[NREG], sn_r[NREG];
-#define A_(i) ((i) < 32 ? a_lo[(i) < 32 ? (i) : 0] : a_hi[(i) < 32 ? 0 : (i) - 32])
-#define C_(i) ((i) < 32 ? c_lo[(i) < 32 ? (i) : 0] : c_hi[(i) < 32 ? 0 : (i) - 32])
-    double *const sl = slack_lds + lane;
-#define BB_GET(i) (LDS_SLACK ? sl[(2 * (i)) * WAVE64] : bb_r[LDS_SLACK ? 0 : (i)])
-#define SN_GET(i) (LDS_SLACK ? sl[(2 * (i) + 1) * WAVE64] : sn_r[LDS_SLACK ? 0 : (i)])
-#define BB_SET(i, v) do { if constexpr (LDS_SLACK) sl[(2 * (i)) * WAVE64] = (v); else bb_r[LDS_SLACK ? 0 : (i)] = (v); } while (0)
-#define SN_SET(i, v) do { if constexpr (LDS_SLACK) sl[(2 * (i) + 1) * WAVE64] = (v); else sn_r[LDS_SLACK ? 0 : (i)] = (v); } while (0)
-    double xrN = 0.0;
-    // row i of a window reference: table[min(start + i, rows - 1)] (the clamp of the window gather); the table is small and stays in L2
-    [[maybe_unused]] const bool window = MPC && L.table_rows > 0;
-    [[maybe_unused]] int wstart = 0;
-    if constexpr (MPC) wstart = window ? L.xref_start[b] : 0;
-    [[maybe_unused]] auto win_at = [&](int i) -> double {
-        const int tr = wstart + i < L.table_rows - 1 ? wstart + i : L.table_rows - 1;
-        return is_x ? L.table[(size_t)tr * NX + row] : 0.0;
-    };
-#pragma unroll
-    for (int i = 0; i < N; i++)
-    {
-        if (RT && i >= n) continue;
-        double xr = 0.0;
-        if (MPC && window) xr = win_at(i);
-        else if (is_x) xr = P.xref[((size_t)i * NX + row) * (size_t)P.xref_stride + (P.xref_stride > 1 ? b : 0)];
-        const double pdi = ld(TINY_ARR_P, TINY_ARR_D, i);
-        if constexpr (PD_REG) pd[i] = pdi;
-        C_(i) = is_x ? -(xr * qrow) : pdi;            // admm.cpp:81 | d_i
-        A_(i) = MPC ? 0.0 : ld(TINY_ARR_G, TINY_ARR_Y, i); // (the closed loop starts every solve from y = g = 0)
-        BB_SET(i, ld(TINY_ARR_V, TINY_ARR_Z, i));
-        SN_SET(i, 0.0);
-        if (i == n - 1) xrN = xr;
-    }
-    double x0 = ld(TINY_ARR_X, TINY_ARR_U, 0); // x.col(0) on the x rows
-    double pterm;
-    {
-        double PT[NX], t[NX]; // p.col(N-1) = -(Xref.col(N-1)^T * Pinf)  (admm.cpp:83): a vectorised reduction over k
-#pragma unroll
-        for (int k = 0; k < NX; k++) PT[k] = gains[(2 * NX + 2 * NU + 1 + k) * 16 + r16];
-        row_products<0, NX>(t, xrN, PT);
-        pterm = -vec_sum(t);
-    }
-    double r_ps = 0, r_pi = 0, r_ds = 0, r_di = 0;
-    {
-        const size_t bi = b;
-        r_ps = P.res[0 * bp + bi]; r_pi = P.res[1 * bp + bi]; r_ds = P.res[2 * bp + bi]; r_di = P.res[3 * bp + bi];
-    }
-    int status = ST_UNSOLVED, itn = 1; // admm.cpp:114-115
-    bool active = valid;
-    double pN = 0.0;
-
-    [[maybe_unused]] int ms = 0; // the MPC step of the on-chip closed loop
-next_solve: // (a label, not a loop around the solve: the one-solve instantiations keep the code they had without one)
-    for (int it = 0; it < P.max_iter; ++it)
-    {
-        if (!__any(active)) break;
-        // No divergent region around the body: a row that has converged keeps executing with its wave and every update of its
-        // state is a select on `active` (a compiler-visible `if (active)` would make hipcc keep the old and the new value of
-        // all 3N state registers alive across the region: 264 spilled registers at N = 30).
-        itn = active ? it + 1 : itn; // admm.cpp:120
-        // the last permitted backward sweep must not overwrite d in c: x, u of an instance that exhausts max_iter come from
-        // the d its last forward sweep used (regenerated below); the final d itself goes to pd
-        const bool keep_d = (it == P.max_iter - 1);
-        // ---- forward_pass + update_slack + update_dual + residual maxima (admm.cpp:27-71, 95-98) ----
-        double s = x0, pri = 0.0, dua = 0.0, t1 = 0.0;
-        double lo[F64_AHEAD], hi[F64_AHEAD];
-        // an offset the compiler cannot see through, renewed every iteration: without it LICM hoists the 2N 64-bit bound
-        // addresses out of the iteration loop and keeps them in 4N registers
-        int oz;
-        asm volatile("s_mov_b32 %0, 0" : "=s"(oz));
-        const double *const pl = pl0 + oz, *const ph = ph0 + oz;
-        auto ld_bounds = [&](int i, double &l, double &h) {
-            const size_t o = (size_t)((is_u && i >= n - 1) ? 0 : i) * bstep;
-            l = pl[o]; h = ph[o];
-        };
-#pragma unroll
-        for (int k = 0; k < F64_AHEAD; k++) ld_bounds(k < n ? k : n - 1, lo[k], hi[k]);
-#pragma unroll
-        for (int i = 0; i < N; i++)
-        {
-            if (RT && i >= n) continue;
-            double sv, xn = 0.0;
-            if (i < n - 1)
-            {
-                double t[NX], t2[NU];
-                row_products<0, NX>(t, s, M1);
-                const double acc = is_x ? lazy_sum<NX>(t) : lazy_sum<NU>(t);   // Adyn*x | Kinf*x
-                const double un = -acc - C_(i);                                   // admm.cpp:31
-                row_products<NX, NU>(t2, un, M2);
-                xn = acc + lazy_sum<NX>(t2);                                     // admm.cpp:35
-                sv = is_u ? un : s;
-            }
-            else sv = is_x ? s : 0.0;
-            const double lo_i = lo[i % F64_AHEAD], hi_i = hi[i % F64_AHEAD];
-            if (i + F64_AHEAD < n) ld_bounds(i + F64_AHEAD, lo[i % F64_AHEAD], hi[i % F64_AHEAD]);
-            const double t0 = sv + A_(i);                                         // admm.cpp:47-48
-            double tc = t0;
-            if (en_b && (i < n - 1 || is_x))                                     // admm.cpp:51-60: min(max, max(min, t)); u has N - 1 steps
-            {
-                tc = (lo_i < tc) ? tc : lo_i;
-                tc = (tc < hi_i) ? tc : hi_i;
-            }
-            const double an = (A_(i) + sv) - tc;                                  // admm.cpp:69-70
-            pri = fmax(pri, fabs(sv - tc));                                      // admm.cpp:95,97
-            dua = fmax(dua, fabs(BB_GET(i) - tc));                               // admm.cpp:96,98
-            A_(i) = active ? an : A_(i);
-            if constexpr (LDS_SLACK) { if (active) SN_SET(i, tc); }
-            else sn_r[LDS_SLACK ? 0 : i] = active ? tc : sn_r[LDS_SLACK ? 0 : i];
-            t1 = tc - an;
-            s = xn;
-        }
-        pN = active ? pterm - rho * t1 : pN; // admm.cpp:83-84
-        const double pri_x = row_max(is_x ? pri : 0.0), dua_x = row_max(is_x ? dua : 0.0);
-        const double pri_u = row_max(is_u ? pri : 0.0), dua_u = row_max(is_u ? dua : 0.0);
-        bool conv = false;
-        if ((it + 1) % P.check_termination == 0) // admm.cpp:91-109 (wave-uniform condition)
-        {
-            r_ps = active ? pri_x : r_ps; r_ds = active ? dua_x * rho : r_ds; r_pi = active ? pri_u : r_pi; r_di = active ? dua_u * rho : r_di;
-            conv = active && (r_ps < P.abs_pri_tol) && (r_pi < P.abs_pri_tol) && (r_ds < P.abs_dua_tol) && (r_di < P.abs_dua_tol);
-        }
-        status = conv ? ST_SOLVED : status; // admm.cpp:136: returns before the v/z copy and the backward pass
-        active = active && !conv;
-        if (!__any(active)) break;
-        // ---- v = vnew, z = znew (admm.cpp:141-142), update_linear_cost + backward_pass_grad (admm.cpp:15-22, 80-82) ----
-        double p = pN;
-        if constexpr (LDS_SLACK) { if (active) BB_SET(n - 1, SN_GET(n - 1)); }
-        else bb_r[LDS_SLACK ? 0 : N - 1] = active ? sn_r[LDS_SLACK ? 0 : N - 1] : bb_r[LDS_SLACK ? 0 : N - 1];
-#pragma unroll
-        for (int i = N - 2; i >= 0; i--)
-        {
-            if (RT && i > n - 2) continue;
-            const double sni = SN_GET(i);
-            if constexpr (LDS_SLACK) { if (active) BB_SET(i, sni); }
-            else bb_r[LDS_SLACK ? 0 : i] = active ? sni : bb_r[LDS_SLACK ? 0 : i];
-            const double cq = is_x ? C_(i) : -0.0; // u rows: r = -rho*(znew - y) keeps the sign of a zero difference
-            const double lin = cq - rho * (sni - A_(i));
-            double t[NX], tk[NU], td[NU];
-            row_products<0, NX>(t, p, M3);
-            // x rows: AmBKt*p (coefficient-evaluated: halving tree, or sequential when nu = 1); u rows: Bdyn^T*p (vectorised reduction)
-            const double dot = is_x ? ((NU == 1 && NX % PS == 0) ? seq_sum(t) : novec_sum(t)) : vec_sum(t);
-            const double wv = lin + dot;               // q + AmBKt*p | Bdyn^T*p + r
-            row_products<NX, NU>(tk, lin, M45);        // Kinf^T * r
-            row_products<NX, NU>(td, wv, M45);         // Quu_inv * (Bdyn^T p + r)
-            const double pn = wv - vec_sum(tk);        // admm.cpp:20
-            const double dd = lazy_sum<NU>(td);        // admm.cpp:19
-            if constexpr (PD_REG) pd[i] = active ? (is_u ? dd : pn) : pd[i];
-            else { if (active) st(TINY_ARR_P, TINY_ARR_D, i, is_u ? dd : pn); }
-            C_(i) = (active && is_u && !keep_d) ? dd : C_(i);
-            p = pn;
-        }
-    }
-    if constexpr (MPC)
-    if (ms + 1 < L.mpc_steps)
-    {
-        // ---- advance to the next MPC step (quadrotor_tracking.cpp:101-118): nothing leaves the chip but u.col(0) ----
-        double t[NX], t2[NU];
-        row_products<0, NX>(t, x0, M1);
-        const double acc = is_x ? lazy_sum<NX>(t) : lazy_sum<NU>(t);
-        const double u0 = -acc - C_(0); // [. ; u_0] of the solve that just finished: step 0 of the forward recursion (admm.cpp:31)
-        if (L.u0_traj && valid && is_u) L.u0_traj[((size_t)ms * P.batch + inst) * NU + row] = u0;
-        if constexpr (SIM)
-        {
-            // x.col(0) = (A_p * x.col(0) + B_p * u.col(0)) + w: the products and sums below with the plant's rows, then one separately rounded add.
-            // The lane offsets are remade here from `inst`, opaque to the compiler (as the gains and the bounds: it otherwise carries the 64-bit
-            // lane addresses through every iteration loop); an out-of-range row reads the last instance's and stores nothing.
-            int ia = inst;
-            asm volatile("" : "+v"(ia));
-            ia = valid ? ia : P.batch - 1;
-            if (S.plant)
-            {
-                const double *const pl = S.plant + ((size_t)ia * S.plant_stride + r16);
-                double Ar[NX], Br[NU]; // transient: this lane's row of [A_p | B_p]
-#pragma unroll
-                for (int k = 0; k < NX; k++) Ar[k] = pl[k * 16];
-#pragma unroll
-                for (int m = 0; m < NU; m++) Br[m] = pl[(NX + m) * 16];
-                x0 = plant_row<NX, NU>(Ar, Br, x0, u0);
-            }
-            else x0 = plant_row<NX, NU>(M1, M2, x0, u0);
-            const size_t xo = ((size_t)ms * P.batch + ia) * NX + (is_x ? r16 : 0);
-            if (S.w && is_x) x0 = x0 + S.w[xo];
-            if (S.x_traj && valid && is_x) S.x_traj[xo] = x0;
-        }
-        else
-        {
-            // x.col(0) = Adyn * x.col(0) + Bdyn * u.col(0) in plant64_kernel's order: rows and depth >= 8 is the GEMV accumulator from +0
-            double ax;
-            if constexpr (NX >= 8)
-            {
-                double c = 0.0;
-#pragma unroll
-                for (int j = 0; j < NX; j++) c = t[j] + c;
-                ax = c * 1.0 + 0.0;
-            }
-            else ax = lazy_sum<NX>(t);
-            row_products<NX, NU>(t2, u0, M2);
-            x0 = ax + lazy_sum<NX>(t2); // (x rows; the other lanes' value is never read as a state)
-        }
-        if (window) wstart += L.window_advance;
-        // the gains through an offset the compiler cannot see through (as the bounds above): otherwise it keeps Q and the NX registers of
-        // Pinf's row from live-in alive through every solve instead of loading them again here
-        int ozg;
-        asm volatile("s_mov_b32 %0, 0" : "=s"(ozg));
-        const double *const gains_again = gains + ozg;
-        const double qrow_again = gains_again[(2 * NX + 2 * NU) * 16 + r16];
-#pragma unroll
-        for (int i = 0; i < N; i++)
-        {
-            if (RT && i >= n) continue;
-            double cx = C_(i);
-            if (window)
-            {
-                const double xr = win_at(i);
-                cx = -(xr * qrow_again);
-                if (i == n - 1) xrN = xr;
-            }
-            C_(i) = is_x ? cx : pd[i]; // d of the workspace is that of the last executed backward sweep (keep_d)
-            A_(i) = 0.0;               // y = g = 0 (quadrotor_hovering.cpp:100-101)
-            __builtin_amdgcn_sched_barrier(0); // one table row in flight at a time: hoisted together the N loads cost 2N registers
-        }
-        if (window) // admm.cpp:83 for the window's new last row, as at live-in
-        {
-            double PT[NX], tp[NX];
-#pragma unroll
-            for (int k = 0; k < NX; k++) PT[k] = gains_again[(2 * NX + 2 * NU + 1 + k) * 16 + r16];
-            row_products<0, NX>(tp, xrN, PT);
-            pterm = -vec_sum(tp);
-        }
-        status = ST_UNSOLVED; itn = 1; active = valid; // the residual fields carry over: they are live-in of the next tiny_solve
-        ++ms;
-        goto next_solve;
-    }
-    // ---- live-out: every work array once ----
-    {
-        const bool solved = status == ST_SOLVED;
-        double s = x0;
-#pragma unroll
-        for (int i = 0; i < N; i++)
-        {
-            if (RT && i >= n) continue;
-            double sv, xn = 0.0;
-            if (i < n - 1) // x, u regenerated from the d of the last executed forward sweep by the same instruction sequence
-            {
-                double t[NX], t2[NU];
-                row_products<0, NX>(t, s, M1);
-                const double acc = is_x ? lazy_sum<NX>(t) : lazy_sum<NU>(t);
-                const double un = -acc - C_(i);
-                row_products<NX, NU>(t2, un, M2);
-                xn = acc + lazy_sum<NX>(t2);
-                sv = is_u ? un : s;
-            }
-            else sv = is_x ? s : 0.0;
-            s = xn;
-            st(TINY_ARR_X, TINY_ARR_U, i, sv);
-            const double sni = SN_GET(i);
-            st(TINY_ARR_Q, TINY_ARR_R, i, (is_x ? C_(i) : -0.0) - rho * (sni - A_(i)));
-            if constexpr (PD_REG) st(TINY_ARR_P, TINY_ARR_D, i, i == n - 1 ? pN : pd[i]);
-            else { if (i == n - 1) st(TINY_ARR_P, TINY_ARR_D, i, pN); }
-            st(TINY_ARR_V, TINY_ARR_Z, i, BB_GET(i));
-            st(TINY_ARR_VNEW, TINY_ARR_ZNEW, i, sni);
-            st(TINY_ARR_G, TINY_ARR_Y, i, A_(i));
-        }
-        if (valid && r16 == 0)
-        {
-            P.res[0 * bp + inst] = r_ps; P.res[1 * bp + inst] = r_pi; P.res[2 * bp + inst] = r_ds; P.res[3 * bp + inst] = r_di;
-            P.status[inst] = status;
-            P.iter[inst] = itn;
-            if (!solved) atomicAdd(P.n_unsolved, 1);
-            if constexpr (MPC)
-                if (window) L.xref_start[inst] = wstart;
-        }
-    }
-#undef A_
-#undef C_
-#undef BB_GET
-#undef SN_GET
-#undef BB_SET
-#undef SN_SET
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// The six functions tiny_solve() is made of (admm.hpp:12-18), one launch each, one thread per instance: each reads and writes
-// exactly the members the reference function does, in the same arithmetic as the fused kernels above.
-// ---------------------------------------------------------------------------------------------------------------------
-enum { F64_FORWARD_PASS = 0, F64_UPDATE_SLACK, F64_UPDATE_DUAL, F64_UPDATE_LINEAR_COST, F64_TERMINATION_CONDITION, F64_BACKWARD_PASS_GRAD };
-
-template <int NX, int NU, int FN>
-__global__ __launch_bounds__(WAVE64) void admm_f64_step_kernel(const Params64 P, int *__restrict__ conv_out)
-{
-    constexpr int NMAT = NU * NX + NX * NX + NU * NU + NX * NX + NX * NX + NX * NU + NX;
-    __shared__ double mats[NMAT];
-    for (int e = threadIdx.x; e < NMAT; e += WAVE64) mats[e] = P.mats[e];
-    __syncthreads();
-    const double *K = mats, *Pinf = K + NU * NX, *Quu = Pinf + NX * NX, *Am = Quu + NU * NU, *A = Am + NX * NX, *Bm = A + NX * NX,
-                 *Q = Bm + NX * NU;
-    const int b = blockIdx.x * WAVE64 + threadIdx.x;
-    if (b >= P.batch) return;
-    const int N = P.N;
-    const size_t bp = (size_t)P.bpad;
-    const double rho = P.rho;
-    auto at = [&](int id, int step, int row, int dim) -> double & { return P.arr[id][((size_t)step * dim + row) * bp + b]; };
-    auto in = [&](const double *base, int stride, int step, int row, int dim) {
-        return base[((size_t)step * dim + row) * (size_t)stride + (stride > 1 ? b : 0)];
-    };
-    if constexpr (FN == F64_FORWARD_PASS) // admm.cpp:27-37
-    {
-        double x[NX];
-#pragma unroll
-        for (int j = 0; j < NX; j++) x[j] = at(TINY_ARR_X, 0, j, NX);
-        for (int i = 0; i < N - 1; i++)
-        {
-            double u[NU], xn[NX];
-#pragma unroll
-            for (int j = 0; j < NU; j++) u[j] = -row_dot<NU, NX>(K, j, x) - at(TINY_ARR_D, i, j, NU);
-#pragma unroll
-            for (int j = 0; j < NX; j++) xn[j] = row_dot<NX, NX>(A, j, x) + row_dot<NX, NU>(Bm, j, u);
-#pragma unroll
-            for (int j = 0; j < NU; j++) at(TINY_ARR_U, i, j, NU) = u[j];
-#pragma unroll
-            for (int j = 0; j < NX; j++) { at(TINY_ARR_X, i + 1, j, NX) = xn[j]; x[j] = xn[j]; }
-        }
-    }
-    else if constexpr (FN == F64_UPDATE_SLACK) // admm.cpp:45-61
-    {
-        for (int i = 0; i < N - 1; i++)
-#pragma unroll
-            for (int j = 0; j < NU; j++)
-            {
-                double zn = at(TINY_ARR_U, i, j, NU) + at(TINY_ARR_Y, i, j, NU);
-                if (P.en_input_bound)
-                {
-                    const double lo = in(P.umin, P.ub_stride, i, j, NU), hi = in(P.umax, P.ub_stride, i, j, NU);
-                    zn = (lo < zn) ? zn : lo;
-                    zn = (zn < hi) ? zn : hi;
-                }
-                at(TINY_ARR_ZNEW, i, j, NU) = zn;
-            }
-        for (int i = 0; i < N; i++)
-#pragma unroll
-            for (int j = 0; j < NX; j++)
-            {
-                double vn = at(TINY_ARR_X, i, j, NX) + at(TINY_ARR_G, i, j, NX);
-                if (P.en_state_bound)
-                {
-                    const double lo = in(P.xmin, P.xb_stride, i, j, NX), hi = in(P.xmax, P.xb_stride, i, j, NX);
-                    vn = (lo < vn) ? vn : lo;
-                    vn = (vn < hi) ? vn : hi;
-                }
-                at(TINY_ARR_VNEW, i, j, NX) = vn;
-            }
-    }
-    else if constexpr (FN == F64_UPDATE_DUAL) // admm.cpp:67-71
-    {
-        for (int i = 0; i < N - 1; i++)
-#pragma unroll
-            for (int j = 0; j < NU; j++) at(TINY_ARR_Y, i, j, NU) = at(TINY_ARR_Y, i, j, NU) + at(TINY_ARR_U, i, j, NU) - at(TINY_ARR_ZNEW, i, j, NU);
-        for (int i = 0; i < N; i++)
-#pragma unroll
-            for (int j = 0; j < NX; j++) at(TINY_ARR_G, i, j, NX) = at(TINY_ARR_G, i, j, NX) + at(TINY_ARR_X, i, j, NX) - at(TINY_ARR_VNEW, i, j, NX);
-    }
-    else if constexpr (FN == F64_UPDATE_LINEAR_COST) // admm.cpp:77-85
-    {
-        for (int i = 0; i < N - 1; i++)
-#pragma unroll
-            for (int j = 0; j < NU; j++) at(TINY_ARR_R, i, j, NU) = -rho * (at(TINY_ARR_ZNEW, i, j, NU) - at(TINY_ARR_Y, i, j, NU));
-        for (int i = 0; i < N; i++)
-#pragma unroll
-            for (int j = 0; j < NX; j++)
-            {
-                double q = -(in(P.xref, P.xref_stride, i, j, NX) * Q[j]);
-                q = q - rho * (at(TINY_ARR_VNEW, i, j, NX) - at(TINY_ARR_G, i, j, NX));
-                at(TINY_ARR_Q, i, j, NX) = q;
-            }
-        double xr[NX];
-#pragma unroll
-        for (int k = 0; k < NX; k++) xr[k] = in(P.xref, P.xref_stride, N - 1, k, NX);
-#pragma unroll
-        for (int j = 0; j < NX; j++)
-        {
-            double t[NX];
-#pragma unroll
-            for (int k = 0; k < NX; k++) t[k] = xr[k] * Pinf[j * NX + k];
-            const double pt = -vec_sum(t);
-            at(TINY_ARR_P, N - 1, j, NX) = pt - rho * (at(TINY_ARR_VNEW, N - 1, j, NX) - at(TINY_ARR_G, N - 1, j, NX));
-        }
-    }
-    else if constexpr (FN == F64_TERMINATION_CONDITION) // admm.cpp:91-109
-    {
-        bool conv = false;
-        if (P.iter[b] % P.check_termination == 0)
-        {
-            double pri_x = 0, dua_x = 0, pri_u = 0, dua_u = 0;
-            for (int i = 0; i < N; i++)
-#pragma unroll
-                for (int j = 0; j < NX; j++)
-                {
-                    const double vn = at(TINY_ARR_VNEW, i, j, NX);
-                    const double px = fabs(at(TINY_ARR_X, i, j, NX) - vn), dx = fabs(at(TINY_ARR_V, i, j, NX) - vn);
-                    pri_x = (i == 0 && j == 0) ? px : (px > pri_x ? px : pri_x);
-                    dua_x = (i == 0 && j == 0) ? dx : (dx > dua_x ? dx : dua_x);
-                }
-            for (int i = 0; i < N - 1; i++)
-#pragma unroll
-                for (int j = 0; j < NU; j++)
-                {
-                    const double zn = at(TINY_ARR_ZNEW, i, j, NU);
-                    const double pu = fabs(at(TINY_ARR_U, i, j, NU) - zn), du = fabs(at(TINY_ARR_Z, i, j, NU) - zn);
-                    pri_u = (i == 0 && j == 0) ? pu : (pu > pri_u ? pu : pri_u);
-                    dua_u = (i == 0 && j == 0) ? du : (du > dua_u ? du : dua_u);
-                }
-            const double r_ps = pri_x, r_ds = dua_x * rho, r_pi = pri_u, r_di = dua_u * rho;
-            P.res[0 * bp + b] = r_ps; P.res[1 * bp + b] = r_pi; P.res[2 * bp + b] = r_ds; P.res[3 * bp + b] = r_di;
-            conv = (r_ps < P.abs_pri_tol) && (r_pi < P.abs_pri_tol) && (r_ds < P.abs_dua_tol) && (r_di < P.abs_dua_tol);
-        }
-        conv_out[b] = conv ? 1 : 0;
-    }
-    else // F64_BACKWARD_PASS_GRAD, admm.cpp:15-22
-    {
-        double pn[NX];
-#pragma unroll
-        for (int j = 0; j < NX; j++) pn[j] = at(TINY_ARR_P, N - 1, j, NX);
-        for (int i = N - 2; i >= 0; i--)
-        {
-            double r[NU], tmp[NU], dn[NU], pi[NX];
-#pragma unroll
-            for (int j = 0; j < NU; j++) r[j] = at(TINY_ARR_R, i, j, NU);
-#pragma unroll
-            for (int j = 0; j < NU; j++)
-            {
-                double t[NX];
-#pragma unroll
-                for (int k = 0; k < NX; k++) t[k] = Bm[j * NX + k] * pn[k];
-                tmp[j] = vec_sum(t) + r[j];
-            }
-#pragma unroll
-            for (int j = 0; j < NU; j++) dn[j] = row_dot<NU, NU>(Quu, j, tmp);
-#pragma unroll
-            for (int j = 0; j < NX; j++)
-            {
-                double t[NX], tk[NU];
-#pragma unroll
-                for (int k = 0; k < NX; k++) t[k] = Am[k * NX + j] * pn[k];
-                const double a = (NU == 1 && NX % PS == 0) ? seq_sum(t) : novec_sum(t);
-#pragma unroll
-                for (int m = 0; m < NU; m++) tk[m] = K[j * NU + m] * r[m];
-                pi[j] = at(TINY_ARR_Q, i, j, NX) + a - vec_sum(tk);
-            }
-#pragma unroll
-            for (int j = 0; j < NU; j++) at(TINY_ARR_D, i, j, NU) = dn[j];
-#pragma unroll
-            for (int j = 0; j < NX; j++) { at(TINY_ARR_P, i, j, NX) = pi[j]; pn[j] = pi[j]; }
-        }
-    }
-}
-
-#ifndef TINY_F64SIM_UNIT // (not templates: the unit of the simulated loop would emit them a second time)
 // host layout [cnt][steps][dim] (cnt = 1: shared, stored once with stride 1)  <->  device [steps][dim][stride]
 __global__ void pack64_kernel(const double *__restrict__ src, double *__restrict__ dst, int nb, int steps, int dim, int stride, int step0, int nsteps)
 {
@@ -983,160 +45,6 @@ __global__ void unpack64_kernel(const double *__restrict__ src, double *__restri
         dst[((long long)b * steps + s) * dim + row] = src[((long long)s * dim + row) * stride + b];
     }
 }
-#endif
-
-// Plant step of the examples' closed loop (quadrotor_hovering.cpp:110-111): x.col(0) <- Adyn * x.col(0) + Bdyn * u.col(0), in
-// Eigen's order for that expression over tiny_VectorNx: a product whose rows and depth are both >= 8 runs through the
-// column-major GEMV kernel (row accumulator from +0, then alpha * acc + result), anything smaller is the lazy product's
-// sequential sum (tests/test_oracle.py: test_plant_step_bit_exact_vs_compiled_reference pins the oracle's restatement of
-// this against the compiled expression, fp64 configurations included).
-template <int NX, int NU>
-__device__ __forceinline__ void plant64_step(double *__restrict__ X, const double (&u)[NU], const double *__restrict__ mats, int b, int bpad)
-{
-    static_assert(!(NX >= 8 && NU >= 8), "Bdyn*u would take the GEMV kernel too");
-    constexpr int OFF_A = NU * NX + NX * NX + NU * NU + NX * NX, OFF_B = OFF_A + NX * NX;
-    const double *A = mats + OFF_A, *Bm = mats + OFF_B;
-    double x[NX], xn[NX];
-#pragma unroll
-    for (int j = 0; j < NX; j++) x[j] = X[(size_t)j * bpad + b];
-#pragma unroll
-    for (int i = 0; i < NX; i++)
-    {
-        double a;
-        if constexpr (NX >= 8)
-        {
-            double c = 0.0;
-#pragma unroll
-            for (int j = 0; j < NX; j++) c = A[j * NX + i] * x[j] + c;
-            a = c * 1.0 + 0.0;
-        }
-        else a = row_dot<NX, NX>(A, i, x);
-        xn[i] = a + row_dot<NX, NU>(Bm, i, u);
-    }
-#pragma unroll
-    for (int i = 0; i < NX; i++) X[(size_t)i * bpad + b] = xn[i];
-}
-template <int NX, int NU>
-__global__ void plant64_kernel(double *__restrict__ X, const double *__restrict__ U, const double *__restrict__ mats, int batch, int bpad)
-{
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= batch) return;
-    double u[NU];
-#pragma unroll
-    for (int j = 0; j < NU; j++) u[j] = U[(size_t)j * bpad + b];
-    plant64_step<NX, NU>(X, u, mats, b, bpad);
-}
-// The plant step of a multi-step run (tiny_batch64_mpc_run): the same step; it also records u.col(0) in this MPC step's row of the
-// trajectory ([B][nu], may be NULL) and slides the instance's reference window (start may be NULL).
-template <int NX, int NU>
-__global__ void plant64_run_kernel(double *__restrict__ X, const double *__restrict__ U, const double *__restrict__ mats, int batch, int bpad,
-                                   double *__restrict__ u0_row, int *__restrict__ start, int window_advance)
-{
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= batch) return;
-    double u[NU];
-#pragma unroll
-    for (int j = 0; j < NU; j++) u[j] = U[(size_t)j * bpad + b];
-    if (u0_row)
-    {
-#pragma unroll
-        for (int j = 0; j < NU; j++) u0_row[(size_t)b * NU + j] = u[j];
-    }
-    plant64_step<NX, NU>(X, u, mats, b, bpad);
-    if (start) start[b] += window_advance;
-}
-
-#ifdef TINY_F64SIM_UNIT
-// ---------------------------------------------------------------------------------------------------------------------
-// The simulated closed loop (tiny_batch64_set_plant, tiny_batch64_mpc_run_sim), compiled as tinympc_batch64_sim.hip: the SIM instantiations of the
-// sixteen-lane kernel, the plant kernel of the launch sequence and of a run's last step, and their launchers — a translation unit of its own, so
-// that every kernel of this file keeps its code.
-// ---------------------------------------------------------------------------------------------------------------------
-// plant64_run_kernel against a separate plant: x.col(0) <- (A_p * x.col(0) + B_p * u.col(0)) + w in plant64_step's order, then one separately
-// rounded add (none without w).  The matrices are the plant's (one pair, or instance b's at + b * stride) or the model's; it records u.col(0) and
-// x.col(0) in this step's rows of the trajectories and slides the window, each where asked to.
-template <int NX, int NU>
-__global__ void plant64_sim_kernel(const PlantSim64 a)
-{
-    static_assert(!(NX >= 8 && NU >= 8), "Bdyn*u would take the GEMV kernel too");
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= a.batch) return;
-    const double *const A = a.A + (size_t)b * a.stride_a, *const Bm = a.B + (size_t)b * a.stride_b;
-    double u[NU], x[NX], xn[NX];
-#pragma unroll
-    for (int j = 0; j < NU; j++) u[j] = a.U[(size_t)j * a.bpad + b];
-    if (a.u0_row)
-    {
-#pragma unroll
-        for (int j = 0; j < NU; j++) a.u0_row[(size_t)b * NU + j] = u[j];
-    }
-#pragma unroll
-    for (int j = 0; j < NX; j++) x[j] = a.X[(size_t)j * a.bpad + b];
-#pragma unroll
-    for (int i = 0; i < NX; i++)
-    {
-        double ax;
-        if constexpr (NX >= 8)
-        {
-            double c = 0.0;
-#pragma unroll
-            for (int j = 0; j < NX; j++) c = A[j * NX + i] * x[j] + c;
-            ax = c * 1.0 + 0.0;
-        }
-        else ax = row_dot<NX, NX>(A, i, x);
-        xn[i] = ax + row_dot<NX, NU>(Bm, i, u);
-        if (a.w) xn[i] = xn[i] + a.w[(size_t)b * NX + i];
-    }
-#pragma unroll
-    for (int i = 0; i < NX; i++)
-    {
-        a.X[(size_t)i * a.bpad + b] = xn[i];
-        if (a.x_traj) a.x_traj[(size_t)b * NX + i] = xn[i];
-    }
-    if (a.start) a.start[b] += a.window_advance;
-}
-
-} // namespace
-
-namespace tinympc64
-{
-hipError_t launch_plant64_sim(int nx, int nu, const PlantSim64 &a)
-{
-#define TINY_F64_PLANT_SIM(NX, NU)                                                                           \
-    if (nx == NX && nu == NU)                                                                                \
-    {                                                                                                        \
-        hipLaunchKernelGGL((plant64_sim_kernel<NX, NU>), dim3((a.batch + 127) / 128), dim3(128), 0, 0, a);   \
-        return hipGetLastError();                                                                            \
-    }
-    TINY_FOR_EACH_F64DIMS(TINY_F64_PLANT_SIM)
-    return hipErrorInvalidValue;
-}
-
-// a SIM instantiation wherever there is an MPC one: the unrolled horizons and the capacity-32 body of every sixteen-lane class
-hipError_t launch_rows64_sim(int nx, int nu, int N, const void *params, const double *gains, const void *mpc, const Sim64 &S)
-{
-    const Params64 &P = *static_cast<const Params64 *>(params);
-    const Mpc64 &L = *static_cast<const Mpc64 *>(mpc);
-    if (L.mpc_steps <= 1 || P.max_iter < 1) return hipErrorInvalidValue;
-    const int nrow_blocks = (P.batch + 3) / 4;
-#define TINY_F64ROWS_SIM_LAUNCH(NX, NU, NN)                                                                                                        \
-    if (nx == NX && nu == NU && N == NN)                                                                                                           \
-    {                                                                                                                                              \
-        hipLaunchKernelGGL((admm_f64_rows_kernel<NX, NU, NN, false, true, Mpc64, Sim64>), dim3(nrow_blocks), dim3(WAVE64), 0, 0, P, gains, L, S); \
-        return hipGetLastError();                                                                                                                  \
-    }
-    TINY_FOR_EACH_F64ROWS(TINY_F64ROWS_SIM_LAUNCH)
-#define TINY_F64ROWS_RT_SIM_LAUNCH(NX, NU)                                                                                                         \
-    if (nx == NX && nu == NU && N >= 2 && N <= 32)                                                                                                 \
-    {                                                                                                                                              \
-        hipLaunchKernelGGL((admm_f64_rows_kernel<NX, NU, 32, true, true, Mpc64, Sim64>), dim3(nrow_blocks), dim3(WAVE64), 0, 0, P, gains, L, S); \
-        return hipGetLastError();                                                                                                                  \
-    }
-    TINY_FOR_EACH_F64ROWS_RT(TINY_F64ROWS_RT_SIM_LAUNCH)
-    return hipErrorInvalidValue;
-}
-} // namespace tinympc64
-#else // TINY_F64SIM_UNIT
 // a window reference as the per-instance array the one-solve kernels read: row i of instance b is table[min(start[b] + i, rows - 1)]
 __global__ void gather_window64_kernel(const double *__restrict__ table, const int *__restrict__ start, double *__restrict__ dst, int rows, int N, int nx,
                                        int batch, int bpad)
@@ -1222,21 +130,6 @@ size_t mat_off(const TinyBatch64 *tb, int which) // Kinf, Pinf, Quu_inv, AmBKt, 
     size_t o = 0;
     for (int k = 0; k < which; k++) o += sz[k];
     return o;
-}
-bool rows_unrolled(int nx, int nu, int N)
-{
-#define TINY_F64ROWS_CHECK(NX, NU, NN) \
-    if (nx == NX && nu == NU && N == NN) return true;
-    TINY_FOR_EACH_F64ROWS(TINY_F64ROWS_CHECK)
-    return false;
-}
-bool rows_supported(int nx, int nu, int N)
-{
-    if (rows_unrolled(nx, nu, N)) return true;
-#define TINY_F64ROWS_RT_CHECK(NX, NU) \
-    if (nx == NX && nu == NU && N >= 2 && N <= F64ROWS_RT_MAX_N) return true;
-    TINY_FOR_EACH_F64ROWS_RT(TINY_F64ROWS_RT_CHECK)
-    return false;
 }
 // lane r of a row holds, per matrix column, the element of the row it owns (x rows r < nx, u rows nx <= r < nx + nu):
 //   M1[k]  x rows Adyn(r,k)   | u rows Kinf(m,k)        M2[m]  x rows Bdyn(r,m)
@@ -1339,18 +232,13 @@ int prepare64(TinyBatch64 *tb, Params64 &P, bool gathered_ref = true)
 }
 
 // one of the six step functions over the whole batch
-template <int FN>
-int run_step64(TinyBatch64 *tb, int *conv_dev)
+int run_step64(TinyBatch64 *tb, int fn, int *conv_dev)
 {
     CHECK64(tb, "NULL handle");
     Params64 P;
     int rc = prepare64(tb, P);
     if (rc < 0) return rc;
-    const int nblocks = tb->bpad / WAVE64;
-#define TINY_F64_STEP_LAUNCH(NX, NU) \
-    if (tb->nx == NX && tb->nu == NU) hipLaunchKernelGGL((admm_f64_step_kernel<NX, NU, FN>), dim3(nblocks), dim3(WAVE64), 0, 0, P, conv_dev);
-    TINY_FOR_EACH_F64DIMS(TINY_F64_STEP_LAUNCH)
-    HIP64(hipGetLastError());
+    HIP64(launch_f64_step(fn, tb->nx, tb->nu, P, conv_dev));
     HIP64(hipDeviceSynchronize());
     return 0;
 }
@@ -1372,38 +260,10 @@ int launch_solve64(TinyBatch64 *tb, const Params64 &P, const Mpc64 *L = nullptr)
     const bool rows = rows_chosen(tb);
     if (rows && !rows_supported(tb->nx, tb->nu, tb->N))
         return fail64(TINY_BATCH_EUNSUPPORTED, "the sixteen-lane fp64 kernel has no instantiation for nx=%d nu=%d N=%d", tb->nx, tb->nu, tb->N);
-    const int nblocks = tb->bpad / WAVE64;
-    if (rows)
-    {
-        const int nrow_blocks = (tb->batch + 3) / 4;
-#define TINY_F64ROWS_LAUNCH(NX, NU, NN)                                                                                                          \
-    if (tb->nx == NX && tb->nu == NU && tb->N == NN)                                                                                             \
-    {                                                                                                                                            \
-        if (mpc) hipLaunchKernelGGL((admm_f64_rows_kernel<NX, NU, NN, false, true, Mpc64>), dim3(nrow_blocks), dim3(WAVE64), 0, 0, P, (const double *)tb->row_gains, *L); \
-        else hipLaunchKernelGGL((admm_f64_rows_kernel<NX, NU, NN>), dim3(nrow_blocks), dim3(WAVE64), 0, 0, P, (const double *)tb->row_gains);   \
-    }
-        if (rows_unrolled(tb->nx, tb->nu, tb->N)) { TINY_FOR_EACH_F64ROWS(TINY_F64ROWS_LAUNCH) }
-        else
-        {
-#define TINY_F64ROWS_RT_LAUNCH(NX, NU)                                                                                                            \
-    if (tb->nx == NX && tb->nu == NU)                                                                                                             \
-    {                                                                                                                                             \
-        if (tb->N <= 32 && mpc) hipLaunchKernelGGL((admm_f64_rows_kernel<NX, NU, 32, true, true, Mpc64>), dim3(nrow_blocks), dim3(WAVE64), 0, 0, P, (const double *)tb->row_gains, *L); \
-        else if (tb->N <= 32) hipLaunchKernelGGL((admm_f64_rows_kernel<NX, NU, 32, true>), dim3(nrow_blocks), dim3(WAVE64), 0, 0, P, (const double *)tb->row_gains); \
-        else if (mpc) return fail64(TINY_BATCH_EUNSUPPORTED, "the capacity-64 body has no on-chip closed loop");                                 \
-        else hipLaunchKernelGGL((admm_f64_rows_kernel<NX, NU, 64, true>), dim3(nrow_blocks), dim3(WAVE64), 0, 0, P, (const double *)tb->row_gains);             \
-    }
-            TINY_FOR_EACH_F64ROWS_RT(TINY_F64ROWS_RT_LAUNCH)
-        }
-    }
-    else
-    {
-        if (mpc) return fail64(TINY_BATCH_EUNSUPPORTED, "the thread-per-instance kernel has no on-chip closed loop");
-#define TINY_F64_LAUNCH(NX, NU) \
-    if (tb->nx == NX && tb->nu == NU) hipLaunchKernelGGL((admm_f64_kernel<NX, NU>), dim3(nblocks), dim3(WAVE64), 0, 0, P);
-        TINY_FOR_EACH_F64DIMS(TINY_F64_LAUNCH)
-    }
-    HIP64(hipGetLastError());
+    if (mpc && !rows) return fail64(TINY_BATCH_EUNSUPPORTED, "the thread-per-instance kernel has no on-chip closed loop");
+    if (mpc && !rows_unrolled(tb->nx, tb->nu, tb->N) && tb->N > 32) return fail64(TINY_BATCH_EUNSUPPORTED, "the capacity-64 body has no on-chip closed loop");
+    if (rows) HIP64(launch_f64_rows(tb->nx, tb->nu, tb->N, P, tb->row_gains, L));
+    else HIP64(launch_f64_thread(tb->nx, tb->nu, P));
     return 0;
 }
 
@@ -1548,18 +408,18 @@ int tiny_batch64_reset_dual_variables(TinyBatch64 *tb)
     return 0;
 }
 
-int tiny_batch64_forward_pass(TinyBatch64 *tb) { return run_step64<F64_FORWARD_PASS>(tb, nullptr); }
-int tiny_batch64_update_slack(TinyBatch64 *tb) { return run_step64<F64_UPDATE_SLACK>(tb, nullptr); }
-int tiny_batch64_update_dual(TinyBatch64 *tb) { return run_step64<F64_UPDATE_DUAL>(tb, nullptr); }
-int tiny_batch64_update_linear_cost(TinyBatch64 *tb) { return run_step64<F64_UPDATE_LINEAR_COST>(tb, nullptr); }
-int tiny_batch64_backward_pass_grad(TinyBatch64 *tb) { return run_step64<F64_BACKWARD_PASS_GRAD>(tb, nullptr); }
+int tiny_batch64_forward_pass(TinyBatch64 *tb) { return run_step64(tb, F64_FORWARD_PASS, nullptr); }
+int tiny_batch64_update_slack(TinyBatch64 *tb) { return run_step64(tb, F64_UPDATE_SLACK, nullptr); }
+int tiny_batch64_update_dual(TinyBatch64 *tb) { return run_step64(tb, F64_UPDATE_DUAL, nullptr); }
+int tiny_batch64_update_linear_cost(TinyBatch64 *tb) { return run_step64(tb, F64_UPDATE_LINEAR_COST, nullptr); }
+int tiny_batch64_backward_pass_grad(TinyBatch64 *tb) { return run_step64(tb, F64_BACKWARD_PASS_GRAD, nullptr); }
 int tiny_batch64_termination_condition(TinyBatch64 *tb, int *converged)
 {
     CHECK64(tb && converged, "NULL argument");
     HIP64(hipSetDevice(tb->device));
     int *dev = nullptr;
     HIP64(hipMalloc((void **)&dev, (size_t)tb->bpad * sizeof(int)));
-    int rc = run_step64<F64_TERMINATION_CONDITION>(tb, dev);
+    int rc = run_step64(tb, F64_TERMINATION_CONDITION, dev);
     if (rc >= 0 && hipMemcpy(converged, dev, (size_t)tb->batch * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
         rc = fail64(TINY_BATCH_EHIP, "copying the termination flags back failed");
     (void)hipFree(dev);
@@ -1584,8 +444,7 @@ int tiny_batch64_solve(TinyBatch64 *tb)
     return n > 0 ? 1 : 0;
 }
 
-// tiny_batch64_mpc_step / _mpc_step_sim: with no plant and no disturbance the launches tiny_batch64_mpc_step has always made.  (Defined here, where
-// tiny_batch64_mpc_step has been: the kernels of this unit are emitted in the order of their first launch in this file, and its code object with them.)
+// tiny_batch64_mpc_step / _mpc_step_sim: with no plant and no disturbance the launches tiny_batch64_mpc_step has always made
 static int mpc_step64(TinyBatch64 *tb, const double *w)
 {
     CHECK64(tb, "NULL handle");
@@ -1605,12 +464,7 @@ static int mpc_step64(TinyBatch64 *tb, const double *w)
         const int rp = enqueue_plant_sim64(tb, w ? tb->sim_w : nullptr, nullptr, nullptr, nullptr, 0);
         return rp < 0 ? rp : rc;
     }
-    const int nb = (tb->batch + 127) / 128;          // :110-111
-#define TINY_F64_PLANT(NX, NU)                                                                                                       \
-    if (tb->nx == NX && tb->nu == NU)                                                                                                \
-        hipLaunchKernelGGL((plant64_kernel<NX, NU>), dim3(nb), dim3(128), 0, 0, tb->arr[TINY_ARR_X], tb->arr[TINY_ARR_U], tb->mats, tb->batch, tb->bpad);
-    TINY_FOR_EACH_F64DIMS(TINY_F64_PLANT)
-    HIP64(hipGetLastError());
+    HIP64(launch_plant64(tb->nx, tb->nu, tb->arr[TINY_ARR_X], tb->arr[TINY_ARR_U], tb->mats, tb->batch, tb->bpad)); // :110-111
     return rc;
 }
 int tiny_batch64_mpc_step(TinyBatch64 *tb) { return mpc_step64(tb, nullptr); }
@@ -1731,12 +585,12 @@ int tiny_batch64_mpc_run_sim(TinyBatch64 *tb, int steps, int window_advance, con
         return enqueue_plant_sim64(tb, d_w ? d_w + (size_t)k * xrow : nullptr, d_x ? d_x + (size_t)k * xrow : nullptr, traj ? traj + (size_t)k * row_len : nullptr,
                                    window ? tb->xref_start : nullptr, adv);
     };
-    int *const start = window ? tb->xref_start : nullptr;
-    const int nb = (tb->batch + 127) / 128;
-#define TINY_F64_PLANT_RUN(NX, NU)                                                                                                            \
-    if (tb->nx == NX && tb->nu == NU)                                                                                                         \
-        hipLaunchKernelGGL((plant64_run_kernel<NX, NU>), dim3(nb), dim3(128), 0, 0, tb->arr[TINY_ARR_X], tb->arr[TINY_ARR_U], tb->mats, tb->batch, \
-                           tb->bpad, traj ? traj + (size_t)k * row_len : nullptr, start, adv);
+    // step k's plant step of a run that is not simulated: the model's, recording u.col(0) and sliding the window
+    auto plant_run = [&](int k) {
+        HIP64(launch_plant64_run(tb->nx, tb->nu, tb->arr[TINY_ARR_X], tb->arr[TINY_ARR_U], tb->mats, tb->batch, tb->bpad,
+                                 traj ? traj + (size_t)k * row_len : nullptr, window ? tb->xref_start : nullptr, adv));
+        return 0;
+    };
     if (onchip)
     {
         // all solves and the plant steps between them in one launch; the last plant step, u.col(0) of the last solve and the last slide follow
@@ -1750,7 +604,7 @@ int tiny_batch64_mpc_run_sim(TinyBatch64 *tb, int steps, int window_advance, con
             if (steps > 1)
             {
                 const Sim64 S{tb->plant_mode ? tb->plant_rows : nullptr, tb->plant_mode == 2 ? (size_t)(tb->nx + tb->nu) * 16 : 0, d_w, d_x};
-                HIP64(launch_rows64_sim(tb->nx, tb->nu, tb->N, &P, tb->row_gains, &L, S));
+                HIP64(launch_rows64_sim(tb->nx, tb->nu, tb->N, P, tb->row_gains, L, S));
             }
             else
             {
@@ -1762,10 +616,10 @@ int tiny_batch64_mpc_run_sim(TinyBatch64 *tb, int steps, int window_advance, con
         }
         else
         {
-            const int rc = launch_solve64(tb, P, &L);
+            int rc = launch_solve64(tb, P, &L);
             if (rc < 0) return rc;
-            TINY_FOR_EACH_F64DIMS(TINY_F64_PLANT_RUN)
-            HIP64(hipGetLastError());
+            rc = plant_run(k);
+            if (rc < 0) return rc;
         }
     }
     else
@@ -1782,16 +636,8 @@ int tiny_batch64_mpc_run_sim(TinyBatch64 *tb, int steps, int window_advance, con
             HIP64(hipMemsetAsync(tb->n_unsolved, 0, sizeof(int), 0));
             const int rc = launch_solve64(tb, P);
             if (rc < 0) return rc;
-            if (sim)
-            {
-                const int rp = plant_sim(k);
-                if (rp < 0) return rp;
-            }
-            else
-            {
-                TINY_FOR_EACH_F64DIMS(TINY_F64_PLANT_RUN)
-                HIP64(hipGetLastError());
-            }
+            const int rp = sim ? plant_sim(k) : plant_run(k);
+            if (rp < 0) return rp;
             if (adv) tb->xwin_valid = false;
         }
     }
@@ -1840,7 +686,7 @@ const char *tiny_batch64_kernel_name(TinyBatch64 *tb)
 {
     static thread_local char nm[64];
     if (!tb) return "";
-    const bool rows = tb->kernel_choice == 2 || (tb->kernel_choice == 0 && rows_supported(tb->nx, tb->nu, tb->N));
+    const bool rows = rows_chosen(tb);
     if (rows && !rows_unrolled(tb->nx, tb->nu, tb->N)) snprintf(nm, sizeof nm, "rows64<%d,%d,n<=%d>", tb->nx, tb->nu, tb->N <= 32 ? 32 : 64);
     else if (rows) snprintf(nm, sizeof nm, "rows64<%d,%d,%d>", tb->nx, tb->nu, tb->N);
     else snprintf(nm, sizeof nm, "thread64<%d,%d>", tb->nx, tb->nu);
@@ -1920,4 +766,3 @@ int tiny_batch64_set_status(TinyBatch64 *tb, const int *iter, const int *status,
 const char *tiny_batch64_last_error(void) { return g_err64.c_str(); }
 
 } // extern "C"
-#endif // TINY_F64SIM_UNIT

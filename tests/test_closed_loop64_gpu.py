@@ -140,6 +140,28 @@ def test_mpc_run_equals_the_oracle_loop(tinympc, oracle_mod, row):
         s.close()
 
 
+# the capacity-32 body's on-chip loop for the classes no row above holds: 5 instances (one full group of four and a tail group), the smallest horizon
+# that selects the body, max_iter = 10.  (4, 2) is also the one class whose run-time plant kernel no row reaches.
+REMAINING = [_row(f"rows64<{nx},{nu},n<=32,mpc>", (nx, nu, 3), 5, "window", 1, dict(max_iter=10), seed=6450 + i, id=f"{nx}_{nu}_3-B5-window1")
+             for i, (nx, nu) in enumerate([(12, 4), (4, 1), (8, 4), (4, 2)])]
+
+
+@pytest.mark.parametrize("row", REMAINING, ids=[r["id"] for r in REMAINING])
+def test_mpc_run_on_the_remaining_capacity_32_classes(tinympc, oracle_mod, row):
+    """a run of three and a run of five steps against the oracle's loop (the inputs are not held to helpers.closed_loop_conditions: the rows are here
+    for the instantiation they reach)"""
+    T, O, r = tinympc, oracle_mod, row
+    prob, settings, x0, ref, bnds = row_inputs(T.problems, O, r)
+    want = oracle_closed_loop(O, prob, np.float64, settings, x0, ref, bnds, STEPS, r["adv"])
+    s = _handle(T, r, prob, settings, x0, ref, bnds)
+    traj = np.concatenate([s.mpc_run_traj(K1, r["adv"]), s.mpc_run_traj(STEPS - K1, r["adv"])])
+    assert same_bits(traj, want["u0"]), f"{r['id']}: u.col(0) of the runs differs"
+    it, stt, _ = s.get_status()
+    assert np.array_equal(it, want["iter"][-1]) and np.array_equal(stt, want["status"][-1]), f"{r['id']}: iter / status of the last step"
+    _check_final(s, r, ref, want, r["id"])
+    s.close()
+
+
 @pytest.mark.parametrize("kernel", [1, 2])
 def test_window_reference_outside_a_run(tinympc, oracle_mod, kernel):
     """solve() with a window equals solve() with the gathered [B][N][nx] array uploaded through set_xref; set_xref after a window returns to the array."""

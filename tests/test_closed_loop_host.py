@@ -30,9 +30,9 @@ def test_tables_list_the_compiled_classes():
     assert sorted(n for (n,) in _macro("admm_tile16.hip", "TINY_FOR_EACH_TILE16")) == sorted(G.TILE16)
     assert set(_macro("tinympc_internal.h", "TINY_FOR_EACH_ROWDIMS")) == {d[:2] for d in G.ROWLOOP}
     assert set(_macro("tinympc_internal.h", "TINY_FOR_EACH_WAVEDIMS")) == {d[:2] for d in G.WAVE}
-    assert set(_macro("tinympc_batch64.hip", "TINY_FOR_EACH_F64DIMS")) == {d[:2] for d in G.F64}
-    assert set(_macro("tinympc_batch64.hip", "TINY_FOR_EACH_F64ROWS")) == G.F64_ROWS_UNROLLED
-    assert set(_macro("tinympc_batch64.hip", "TINY_FOR_EACH_F64DIMS")) - set(_macro("tinympc_batch64.hip", "TINY_FOR_EACH_F64ROWS_RT")) == G.F64_NO_ROWS
+    assert set(_macro("f64_internal.h", "TINY_FOR_EACH_F64DIMS")) == {d[:2] for d in G.F64}
+    assert set(_macro("f64_internal.h", "TINY_FOR_EACH_F64ROWS")) == G.F64_ROWS_UNROLLED
+    assert set(_macro("f64_internal.h", "TINY_FOR_EACH_F64DIMS")) - set(_macro("f64_internal.h", "TINY_FOR_EACH_F64ROWS_RT")) == G.F64_NO_ROWS
     import test_parity_gpu as P
     assert set(P.GENERIC_DIMS) | {(12, 4, 35)} == set(G.GENERIC)
 

@@ -1,6 +1,7 @@
-"""Static figures of the fp64 simulated closed loop's kernels (tinympc_batch64_sim.hip: the SIM instantiations of admm_f64_rows_kernel in a
-translation unit of their own) beside their MPC twins in tinympc_batch64.hip, read from the `hipcc -S` listings (build.device_asm), and the machine
-code of tinympc_batch64.hip itself, which the feature must not move.  CPU test: hipcc cross-compiles, no GPU needed."""
+"""Static figures of the fp64 simulated closed loop's kernels (admm_f64_rowsim.hip: the SIM instantiations of admm_f64_rows_kernel in a
+translation unit of their own) beside their MPC twins in admm_f64_rows.hip, read from the `hipcc -S` listings (build.device_asm), and the
+instruction streams of every kernel of the fp64 library, pinned across its units.  CPU test: hipcc cross-compiles, no GPU needed."""
+import hashlib
 import re
 from pathlib import Path
 
@@ -9,8 +10,11 @@ import pytest
 import accelerated_tinympc_amd as T
 from test_isa import kernels_of
 
-# device_isa_sha("tinympc_batch64.hip") of the commit before the simulated loop ("Closed loop against a separate plant, with disturbances")
-PARENT_ISA_SHA = "0d7d1b9fbe03a3f9"
+# the fp64 library's translation units with device code: the four kernel units and the host file's three helper kernels
+F64_UNITS = ("admm_f64_thread.hip", "admm_f64_rows.hip", "admm_f64_rowsim.hip", "admm_f64_plant.hip", "tinympc_batch64.hip")
+# fingerprint() of the library when all of it was two units (tinympc_batch64.hip, compiled a second time for the SIM instantiations): (kernels,
+# instruction lines, hash).  Moving a kernel between units, or editing host code, leaves it alone; it moves when a kernel's instructions do
+F64_FINGERPRINT = (112, 805134, "a42208fda02dcc37")
 # (NX, NU, N or capacity, RT): (VGPRs, AGPRs, bytes of scratch per lane) of the SIM instantiation as built, and of its MPC twin
 SIM = {(12, 4, 10, 0): (256, 0, 508), (12, 4, 30, 0): (256, 256, 708), (12, 4, 20, 0): (256, 256, 388), (4, 1, 10, 0): (256, 0, 0), (8, 4, 9, 0): (256, 0, 144),
        (12, 4, 32, 1): (256, 256, 160), (4, 1, 32, 1): (256, 210, 0), (8, 4, 32, 1): (256, 248, 0), (12, 2, 32, 1): (256, 256, 76), (4, 2, 32, 1): (256, 214, 0),
@@ -32,22 +36,48 @@ def figures(listing, want_sim):
     return out
 
 
+def kernel_key(name):
+    """mangled kernel name -> what it instantiates: (kernel, template literals, closed loop, simulated)"""
+    base = re.search(r"\d+([a-z_0-9]+?_kernel)", name).group(1)
+    lits = tuple(int(v) for v in re.findall(r"L[ib](\d+)E", name))
+    return (base, lits, "Mpc64" in name, "Sim64" in name)
+
+
+def fingerprint(listings):
+    """(kernels, instruction lines, sha256[:16]) over the instruction streams of every kernel of the listings, whichever unit holds it and whatever
+    it is called there: keyed by kernel_key, block labels unnumbered, the kernel's own name replaced"""
+    ks = {}
+    for text in listings:
+        for name, lines in kernels_of(text).items():
+            k = kernel_key(name)
+            assert k not in ks, k
+            ks[k] = [re.sub(r"\.LBB\d+_", ".LBB_", l).replace(name, "K") for l in lines]
+    h = hashlib.sha256()
+    for k in sorted(ks):
+        h.update((repr(k) + "\n" + "\n".join(ks[k]) + "\n").encode())
+    return len(ks), sum(map(len, ks.values())), h.hexdigest()[:16]
+
+
 @pytest.fixture(scope="module")
 def sim_listing():
-    return T.build.device_asm("tinympc_batch64_sim.hip").read_text()
+    return T.build.device_asm("admm_f64_rowsim.hip").read_text()
 
 
 @pytest.fixture(scope="module")
 def main_listing():
-    return T.build.device_asm("tinympc_batch64.hip").read_text()
+    return T.build.device_asm("admm_f64_rows.hip").read_text()
 
 
-def test_the_unit_holds_the_sim_instantiations_and_the_plant_kernel(sim_listing):
+def test_the_rowsim_unit_holds_the_sim_instantiations_and_nothing_else(sim_listing):
     names = list(kernels_of(sim_listing))
-    rows = [n for n in names if "admm_f64_rows_kernel" in n]
-    plant = [n for n in names if "plant64_sim_kernel" in n]
-    assert len(rows) == 11 and all("Mpc64" in n and "Sim64" in n for n in rows), rows
-    assert len(plant) == 7 and len(names) == 18, names      # one plant kernel per class of TINY_FOR_EACH_F64DIMS, nothing else
+    assert len(names) == 11 and all("admm_f64_rows_kernel" in n and "Mpc64" in n and "Sim64" in n for n in names), names
+
+
+def test_the_plant_unit_holds_the_three_plant_kernels_of_every_class():
+    names = list(kernels_of(T.build.device_asm("admm_f64_plant.hip").read_text()))
+    for kernel in ("plant64_kernel", "plant64_run_kernel", "plant64_sim_kernel"):  # one per class of TINY_FOR_EACH_F64DIMS
+        assert sum(kernel_key(n)[0] == kernel for n in names) == 7, (kernel, names)
+    assert len(names) == 21, names
 
 
 def test_every_mpc_instantiation_has_a_sim_twin_at_its_occupancy(sim_listing, main_listing):
@@ -74,12 +104,19 @@ def test_design_records_the_figures_beside_the_twins():
         assert re.search(rf"\| {re.escape(label)} \| {ag} / {sc} \| {mag} / {msc} \|", sec), f"DESIGN §5.6 has no row '{label} | {ag} / {sc} | {mag} / {msc}'"
 
 
-def test_the_fp64_unit_keeps_its_machine_code():
-    """the SIM flag, the second argument struct and the new host calls leave every existing fp64 kernel as it was"""
+def test_the_fp64_kernels_keep_their_instruction_streams(sim_listing, main_listing):
+    """every kernel the library had as two units is found again in today's units, instruction for instruction: a unit's layout, and so its
+    device_isa_sha, may move with what else it holds; a kernel's code may not"""
+    got = fingerprint([sim_listing if u == "admm_f64_rowsim.hip" else main_listing if u == "admm_f64_rows.hip" else T.build.device_asm(u).read_text()
+                       for u in F64_UNITS])
+    print(f"fingerprint of the fp64 units = {got}, pinned at {F64_FINGERPRINT}")
+    assert got == F64_FINGERPRINT
+
+
+def test_kernel_names_are_routed_to_their_units():
     T.build.build()
-    got = T.build.device_isa_sha("tinympc_batch64.hip")
-    print(f"device_isa_sha(tinympc_batch64.hip) = {got}, the parent's = {PARENT_ISA_SHA}")
-    assert got == PARENT_ISA_SHA
-    assert T.build.device_isa_sha("tinympc_batch64_sim.hip") != got
-    assert T.build.kernel_isa_sha("rows64<12,4,10,sim>") == T.build.device_isa_sha("tinympc_batch64_sim.hip")
-    assert T.build.kernel_isa_sha("rows64<12,4,10,mpc>") == got
+    sha = T.build.device_isa_sha
+    assert len({sha(u) for u in F64_UNITS}) == len(F64_UNITS)
+    assert T.build.kernel_isa_sha("rows64<12,4,10,sim>") == sha("admm_f64_rowsim.hip")
+    assert T.build.kernel_isa_sha("rows64<12,4,10,mpc>") == T.build.kernel_isa_sha("rows64<12,4,10>") == sha("admm_f64_rows.hip")
+    assert T.build.kernel_isa_sha("thread64<12,4>") == sha("admm_f64_thread.hip")

@@ -2738,6 +2738,61 @@ def test_fp64_vs_oracle(tinympc, oracle_mod, nx, nu, N, kernel):
         tinympc.TinyBatchSolver64(dict(prob, nx=5), 4)
 
 
+# The launcher x class pairs of the fp64 kernel units (csrc/admm_f64_*.hip) that no test above and no closed-loop test reaches, each at 5 instances
+# (one full group of four and a tail group), max_iter = 10, bitwise against the fp64 oracle.
+@pytest.mark.parametrize("nx,nu,N", [(4, 1, 3), (8, 4, 3), (12, 2, 33), (4, 4, 33)])
+def test_fp64_rows_bodies_of_the_remaining_classes(tinympc, oracle_mod, nx, nu, N):
+    """one solve on the run-time-horizon body at the smallest horizon that selects it: 3 for the capacity of 32, 33 for the capacity of 64"""
+    O, pr = oracle_mod, tinympc.problems
+    prob = pr.cartpole(N, riccati=O.riccati) if (nx, nu) == (4, 1) else pr.random_system(nx, nu, N, seed=nx * 100 + nu, riccati=O.riccati)
+    B, settings = 5, dict(O.DEFAULT_SETTINGS, max_iter=10)
+    rng = np.random.default_rng(N + nx)
+    st = O.new_state(B, nx, nu, N, np.float64)
+    for k in STATE_ORDER:
+        st[k][:] = rng.standard_normal(st[k].shape) * 0.3
+    st["residuals"][:] = rng.random((B, 4)); st["iter"][:] = 3; st["status"][:] = 11
+    bnds = tuple(np.array(v, np.float64) for v in pr.bounds_arrays(prob, np.float64))
+    xref = rng.standard_normal((N, nx)) * 0.2
+    sol = tinympc.TinyBatchSolver64(prob, B, settings=settings)
+    assert sol.kernel_name() == f"rows64<{nx},{nu},n<={32 if N <= 32 else 64}>"
+    sol.set_bounds(*bnds); sol.set_xref(xref); sol.set_state(st)
+    rc_ref = O.Oracle(prob, np.float64, settings).solve(st, *bnds, xref, nthreads=4)
+    assert sol.solve() == (1 if rc_ref else 0)
+    assert_bitwise(sol.get_state(), st, f"fp64 ({nx},{nu},{N})")
+    sol.close()
+
+
+@pytest.mark.parametrize("nx,nu", [(12, 2), (4, 2), (4, 4), (16, 4)])
+def test_fp64_step_functions_of_the_remaining_classes(tinympc, oracle_mod, nx, nu):
+    """the six step functions over a batch, as test_fp64_step_functions_batched_and_native drives them, for the classes it does not hold"""
+    O, pr = oracle_mod, tinympc.problems
+    N, B = 3, 5
+    prob = pr.random_system(nx, nu, N, seed=nx * 100 + nu, riccati=O.riccati)
+    rng = np.random.default_rng(nx + nu)
+    bnds = tuple(np.asarray(a, np.float64) * s for a, s in zip(pr.bounds_arrays(prob, np.float64), (0.2, 0.2, 1.0, 1.0)))
+    settings = dict(O.DEFAULT_SETTINGS, max_iter=10, check_termination=2, abs_pri_tol=0.5, abs_dua_tol=5.0)
+    st = O.new_state(B, nx, nu, N, np.float64)
+    for k in STATE_ORDER:
+        st[k][:] = rng.standard_normal(st[k].shape) * 0.3
+    st["iter"][:] = 4; st["status"][:] = 11
+    st["iter"][::3] = 5   # odd: termination_condition must skip these
+    st["residuals"][:] = rng.uniform(0, 1, size=(B, 4))
+    xref = rng.standard_normal((B, N, nx)) * 0.3
+    orc = O.Oracle(prob, np.float64, settings)
+    sol = tinympc.TinyBatchSolver64(prob, B, settings=settings)
+    sol.set_bounds(*bnds); sol.set_xref(xref)
+    for fn in O.Oracle.STEP_FUNCTIONS:
+        sol.set_state(st)
+        ref_rv = orc.step(fn, st, *bnds, xref)
+        rv = getattr(sol, fn)()
+        got = sol.get_state()
+        if fn == "termination_condition":
+            assert np.array_equal(rv, ref_rv)
+        for k in STATE_ORDER + ("residuals",):
+            assert np.array_equal(got[k], st[k]) and np.array_equal(np.signbit(got[k]), np.signbit(st[k])), f"{fn}: {k}"
+    sol.close()
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # one node, several GPUs, from C++ through the C-ABI (SURVEY.md section 8(e): one host thread, one handle + stream per device)
 # ---------------------------------------------------------------------------------------------------------------------

@@ -228,6 +228,23 @@ def test_simulated_run_equals_the_oracle_loop(tinympc, oracle_mod, row):
     _three_ways(tinympc, row, inp, want)
 
 
+# the capacity-32 body's SIM instantiation for the classes no row above holds: 5 instances (one full group of four and a tail group), the smallest
+# horizon that selects the body, max_iter = 10.  (4, 2) is also the one class whose simulated plant kernel no row reaches.
+REMAINING = [_row(f"rows64<{nx},{nu},n<=32,sim>", (nx, nu, 3), 5, "window", 1, "inst", True, dict(max_iter=10), id=f"{nx}_{nu}_3-B5-window1-plant_inst-w")
+             for nx, nu in [(12, 4), (4, 1), (8, 4), (4, 2)]]
+
+
+@pytest.mark.parametrize("row", REMAINING, ids=[r["id"] for r in REMAINING])
+def test_simulated_run_on_the_remaining_capacity_32_classes(tinympc, oracle_mod, row):
+    """mpc_run_sim in chunks (3, 5) against the oracle's loop (the inputs are not held to helpers.closed_loop_conditions: the rows are here for the
+    instantiation they reach)"""
+    inp = row_inputs(tinympc.problems, oracle_mod, row)
+    want = row_oracle(oracle_mod, row, inp)
+    s = _handle(tinympc, row, inp)
+    _run(s, row, inp, (K1, STEPS - K1), want, row["id"])
+    s.close()
+
+
 # ---- identities -------------------------------------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("row", [ROWS[0], ROWS[3]], ids=[ROWS[0]["id"], ROWS[3]["id"]])

@@ -31,8 +31,8 @@ def test_the_interface_is_declared_bound_and_exported(tinympc):
     for m in METHODS:
         assert callable(getattr(tinympc.TinyBatchSolver64, m, None)), m
     B = tinympc.build
-    assert "tinympc_batch64_sim.hip" in B.SOURCES and B.INCLUDED_SOURCES["tinympc_batch64_sim.hip"] == ["tinympc_batch64.hip"]
-    assert B.KERNEL_SOURCES["rows64"] == "tinympc_batch64.hip"
+    assert "admm_f64_rowsim.hip" in B.SOURCES and B.INCLUDED_SOURCES["admm_f64_rowsim.hip"] == ["admm_f64_rows.hip"]
+    assert B.KERNEL_SOURCES["rows64"] == "admm_f64_rows.hip"
 
 
 def test_rows_are_the_issue_s_table():
