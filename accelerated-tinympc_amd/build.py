@@ -17,9 +17,9 @@ CSRC = PKG / "csrc"
 LIB = PKG / "lib" / "libtinympc_hip.so"
 WRAPPER_LIB = PKG / "lib" / "libtinympc_wrapper.so"  # same-name twin of the reference's generated wrapper library
 WRAPPER64_LIB = PKG / "lib" / "libtinympc_wrapper64.so"  # the native names (tiny_solve, forward_pass, ...) for tinytype = double
-SOURCES = ["tinympc_batch.hip", "tinympc_batch64.hip", "admm_f64_thread.hip", "admm_f64_rows.hip", "admm_f64_rowsim.hip", "admm_f64_plant.hip", "admm_stream.hip", "admm_generic.hip", "admm_rowlane.hip", "admm_rowsim.hip", "admm_rowloop.hip", "admm_quadlane.hip", "admm_tile16.hip", "admm_tile16_pi.hip", "admm_wave.hip", "admm_waveres.hip", "admm_tile48.hip", "admm_steps.hip", "dispatch_order.hip", "riccati.cpp", "riccati_batch.hip"]
+SOURCES = ["tinympc_batch.hip", "batch_helpers.hip", "tinympc_batch64.hip", "batch64_helpers.hip", "admm_f64_thread.hip", "admm_f64_rows.hip", "admm_f64_rowsim.hip", "admm_f64_plant.hip", "admm_stream.hip", "admm_generic.hip", "admm_rowlane.hip", "admm_rowsim.hip", "admm_rowloop.hip", "admm_quadlane.hip", "admm_tile16.hip", "admm_tile16_pi.hip", "admm_wave.hip", "admm_waveres.hip", "admm_tile48.hip", "admm_steps.hip", "dispatch_order.hip", "riccati.cpp", "riccati_batch.hip"]
 WRAPPER_SRCS = [CSRC / "wrapper_compat.cpp", CSRC / "admm_compat.cpp"]
-HEADERS = [CSRC / "tinympc_internal.h", CSRC / "eigen_orders.h", CSRC / "rowlane_math.h", CSRC / "tile_math.h", CSRC / "wave_math.h", CSRC / "dpp_ops_gen.h", CSRC / "f64_internal.h", CSRC / "f64_math.h", PKG.parent / "include" / "tinympc_batch.h", PKG.parent / "include" / "tinympc_batch64.h"]
+HEADERS = [CSRC / "tinympc_internal.h", CSRC / "batch_helpers.h", CSRC / "eigen_orders.h", CSRC / "rowlane_math.h", CSRC / "tile_math.h", CSRC / "wave_math.h", CSRC / "dpp_ops_gen.h", CSRC / "f64_internal.h", CSRC / "f64_math.h", PKG.parent / "include" / "tinympc_batch.h", PKG.parent / "include" / "tinympc_batch64.h"]
 # -ffp-contract=off : exact arithmetic must not fuse a*b+c; the fast paths call fma explicitly
 # -fno-slp-vectorize: hipcc otherwise pairs scalar fp32 adds into v_pk_add_f32 (+ v_mov to build the pairs), which on
 #                     gfx950 is slower than two plain v_add_f32 (measured, tools/micro/*.hip)

@@ -1032,7 +1032,7 @@ __global__ __launch_bounds__(WAVE * TILE16_WAVES, 1) void admm_tile16_kernel(con
         const bool solved = st == TINY_STATUS_SOLVED_;
         // [x_0 ; u_0] of the solve that just finished, in the solver's own arithmetic — from the d its last FORWARD sweep used, i.e. before the
         // deferred backward sweep below replaces it (the live-out's order) —; then the plant step in the plant kernel's
-        // (plant_step_kernel, tinympc_batch.hip: separately rounded products; Adyn x0 through Eigen's GEMV accumulator from +0,
+        // (plant_step_kernel, batch_helpers.hip: separately rounded products; Adyn x0 through Eigen's GEMV accumulator from +0,
         // Bdyn u_0 the lazy product's sequential sum — rowlane_math.h plant_step)
         float un, xn_[3];
         M.lqr(x0, dr[0], un, xn_);

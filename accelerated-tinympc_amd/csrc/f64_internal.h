@@ -1,4 +1,4 @@
-// f64_internal.h — what the host file of the fp64 library (tinympc_batch64.hip) and its kernel units (admm_f64_*.hip) share: the kernel argument
+// f64_internal.h — what the host file of the fp64 library (tinympc_batch64.hip) and its kernel units (admm_f64_*.hip, batch64_helpers.hip) share: the kernel argument
 // structs, the lists of instantiated problem classes, and one typed launcher per kernel family.  Every launcher enqueues on the null stream and
 // answers hipErrorInvalidValue where there is no instantiation for the class; the host turns that into its own messages.
 #pragma once
@@ -96,4 +96,9 @@ hipError_t launch_rows64_sim(int nx, int nu, int N, const Params64 &P, const dou
 hipError_t launch_plant64(int nx, int nu, double *X, const double *U, const double *mats, int batch, int bpad);
 hipError_t launch_plant64_run(int nx, int nu, double *X, const double *U, const double *mats, int batch, int bpad, double *u0_row, int *start, int window_advance);
 hipError_t launch_plant64_sim(int nx, int nu, const PlantSim64 &a);
+// batch64_helpers.hip: host layout [nb][steps][dim] (nb = 1: shared, stride 1) into steps [step0, step0 + nsteps) of device [steps][dim][stride]; all steps
+// of the device array back into the host layout; a window reference gathered into the per-instance array [N][nx][bpad] the one-solve kernels read
+hipError_t launch_pack64(const double *src, double *dst, int nb, int steps, int dim, int stride, int step0, int nsteps);
+hipError_t launch_unpack64(const double *src, double *dst, int nb, int steps, int dim, int stride);
+hipError_t launch_gather_window64(const double *table, const int *start, double *dst, int rows, int N, int nx, int batch, int bpad);
 } // namespace tinympc64

@@ -226,7 +226,7 @@ __device__ __forceinline__ void lqr_step(const RowGains<NX, NU> &G, bool is_x, b
 
 // plant step of the closed loop (examples/quadrotor_hovering.cpp:110-111): xn = Adyn*x + Bdyn*u with sv = [x ; u], always in
 // the reference's own order whatever the arithmetic mode of the solver, so that the on-chip closed loop and the
-// step-by-step one (plant_step_kernel, tinympc_batch.hip) continue from identical states.  The order is Eigen's for
+// step-by-step one (plant_step_kernel, batch_helpers.hip) continue from identical states.  The order is Eigen's for
 // "x1 = work.Adyn * x0 + work.Bdyn * work.u.col(0)" (pinned against that expression compiled from the reference, tests/test_oracle.py:
 // test_plant_step_bit_exact_vs_compiled_reference): a product whose rows and depth are both >= 8 goes through the column-major GEMV kernel, whose row
 // accumulator starts at +0 (visible in the sign of a zero result); otherwise the lazy product's plain sequential sum.

@@ -1,11 +1,12 @@
 // tinympc_batch.hip — host side of the C-ABI declared in include/tinympc_batch.h:
-// device-resident batched workspace, layout conversion kernels, gain packing and kernel dispatch.
-// The solver kernels live in admm_rowlane.hip (state on chip) and admm_stream.hip (state in HBM).
+// device-resident batched workspace, gain packing and kernel dispatch.  Host code only: the solver kernels live in
+// admm_rowlane.hip (state on chip), admm_stream.hip (state in HBM) and their siblings, the helper kernels (layout
+// conversion, plant step, model records, guard zones) in batch_helpers.hip, each behind a typed launcher.
 //
 // There is deliberately NO CPU fallback in this library: every entry point that computes
 // launches a HIP kernel and reports HIP failures as TINY_BATCH_EHIP.
 #include "../../include/tinympc_batch.h"
-#include "eigen_orders.h"
+#include "batch_helpers.h"
 #include "tinympc_internal.h"
 
 #include <cmath>
@@ -60,23 +61,11 @@ int fail(int code, const char *fmt, ...)
 // with a quiet-NaN pattern.  An out-of-bounds WRITE of any kernel then lands in a guard and tiny_batch_debug_check() counts the
 // damaged words; an out-of-bounds READ returns NaN, which no parity test survives.  It is a mode of the same library — the kernels
 // are the shipped ones, unchanged — used by tests/test_parity_gpu.py::test_debug_guard_zones_stay_intact over every kernel family.
+// (kGuard, the floats on each side, and the fill and count kernels: batch_helpers.h)
 // ---------------------------------------------------------------------------------------------
-constexpr size_t kGuard = 256;               // floats on each side (1 KB: keeps the 256-byte alignment of hipMalloc)
-constexpr unsigned kGuardWord = 0x7fc0dea1u; // a quiet NaN
 std::mutex g_guard_mu;
 std::map<void *, size_t> g_guarded;          // user pointer -> user bytes
 bool g_guards_on = false;
-
-__global__ void guard_fill_kernel(unsigned *p, size_t nwords)
-{
-    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < nwords; e += (size_t)gridDim.x * blockDim.x) p[e] = kGuardWord;
-}
-__global__ void guard_count_kernel(const unsigned *p, size_t nwords, unsigned long long *bad)
-{
-    unsigned long long n = 0;
-    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < nwords; e += (size_t)gridDim.x * blockDim.x) n += p[e] != kGuardWord;
-    if (n) atomicAdd(bad, n);
-}
 
 hipError_t guarded_malloc(void **out, size_t bytes)
 {
@@ -85,9 +74,9 @@ hipError_t guarded_malloc(void **out, size_t bytes)
     char *raw = nullptr;
     hipError_t e = hipMalloc((void **)&raw, user + 2 * kGuard * sizeof(float));
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(guard_fill_kernel, dim3(1), dim3(256), 0, nullptr, (unsigned *)raw, kGuard);
-    hipLaunchKernelGGL(guard_fill_kernel, dim3(1), dim3(256), 0, nullptr, (unsigned *)(raw + kGuard * sizeof(float) + user), kGuard);
-    e = hipStreamSynchronize(nullptr);
+    e = launch_guard_fill((unsigned *)raw, kGuard, nullptr);
+    if (e == hipSuccess) e = launch_guard_fill((unsigned *)(raw + kGuard * sizeof(float) + user), kGuard, nullptr);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
     if (e != hipSuccess) { (void)hipFree(raw); return e; }
     *out = raw + kGuard * sizeof(float);
     std::lock_guard<std::mutex> lk(g_guard_mu);
@@ -109,366 +98,10 @@ hipError_t guarded_free(void *p)
     return hipFree(p);
 }
 
-enum { LAYOUT_TILE = 0, LAYOUT_ROW = 1 };
 enum { VAR_AUTO = 0, VAR_STREAM = 1, VAR_ROW_EXACT = 2, VAR_ROW_FAST = 3, VAR_GENERIC = 4 }; // 4: admm_generic.hip, exact arithmetic for any eligible class
 
 // The solve kernels; kKernelTraits below says everything the host code needs to know about each of them.
 enum class Kernel { Rowlane, Rowloop, Rowstream, Wavestream, Quadlane, Tile16, Waveres, Tile48, Stream, Generic };
-
-// ---------------------------------------------------------------------------------------------
-// Element addressing of the two device layouts.  `fam` 0 = state-type (nx rows, N steps),
-// 1 = input-type (nu rows, N-1 steps).
-//   TILE (admm_stream.hip):  x-family [ntiles][N][64][NXC], u-family [ntiles][N-1][64][NUC]
-//   ROW  (row / wave kernels): pair array [batch_pad4][N][rw], rows [0,nx) state member, [nx,nx+nu) input member;
-//        rw = 16 (one DPP row per instance) or 64 (one wavefront per instance, admm_wave.hip)
-// ---------------------------------------------------------------------------------------------
-struct Geo
-{
-    int nx, nu, N, NXC, NUC;
-    int rw; // lanes per instance-step of the ROW layout: 16 (one DPP row) or 64 (one wavefront, 16 < nx + nu <= 64)
-};
-
-__device__ __forceinline__ long long idx_tile(const Geo g, int fam, int b, int step, int row)
-{
-    const int tile = b / TILE, c = b % TILE, lane = (row & 3) * 16 + c, ch = row >> 2;
-    const int steps = fam ? g.N - 1 : g.N, NC = fam ? g.NUC : g.NXC;
-    return (((long long)tile * steps + step) * WAVE + lane) * NC + ch;
-}
-__device__ __forceinline__ long long idx_row(const Geo g, int fam, int b, int step, int row)
-{
-    return ((long long)b * g.N + step) * g.rw + (fam ? g.nx + row : row);
-}
-__device__ __forceinline__ long long idx_of(int layout, const Geo g, int fam, int b, int step, int row)
-{
-    return layout == LAYOUT_ROW ? idx_row(g, fam, b, step, row) : idx_tile(g, fam, b, step, row);
-}
-
-// element access of a device-layout array: fp32, or IEEE binary16 when the handle stores fp16 (ROW layout only)
-__device__ __forceinline__ void put_elem(float *dst, long long i, float v, int h16)
-{
-    if (h16) reinterpret_cast<_Float16 *>(dst)[i] = (_Float16)v; // round to nearest even
-    else dst[i] = v;
-}
-__device__ __forceinline__ float get_elem(const float *src, long long i, int h16)
-{
-    return h16 ? (float)reinterpret_cast<const _Float16 *>(src)[i] : src[i];
-}
-
-// host-layout src [cnt][nsteps][dim] (cnt = 1: shared by all instances)  ->  device layout, steps [step0, step0+nsteps)
-// of instances [0, nb).  Rows/instances beyond the source are left untouched (they were zeroed at allocation).
-// `mirror` (may be NULL): a plain copy of src, element for element — set_x0_device fills x.col(0) and the [B][nx] state buffer of the closed loop in
-// ONE launch (round 4: it was a device-to-device copy plus this kernel)
-__global__ void pack_kernel(const float *__restrict__ src, float *__restrict__ dst, int layout, Geo g, int fam, int nb,
-                            int shared, int step0, int nsteps, int h16, float *__restrict__ mirror = nullptr)
-{
-    const int dim = fam ? g.nu : g.nx;
-    const long long total = (long long)nb * nsteps * dim;
-    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x)
-    {
-        const int row = (int)(e % dim);
-        const long long t = e / dim;
-        const int s = (int)(t % nsteps), b = (int)(t / nsteps);
-        const float val = src[((long long)(shared ? 0 : b) * nsteps + s) * dim + row];
-        put_elem(dst, idx_of(layout, g, fam, b, step0 + s, row), val, h16);
-        if (mirror) mirror[e] = val;
-    }
-}
-
-__global__ void unpack_kernel(const float *__restrict__ src, float *__restrict__ dst, int layout, Geo g, int fam, int nb,
-                              int step0, int nsteps, int h16)
-{
-    const int dim = fam ? g.nu : g.nx;
-    const long long total = (long long)nb * nsteps * dim;
-    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x)
-    {
-        const int row = (int)(e % dim);
-        const long long t = e / dim;
-        const int s = (int)(t % nsteps), b = (int)(t / nsteps);
-        dst[e] = get_elem(src, idx_of(layout, g, fam, b, step0 + s, row), h16);
-    }
-}
-
-// zero steps [step0, step0+nsteps) of one member of a device array
-__global__ void zero_kernel(float *__restrict__ dst, int layout, Geo g, int fam, int nb, int step0, int nsteps, int h16)
-{
-    const int dim = fam ? g.nu : g.nx;
-    const long long total = (long long)nb * nsteps * dim;
-    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x)
-    {
-        const int row = (int)(e % dim);
-        const long long t = e / dim;
-        put_elem(dst, idx_of(layout, g, fam, (int)(t / nsteps), step0 + (int)(t % nsteps), row), 0.f, h16);
-    }
-}
-
-// the duals pair g | y between fp32 and binary16 (tiny_batch_set_storage(tb, 16) is a preference: the width follows the kernel a call resolves to)
-__global__ void dual_width_kernel(const float *__restrict__ src, float *__restrict__ dst, long long n, int to32)
-{
-    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x)
-    {
-        if (to32) dst[e] = (float)reinterpret_cast<const _Float16 *>(src)[e];
-        else reinterpret_cast<_Float16 *>(dst)[e] = (_Float16)src[e]; // round to nearest even, like every store of the 16-bit mode
-    }
-}
-
-// x0 <- Adyn*x0 + Bdyn*u.col(0)   (quadrotor_hovering.cpp:110-111), and x.col(0) <- x0 (:95).
-// One thread per instance; matrices column-major in global memory (tiny, cache resident).
-// Summation order = Eigen's for that expression (pinned bit for bit against that expression compiled from the reference, tests/test_oracle.py:
-// test_plant_step_bit_exact_vs_compiled_reference): dst = Adyn*x0, then dst += Bdyn*u0; a product whose rows and depth are both >= 8 takes the column-major
-// GEMV kernel (row accumulator starting at +0, products added in ascending column order), a smaller one the lazy product in the order of its
-// row count (eigen_orders.h: sequential for nx % 4 == 0, the halving tree for nx = 2, 3, the packet tree for nx = 1)
-__device__ __forceinline__ void plant_step_one(int b, float *__restrict__ x0buf, float *__restrict__ xarr, const float *__restrict__ uarr,
-                                               const float *__restrict__ A, const float *__restrict__ Bm, int *__restrict__ wstart,
-                                               int window_advance, int layout, Geo g, int h16, const float *__restrict__ w = nullptr,
-                                               float *__restrict__ x_traj = nullptr)
-{
-    const int nx = g.nx, nu = g.nu;
-    const float *x0 = x0buf + (long long)b * nx;
-    const bool gemv_a = nx >= 8, gemv_b = nx >= 8 && nu >= 8;
-    float xn[64], u0[64], t[64];
-    for (int m = 0; m < nu; m++) u0[m] = get_elem(uarr, idx_of(layout, g, 1, b, 0, m), h16);
-    for (int i = 0; i < nx; i++)
-    {
-        float acc, acc2;
-        if (gemv_a)
-        {
-            acc = 0.f + A[i] * x0[0];
-            for (int k = 1; k < nx; k++) acc += A[k * nx + i] * x0[k];
-        }
-        else acc = gen_row_dot(A, nx, nx, i, x0, t);
-        if (gemv_b)
-        {
-            acc2 = 0.f + Bm[i] * u0[0];
-            for (int m = 1; m < nu; m++) acc2 += Bm[m * nx + i] * u0[m];
-        }
-        else acc2 = gen_row_dot(Bm, nx, nu, i, u0, t);
-        xn[i] = acc + acc2;
-        if (w) xn[i] = xn[i] + w[(long long)b * nx + i]; // the disturbance: one separately rounded add behind the product
-    }
-    for (int i = 0; i < nx; i++)
-    {
-        x0buf[(long long)b * nx + i] = xn[i];
-        if (x_traj) x_traj[(long long)b * nx + i] = xn[i];
-        put_elem(xarr, idx_of(layout, g, 0, b, 0, i), xn[i], h16);
-    }
-    if (wstart && window_advance) wstart[b] += window_advance;
-}
-
-__global__ void plant_step_kernel(float *__restrict__ x0buf, float *__restrict__ xarr, const float *__restrict__ uarr,
-                                  const float *__restrict__ A, const float *__restrict__ Bm, int *__restrict__ wstart,
-                                  int window_advance, int batch, int layout, Geo g, int h16)
-{
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= batch) return;
-    plant_step_one(b, x0buf, xarr, uarr, A, Bm, wstart, window_advance, layout, g, h16);
-}
-
-// ... with per-instance models: the instance's own Adyn / Bdyn from its record (Kinf | Pinf | Quu_inv | AmBKt | Adyn | Bdyn | Q, pm_gen_floats apart)
-__global__ void plant_step_pm_kernel(float *__restrict__ x0buf, float *__restrict__ xarr, const float *__restrict__ uarr,
-                                     const float *__restrict__ recs, int *__restrict__ wstart, int window_advance, int batch, int layout, Geo g, int h16)
-{
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= batch) return;
-    const int nx = g.nx, nu = g.nu;
-    const float *r = recs + (size_t)b * pm_gen_floats(nx, nu) + nu * nx + nx * nx + nu * nu + nx * nx;
-    plant_step_one(b, x0buf, xarr, uarr, r, r + nx * nx, wstart, window_advance, layout, g, h16);
-}
-
-// ... of a simulated closed loop (tiny_batch_set_plant, tiny_batch_mpc_step_sim_async): A / Bm are the plant's matrices (one pair, or one per instance
-// a_stride / b_stride floats apart), the model record's where recs is set, else the shared model's; w and x_traj are this step's [batch][nx] rows or NULL
-__global__ void plant_step_sim_kernel(float *__restrict__ x0buf, float *__restrict__ xarr, const float *__restrict__ uarr, const float *__restrict__ A,
-                                      const float *__restrict__ Bm, unsigned a_stride, unsigned b_stride, const float *__restrict__ recs,
-                                      const float *__restrict__ w, float *__restrict__ x_traj, int *__restrict__ wstart, int window_advance, int batch,
-                                      int layout, Geo g, int h16)
-{
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= batch) return;
-    const int nx = g.nx, nu = g.nu;
-    if (recs)
-    {
-        A = recs + (size_t)b * pm_gen_floats(nx, nu) + nu * nx + nx * nx + nu * nu + nx * nx;
-        Bm = A + nx * nx;
-    }
-    else
-    {
-        A += (size_t)b * a_stride;
-        Bm += (size_t)b * b_stride;
-    }
-    plant_step_one(b, x0buf, xarr, uarr, A, Bm, wstart, window_advance, layout, g, h16, w, x_traj);
-}
-
-// Per-instance models (tiny_batch_set_models_device): the caller's eight [B] arrays into one record per instance in the run-time-dimension kernel's
-// order Kinf | Pinf | Quu_inv | AmBKt | Adyn | Bdyn | Q (plain copies), rho into its own array
-__global__ void models_gather_kernel(const float *__restrict__ rho, const float *__restrict__ K, const float *__restrict__ Pf, const float *__restrict__ Qi,
-                                     const float *__restrict__ Am, const float *__restrict__ A, const float *__restrict__ Bm, const float *__restrict__ Q,
-                                     float *__restrict__ dst, float *__restrict__ dst_rho, int batch, int nx, int nu)
-{
-    const int G = pm_gen_floats(nx, nu);
-    const long long total = (long long)batch * G;
-    const int sz[7] = {nu * nx, nx * nx, nu * nu, nx * nx, nx * nx, nx * nu, nx};
-    const float *src[7] = {K, Pf, Qi, Am, A, Bm, Q};
-    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x)
-    {
-        const long long b = e / G;
-        int o = (int)(e % G), k = 0;
-        while (o >= sz[k]) o -= sz[k++];
-        dst[e] = src[k][b * sz[k] + o];
-        if (o == 0 && k == 0) dst_rho[b] = rho[b];
-    }
-}
-
-// ... and from those records the gain rows of the 16-lane kernel, element for element what pack_gains writes for one shared model (rows 0 .. 3nx + 2nu:
-// M1, M2, M3, M45, Q, PT; the optional-term rows are not instantiated with per-instance models).  fast = 1: the fma form (u rows of M1 and x rows of M45
-// hold -K; the exact form holds +K and the kernel negates the sum)
-__global__ void models_pack_row_kernel(const float *__restrict__ recs, float *__restrict__ dst, int batch, int nx, int nu, int fast)
-{
-    const int G = pm_gen_floats(nx, nu), R = pm_row_floats(nx, nu);
-    const long long total = (long long)batch * R;
-    const float sg = fast ? -1.f : 1.f;
-    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x)
-    {
-        const long long b = e / R;
-        const int o = (int)(e % R), reg = o / 16, r = o % 16;
-        const float *K = recs + b * G, *Pf = K + nu * nx, *Qi = Pf + nx * nx, *Am = Qi + nu * nu, *A = Am + nx * nx, *Bm = A + nx * nx, *Q = Bm + nx * nu;
-        const bool isx = r < nx, isu = r >= nx && r < nx + nu;
-        const int mr = r - nx;
-        float v = 0.f;
-        if (reg < nx) v = isx ? A[reg * nx + r] : (isu ? sg * K[reg * nu + mr] : 0.f); // M1: A(r,k) | K(m,k) (exact), -K(m,k) (fast)
-        else if (reg < nx + nu) v = isx ? Bm[(reg - nx) * nx + r] : 0.f;                // M2: B(r,m)
-        else if (reg < 2 * nx + nu)
-        {
-            const int k = reg - nx - nu;                                                // M3: AmBKt(r,k) | B(k,m)
-            v = isx ? Am[k * nx + r] : (isu ? Bm[mr * nx + k] : 0.f);
-        }
-        else if (reg < 2 * nx + 2 * nu)
-        {
-            const int mm = reg - 2 * nx - nu;                                           // M45: K(m,r) (exact), -K(m,r) (fast) | Quu_inv(mr,m)
-            v = isx ? sg * K[r * nu + mm] : (isu ? Qi[mm * nu + mr] : 0.f);
-        }
-        else if (reg == 2 * nx + 2 * nu) v = isx ? Q[r] : 0.f;                          // Q(r)
-        else v = isx ? Pf[r * nx + (reg - 2 * nx - 2 * nu - 1)] : 0.f;                  // PT[k]: Pinf(k,r)
-        dst[e] = v;
-    }
-}
-
-// tiny_batch_set_systems: fp64 systems and their Riccati caches into the fp32 arrays of tiny_batch_set_models_device, with the conventions of
-// problems.with_cache(): rho, Kinf ..., Adyn, Bdyn cast, Q = (float)(Q + rho) formed in fp64
-__global__ void systems_to_models_kernel(const double *__restrict__ rho, const double *__restrict__ K, const double *__restrict__ Pf, const double *__restrict__ Qi,
-                                         const double *__restrict__ Am, const double *__restrict__ A, const double *__restrict__ Bm, const double *__restrict__ Q,
-                                         float *__restrict__ dst, int batch, int nx, int nu)
-{
-    // dst: rho [B] | Kinf | Pinf | Quu_inv | AmBKt | Adyn | Bdyn | Q, each [B][...]
-    const int sz[8] = {1, nu * nx, nx * nx, nu * nu, nx * nx, nx * nx, nx * nu, nx};
-    const double *src[8] = {rho, K, Pf, Qi, Am, A, Bm, Q};
-    const long long total = (long long)batch * (1 + pm_gen_floats(nx, nu));
-    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x)
-    {
-        long long o = e;
-        int k = 0;
-        while (o >= (long long)batch * sz[k]) o -= (long long)batch * sz[k++];
-        double v = src[k][o];
-        if (k == 7) v = v + rho[o / nx];
-        dst[e] = (float)v;
-    }
-}
-
-// A stored {lo, hi} on which v_med3_f32 and the reference's compare-selects can break a tie between zeros differently (tinympc_internal.h: box_project):
-// lo = -0 under hi > 0 (t = +0), or hi = +0 over lo < 0 or lo = -0 (t = -0), as the table holds them — folded, rounded to the storage format.  Every other
-// pair with a zero in it gives the same bits either way — the box [+0, +0] of bounds never set among them — and a disabled bound is +-inf
-__host__ __device__ inline bool zero_tie_bound(float lo, float hi)
-{
-    const bool lo_neg0 = lo == 0.f && __builtin_signbit(lo), hi_pos0 = hi == 0.f && !__builtin_signbit(hi);
-    return (lo_neg0 && hi > 0.f) || (hi_pos0 && (lo < 0.f || lo_neg0));
-}
-
-// per-instance bounds table of the ROW layout: dst[b][step][r] = {min(lo, hi), hi}, +-inf where a bound is disabled or the
-// row carries nothing.  Sources are the canonical inputs ([B or 1][steps][dim], NULL = not set = 0).
-__global__ void bounds_table_kernel(const float *__restrict__ xmin, const float *__restrict__ xmax, const float *__restrict__ umin,
-                                    const float *__restrict__ umax, int sh_x, int sh_u, float *__restrict__ dst, Geo g, int nb,
-                                    int en_state, int en_input, int h16, int *__restrict__ zero_ties)
-{
-    const long long total = (long long)nb * g.N * g.rw;
-    const float inf = __builtin_inff();
-    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x)
-    {
-        const int r = (int)(e % g.rw);
-        const long long t = e / g.rw;
-        const int i = (int)(t % g.N), b = (int)(t / g.N);
-        float lo = -inf, hi = inf;
-        if (r < g.nx && en_state)
-        {
-            const long long o = ((long long)(sh_x ? 0 : b) * g.N + i) * g.nx + r;
-            lo = xmin ? xmin[o] : 0.f; hi = xmax ? xmax[o] : 0.f;
-        }
-        else if (r >= g.nx && r < g.nx + g.nu && i < g.N - 1 && en_input)
-        {
-            const long long o = ((long long)(sh_u ? 0 : b) * (g.N - 1) + i) * g.nu + (r - g.nx);
-            lo = umin ? umin[o] : 0.f; hi = umax ? umax[o] : 0.f;
-        }
-        lo = lo < hi ? lo : hi;
-        if (h16)
-        {
-            reinterpret_cast<_Float16 *>(dst)[2 * e] = (_Float16)lo;
-            reinterpret_cast<_Float16 *>(dst)[2 * e + 1] = (_Float16)hi;
-            lo = (float)(_Float16)lo; hi = (float)(_Float16)hi;
-        }
-        else { dst[2 * e] = lo; dst[2 * e + 1] = hi; }
-        if (zero_tie_bound(lo, hi)) *zero_ties = 1; // (every writer stores the same word)
-    }
-}
-
-// Tile images of the ROW tables for the LDS-DMA rings of admm_tile16_pi.hip: dst[tile][step][piece][lane = 16 g + c] (float4) = words 4 (P g + piece) .. + 3 of
-// row `step` of instance 16 tile + c, P = pieces per lane (1: the 16-float reference rows, 2: the 32-float {lo, hi} rows) — byte for byte what a ring slot
-// holds, so that one DMA reads 1 KB of consecutive memory.  Columns past the batch repeat its last instance (they are computed and never stored).
-__global__ void tile16_image_kernel(const float4 *__restrict__ src, float4 *__restrict__ dst, int nb, int N, int pieces, long long inst_stride_f4)
-{
-    const long long total = (long long)((nb + 15) / 16) * N * pieces * 64;
-    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x)
-    {
-        const int lane = (int)(e & 63), piece = (int)((e >> 6) % pieces);
-        const long long t = e / (64 * pieces);
-        const int step = (int)(t % N), g = lane >> 4, c = lane & 15;
-        long long inst = (t / N) * 16 + c;
-        inst = inst < nb ? inst : nb - 1;
-        dst[e] = src[inst * inst_stride_f4 + (long long)step * 4 * pieces + pieces * g + piece];
-    }
-}
-
-// Do the per-instance ROW tables change along the horizon?  vary[0]: the {lo, hi} table [nb][N][16] (x rows over all N steps, u rows over the
-// N - 1 steps that have an input), vary[1]: the reference [nb][N][16].  Bit patterns are compared.  admm_tile16_pi.hip keeps a table that does
-// not as ONE resident row per instance instead of streaming N of them through its ring every iteration (RowParams::pi_flags).
-__global__ void rows_vary_kernel(const float2 *__restrict__ bounds, const float *__restrict__ xref, int nb, int N, int nx, int nu, int *__restrict__ vary)
-{
-    const long long total = (long long)nb * 16;
-    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x)
-    {
-        const int r = (int)(e & 15);
-        const long long b = e >> 4;
-        if (bounds && r < nx + nu)
-        {
-            const int steps = r < nx ? N : N - 1;
-            const unsigned long long *p = reinterpret_cast<const unsigned long long *>(bounds) + (b * N) * 16 + r;
-            bool differ = false;
-            for (int i = 1; i < steps; i++) differ |= p[(size_t)i * 16] != p[0];
-            if (differ) vary[0] = 1;
-        }
-        if (xref && r < nx)
-        {
-            const unsigned *p = reinterpret_cast<const unsigned *>(xref) + (b * N) * 16 + r;
-            bool differ = false;
-            for (int i = 1; i < N; i++) differ |= p[(size_t)i * 16] != p[0];
-            if (differ) vary[1] = 1;
-        }
-    }
-}
-
-int grid_for(long long total, int block = 256)
-{
-    long long gsz = (total + block - 1) / block;
-    if (gsz > 8192) gsz = 8192;
-    if (gsz < 1) gsz = 1;
-    return (int)gsz;
-}
 
 // pair index of each work array in the ROW layout: x,u | q,r | p,d | v,z | vnew,znew | g,y
 const int kPairOf[TINY_ARR_COUNT] = {0, 0, 1, 1, 2, 2, 3, 4, 3, 4, 5, 5};
@@ -694,28 +327,20 @@ void free_layout(TinyBatch *tb, int layout)
         for (int id = 0; id < TINY_ARR_COUNT; id++) { (void)guarded_free(tb->arr[id]); tb->arr[id] = nullptr; }
 }
 
+// the copy kernels of batch_helpers.hip on the handle's stream, with its geometry and the element type of the array
 int launch_pack(TinyBatch *tb, const float *src, float *dst, int layout, int fam, int nb, bool shared, int step0, int nsteps, float *mirror = nullptr)
 {
-    const long long total = (long long)nb * nsteps * (fam ? tb->nu : tb->nx);
-    hipLaunchKernelGGL(pack_kernel, dim3(grid_for(total)), dim3(256), 0, tb->stream, src, dst, layout, geo(tb), fam, nb,
-                       shared ? 1 : 0, step0, nsteps, h16_at(tb, layout, dst), mirror);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(tinympc::launch_pack(src, dst, layout, geo(tb), fam, nb, shared ? 1 : 0, step0, nsteps, h16_at(tb, layout, dst), mirror, tb->stream));
     return 0;
 }
 int launch_unpack(TinyBatch *tb, const float *src, float *dst, int layout, int fam, int nb, int step0, int nsteps)
 {
-    const long long total = (long long)nb * nsteps * (fam ? tb->nu : tb->nx);
-    hipLaunchKernelGGL(unpack_kernel, dim3(grid_for(total)), dim3(256), 0, tb->stream, src, dst, layout, geo(tb), fam, nb,
-                       step0, nsteps, h16_at(tb, layout, src));
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(tinympc::launch_unpack(src, dst, layout, geo(tb), fam, nb, step0, nsteps, h16_at(tb, layout, src), tb->stream));
     return 0;
 }
 int launch_zero(TinyBatch *tb, float *dst, int layout, int fam, int step0, int nsteps)
 {
-    const long long total = (long long)tb->batch * nsteps * (fam ? tb->nu : tb->nx);
-    hipLaunchKernelGGL(zero_kernel, dim3(grid_for(total)), dim3(256), 0, tb->stream, dst, layout, geo(tb), fam, tb->batch,
-                       step0, nsteps, h16_at(tb, layout, dst));
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(tinympc::launch_zero(dst, layout, geo(tb), fam, tb->batch, step0, nsteps, h16_at(tb, layout, dst), tb->stream));
     return 0;
 }
 
@@ -1013,12 +638,10 @@ int prepare_inputs(TinyBatch *tb, int layout)
             if (!tb->zero_ties_dev) TRY(dev_alloc_zero((float **)&tb->zero_ties_dev, 1));
             HIP_TRY(hipMemsetAsync(tb->zero_ties_dev, 0, sizeof(int), tb->stream));
             const InputArr *in = tb->in_bnd;
-            hipLaunchKernelGGL(bounds_table_kernel, dim3(grid_for((long long)tb->batch * N * RW)), dim3(256), 0, tb->stream,
-                               in[0].set ? in[0].dev : nullptr, in[1].set ? in[1].dev : nullptr, in[2].set ? in[2].dev : nullptr,
-                               in[3].set ? in[3].dev : nullptr, (in[0].set ? in[0].shared : in[1].shared) ? 1 : 0,
-                               (in[2].set ? in[2].shared : in[3].shared) ? 1 : 0, tb->r_bounds, geo(tb), tb->batch, tb->en_state_bound,
-                               tb->en_input_bound, tb->h16 ? 1 : 0, tb->zero_ties_dev);
-            HIP_TRY(hipGetLastError());
+            HIP_TRY(launch_bounds_table(in[0].set ? in[0].dev : nullptr, in[1].set ? in[1].dev : nullptr, in[2].set ? in[2].dev : nullptr,
+                                        in[3].set ? in[3].dev : nullptr, (in[0].set ? in[0].shared : in[1].shared) ? 1 : 0,
+                                        (in[2].set ? in[2].shared : in[3].shared) ? 1 : 0, tb->r_bounds, geo(tb), tb->batch, tb->en_state_bound,
+                                        tb->en_input_bound, tb->h16 ? 1 : 0, tb->zero_ties_dev, tb->stream));
             int h = 0;
             HIP_TRY(hipMemcpyAsync(&h, tb->zero_ties_dev, sizeof h, hipMemcpyDeviceToHost, tb->stream));
             HIP_TRY(hipStreamSynchronize(tb->stream));
@@ -1080,10 +703,8 @@ int prepare_inputs(TinyBatch *tb, int layout)
         {
             if (!tb->rows_vary_dev) TRY(dev_alloc_zero((float **)&tb->rows_vary_dev, 2));
             HIP_TRY(hipMemsetAsync(tb->rows_vary_dev, 0, 2 * sizeof(int), tb->stream));
-            hipLaunchKernelGGL(rows_vary_kernel, dim3(grid_for((long long)tb->batch * 16)), dim3(256), 0, tb->stream,
-                               bounds_all_shared(tb) ? nullptr : reinterpret_cast<const float2 *>(tb->r_bounds), xper ? tb->r_xref : nullptr, tb->batch, N, nx, nu,
-                               tb->rows_vary_dev);
-            HIP_TRY(hipGetLastError());
+            HIP_TRY(launch_rows_vary(bounds_all_shared(tb) ? nullptr : reinterpret_cast<const float2 *>(tb->r_bounds), xper ? tb->r_xref : nullptr, tb->batch, N, nx,
+                                     nu, tb->rows_vary_dev, tb->stream));
             int h[2] = {1, 1};
             HIP_TRY(hipMemcpyAsync(h, tb->rows_vary_dev, sizeof h, hipMemcpyDeviceToHost, tb->stream));
             HIP_TRY(hipStreamSynchronize(tb->stream));
@@ -1092,16 +713,14 @@ int prepare_inputs(TinyBatch *tb, int layout)
             if (!bounds_all_shared(tb) && (tb->rows_vary & 1u))
             {
                 TRY(sized_buffer(&tb->r_bounds_img, &tb->r_bounds_img_n, (size_t)ntl * N * 2 * 64 * 4));
-                hipLaunchKernelGGL(tile16_image_kernel, dim3(grid_for(ntl * N * 128)), dim3(256), 0, tb->stream, reinterpret_cast<const float4 *>(tb->r_bounds),
-                                   reinterpret_cast<float4 *>(tb->r_bounds_img), tb->batch, N, 2, (long long)N * 8);
-                HIP_TRY(hipGetLastError());
+                HIP_TRY(launch_tile16_image(reinterpret_cast<const float4 *>(tb->r_bounds), reinterpret_cast<float4 *>(tb->r_bounds_img), tb->batch, N, 2,
+                                            (long long)N * 8, tb->stream));
             }
             if (xper && (tb->rows_vary & 2u))
             {
                 TRY(sized_buffer(&tb->r_xref_img, &tb->r_xref_img_n, (size_t)ntl * N * 64 * 4));
-                hipLaunchKernelGGL(tile16_image_kernel, dim3(grid_for(ntl * N * 64)), dim3(256), 0, tb->stream, reinterpret_cast<const float4 *>(tb->r_xref),
-                                   reinterpret_cast<float4 *>(tb->r_xref_img), tb->batch, N, 1, (long long)N * 4);
-                HIP_TRY(hipGetLastError());
+                HIP_TRY(launch_tile16_image(reinterpret_cast<const float4 *>(tb->r_xref), reinterpret_cast<float4 *>(tb->r_xref_img), tb->batch, N, 1,
+                                            (long long)N * 4, tb->stream));
             }
         }
     }
@@ -1136,8 +755,7 @@ int settle_dual_width(TinyBatch *tb, bool kernel_keeps_fp32_duals)
     {
         float *nw = nullptr;
         TRY(dev_alloc_zero(&nw, want32 ? tb->pair_floats : (tb->pair_floats + 1) / 2));
-        hipLaunchKernelGGL(dual_width_kernel, dim3(grid_for((long long)tb->pair_floats)), dim3(256), 0, tb->stream, tb->pair[5], nw, (long long)tb->pair_floats, want32 ? 1 : 0);
-        HIP_TRY(hipGetLastError());
+        HIP_TRY(launch_dual_width(tb->pair[5], nw, (long long)tb->pair_floats, want32 ? 1 : 0, tb->stream));
         HIP_TRY(hipStreamSynchronize(tb->stream));
         (void)guarded_free(tb->pair[5]);
         tb->pair[5] = nw;
@@ -1449,8 +1067,7 @@ int pack_models(TinyBatch *tb, const KernelPlan &pl)
     if (!tb->pm_row_dirty[f]) return 0;
     const long long n = (long long)tb->batch * pm_row_floats(tb->nx, tb->nu);
     if (!tb->pm_row[f]) HIP_TRY(guarded_malloc((void **)&tb->pm_row[f], (size_t)n * sizeof(float)));
-    hipLaunchKernelGGL(models_pack_row_kernel, dim3(grid_for(n)), dim3(256), 0, tb->stream, tb->pm_src, tb->pm_row[f], tb->batch, tb->nx, tb->nu, f);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_models_pack_row(tb->pm_src, tb->pm_row[f], tb->batch, tb->nx, tb->nu, f, tb->stream));
     tb->pm_row_dirty[f] = false;
     return 0;
 }
@@ -1689,29 +1306,27 @@ int enqueue_solve(TinyBatch *tb, const KernelPlan &pl, bool record_events)
 int enqueue_plant_step(TinyBatch *tb, int window_advance, const float *d_w = nullptr, float *d_x_traj = nullptr)
 {
     if (tb->xref_mode == 1 && window_advance) tb->tile_map_dirty = true; // the kernel slides xref_start[]
-    if (tb->plant_mode || d_w || d_x_traj)
-    {
-        // priority: the plant, then the per-instance model record, then the shared model
-        const bool per = tb->plant_mode == 2;
-        const float *A = tb->plant_mode ? tb->plant_A : tb->dA, *Bm = tb->plant_mode ? tb->plant_B : tb->dB;
-        hipLaunchKernelGGL(plant_step_sim_kernel, dim3((tb->batch + 127) / 128), dim3(128), 0, tb->stream, tb->x0buf, work_ptr(tb, TINY_ARR_X), work_ptr(tb, TINY_ARR_U),
-                           A, Bm, per ? (unsigned)(tb->nx * tb->nx) : 0u, per ? (unsigned)(tb->nx * tb->nu) : 0u, (!tb->plant_mode && tb->pm) ? tb->pm_src : nullptr,
-                           d_w, d_x_traj, tb->xref_mode == 1 ? tb->xref_start : nullptr, window_advance, tb->batch, tb->layout, geo(tb), h16_of(tb, tb->layout));
-        HIP_TRY(hipGetLastError());
-        return 0;
-    }
-    if (tb->pm)
-    {
-        hipLaunchKernelGGL(plant_step_pm_kernel, dim3((tb->batch + 127) / 128), dim3(128), 0, tb->stream, tb->x0buf, work_ptr(tb, TINY_ARR_X), work_ptr(tb, TINY_ARR_U),
-                           tb->pm_src, tb->xref_mode == 1 ? tb->xref_start : nullptr, window_advance, tb->batch, tb->layout, geo(tb), h16_of(tb, tb->layout));
-        HIP_TRY(hipGetLastError());
-        return 0;
-    }
-    hipLaunchKernelGGL(plant_step_kernel, dim3((tb->batch + 127) / 128), dim3(128), 0, tb->stream, tb->x0buf,
-                       work_ptr(tb, TINY_ARR_X), work_ptr(tb, TINY_ARR_U), tb->dA, tb->dB,
-                       tb->xref_mode == 1 ? tb->xref_start : nullptr, window_advance, tb->batch, tb->layout, geo(tb),
-                       h16_of(tb, tb->layout));
-    HIP_TRY(hipGetLastError());
+    // priority: the plant, then the per-instance model record, then the shared model (launch_plant_step picks the kernel by what is set here)
+    const bool plant = tb->plant_mode != 0, per = tb->plant_mode == 2;
+    PlantStepArgs a;
+    a.x0buf = tb->x0buf;
+    a.xarr = work_ptr(tb, TINY_ARR_X);
+    a.uarr = work_ptr(tb, TINY_ARR_U);
+    a.A = plant ? tb->plant_A : tb->dA;
+    a.Bm = plant ? tb->plant_B : tb->dB;
+    a.plant = plant;
+    a.a_stride = per ? (unsigned)(tb->nx * tb->nx) : 0u;
+    a.b_stride = per ? (unsigned)(tb->nx * tb->nu) : 0u;
+    a.recs = (!plant && tb->pm) ? tb->pm_src : nullptr;
+    a.w = d_w;
+    a.x_traj = d_x_traj;
+    a.wstart = tb->xref_mode == 1 ? tb->xref_start : nullptr;
+    a.window_advance = window_advance;
+    a.batch = tb->batch;
+    a.layout = tb->layout;
+    a.g = geo(tb);
+    a.h16 = h16_of(tb, tb->layout);
+    HIP_TRY(launch_plant_step(a, tb->stream));
     return 0;
 }
 
@@ -1885,9 +1500,7 @@ int tiny_batch_set_models_device(TinyBatch *tb, const float *d_rho, const float 
     const long long n = (long long)tb->batch * pm_gen_floats(tb->nx, tb->nu);
     if (!tb->pm_src) HIP_TRY(guarded_malloc((void **)&tb->pm_src, (size_t)n * sizeof(float)));
     if (!tb->pm_rho) HIP_TRY(guarded_malloc((void **)&tb->pm_rho, (size_t)tb->batch * sizeof(float)));
-    hipLaunchKernelGGL(models_gather_kernel, dim3(grid_for(n)), dim3(256), 0, tb->stream, d_rho, d_Kinf, d_Pinf, d_Quu_inv, d_AmBKt, d_Adyn, d_Bdyn, d_Q,
-                       tb->pm_src, tb->pm_rho, tb->batch, tb->nx, tb->nu);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_models_gather(d_rho, d_Kinf, d_Pinf, d_Quu_inv, d_AmBKt, d_Adyn, d_Bdyn, d_Q, tb->pm_src, tb->pm_rho, tb->batch, tb->nx, tb->nu, tb->stream));
     tb->pm = true;
     tb->pm_row_dirty[0] = tb->pm_row_dirty[1] = true; // the packed rows follow the records
     return 0;
@@ -2080,12 +1693,8 @@ int tiny_batch_set_systems(TinyBatch *tb, const double *A, const double *B, cons
     }
     if (rc == 0 && iters && hipMemcpy(iters, it, Bn * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(TINY_BATCH_EHIP, "hipMemcpy failed");
     if (rc == 0 && nfail > 0) rc = fail(TINY_BATCH_EINVAL, "tiny_batch_set_systems: the Riccati recursion is singular for %d of %zu systems (iters = -1); models unchanged", nfail, Bn);
-    if (rc == 0)
-    {
-        hipLaunchKernelGGL(systems_to_models_kernel, dim3(grid_for((long long)nf)), dim3(256), 0, tb->stream, dp[4], dp[5], dp[6], dp[7], dp[8], dp[0], dp[1], dp[2], f,
-                           tb->batch, tb->nx, tb->nu);
-        if (hipGetLastError() != hipSuccess) rc = fail(TINY_BATCH_EHIP, "kernel launch failed");
-    }
+    if (rc == 0 && launch_systems_to_models(dp[4], dp[5], dp[6], dp[7], dp[8], dp[0], dp[1], dp[2], f, tb->batch, tb->nx, tb->nu, tb->stream) != hipSuccess)
+        rc = fail(TINY_BATCH_EHIP, "kernel launch failed");
     if (rc == 0) rc = set_models_packed(tb, f);
     if (hipStreamSynchronize(tb->stream) != hipSuccess && rc == 0) rc = fail(TINY_BATCH_EHIP, "hipStreamSynchronize failed");
     (void)guarded_free(d); (void)guarded_free(f); (void)guarded_free(it);
@@ -2782,13 +2391,14 @@ long long tiny_batch_debug_check(void)
     unsigned long long *bad = nullptr, host = 0;
     if (hipMalloc((void **)&bad, sizeof *bad) != hipSuccess || hipMemset(bad, 0, sizeof *bad) != hipSuccess) return fail(TINY_BATCH_EHIP, "tiny_batch_debug_check: allocation failed");
     if (hipDeviceSynchronize() != hipSuccess) { (void)hipFree(bad); return fail(TINY_BATCH_EHIP, "tiny_batch_debug_check: a kernel faulted: %s", hipGetErrorString(hipGetLastError())); }
+    hipError_t e = hipSuccess;
     for (const auto &kv : g_guarded)
     {
         char *u = (char *)kv.first;
-        hipLaunchKernelGGL(guard_count_kernel, dim3(1), dim3(256), 0, nullptr, (const unsigned *)(u - kGuard * sizeof(float)), kGuard, bad);
-        hipLaunchKernelGGL(guard_count_kernel, dim3(1), dim3(256), 0, nullptr, (const unsigned *)(u + kv.second), kGuard, bad);
+        if (e == hipSuccess) e = launch_guard_count((const unsigned *)(u - kGuard * sizeof(float)), kGuard, bad, nullptr);
+        if (e == hipSuccess) e = launch_guard_count((const unsigned *)(u + kv.second), kGuard, bad, nullptr);
     }
-    hipError_t e = hipMemcpy(&host, bad, sizeof host, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(&host, bad, sizeof host, hipMemcpyDeviceToHost);
     (void)hipFree(bad);
     if (e != hipSuccess) return fail(TINY_BATCH_EHIP, "tiny_batch_debug_check: %s", hipGetErrorString(e));
     return (long long)host;

@@ -1,10 +1,10 @@
 // tinympc_batch64.hip — the batched TinyMPC ADMM solver for `typedef double tinytype` (the reference as shipped,
 // src/tinympc/glob_opts.hpp:3): the handle, the device workspace, the choice of kernel and the C-ABI of include/tinympc_batch64.h.
 //
-// Host code, and three helper kernels that move arrays between the host's layout and the workspace's.  Every solve, step and plant kernel lives
-// in a translation unit of its own (admm_f64_thread.hip, admm_f64_rows.hip, admm_f64_rowsim.hip, admm_f64_plant.hip) and is reached through
+// Host code only.  Every kernel lives in a translation unit of its own (admm_f64_thread.hip, admm_f64_rows.hip, admm_f64_rowsim.hip,
+// admm_f64_plant.hip; batch64_helpers.hip: the three that move arrays between the host's layout and the workspace's) and is reached through
 // the typed launchers of f64_internal.h, so nothing in this file — not the order of its functions, not a name in it — has a bearing on
-// their device code.
+// device code.
 //
 // Every per-instance array is stored instance-minor — element (step, row) of instance b at ((step * dim + row) * Bpad + b).  Results are
 // bitwise equal to the compiled reference (tests/test_parity_gpu.py: golden vectors of the as-shipped fp64 N = 10 hovering run).
@@ -21,44 +21,6 @@
 namespace
 {
 using namespace tinympc64;
-
-// host layout [cnt][steps][dim] (cnt = 1: shared, stored once with stride 1)  <->  device [steps][dim][stride]
-__global__ void pack64_kernel(const double *__restrict__ src, double *__restrict__ dst, int nb, int steps, int dim, int stride, int step0, int nsteps)
-{
-    const long long total = (long long)nb * nsteps * dim;
-    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x)
-    {
-        const int b = (int)(e % nb);
-        const long long t = e / nb;
-        const int row = (int)(t % dim), s = (int)(t / dim);
-        dst[((long long)(step0 + s) * dim + row) * stride + (stride > 1 ? b : 0)] = src[((long long)b * steps + step0 + s) * dim + row];
-    }
-}
-__global__ void unpack64_kernel(const double *__restrict__ src, double *__restrict__ dst, int nb, int steps, int dim, int stride)
-{
-    const long long total = (long long)nb * steps * dim;
-    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x)
-    {
-        const int b = (int)(e % nb);
-        const long long t = e / nb;
-        const int row = (int)(t % dim), s = (int)(t / dim);
-        dst[((long long)b * steps + s) * dim + row] = src[((long long)s * dim + row) * stride + b];
-    }
-}
-// a window reference as the per-instance array the one-solve kernels read: row i of instance b is table[min(start[b] + i, rows - 1)]
-__global__ void gather_window64_kernel(const double *__restrict__ table, const int *__restrict__ start, double *__restrict__ dst, int rows, int N, int nx,
-                                       int batch, int bpad)
-{
-    const long long total = (long long)batch * N * nx;
-    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x)
-    {
-        const int b = (int)(e % batch);
-        const long long t = e / batch;
-        const int row = (int)(t % nx), i = (int)(t / nx);
-        const int tr = start[b] + i < rows - 1 ? start[b] + i : rows - 1;
-        dst[((long long)i * nx + row) * bpad + b] = table[(long long)tr * nx + row];
-    }
-}
 
 thread_local std::string g_err64;
 int fail64(int code, const char *fmt, ...)
@@ -81,11 +43,6 @@ int fail64(int code, const char *fmt, ...)
     if (!(c)) return fail64(TINY_BATCH_EINVAL, __VA_ARGS__)
 
 bool xfam(int id) { return id == TINY_ARR_X || id == TINY_ARR_Q || id == TINY_ARR_P || id == TINY_ARR_V || id == TINY_ARR_VNEW || id == TINY_ARR_G; }
-int grid64(long long total)
-{
-    long long g = (total + 255) / 256;
-    return (int)(g < 1 ? 1 : (g > 8192 ? 8192 : g));
-}
 
 } // namespace
 
@@ -174,8 +131,7 @@ int set_input(TinyBatch64 *tb, int which, const double *src, int shared)
         HIP64(hipMemset(tb->in[which], 0, (size_t)steps * dim * stride * sizeof(double)));
     }
     HIP64(hipMemcpy(tb->staging, src, (size_t)nb * steps * dim * sizeof(double), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(pack64_kernel, dim3(grid64((long long)nb * steps * dim)), dim3(256), 0, 0, tb->staging, tb->in[which], nb, steps, dim, stride, 0, steps);
-    HIP64(hipGetLastError());
+    HIP64(launch_pack64(tb->staging, tb->in[which], nb, steps, dim, stride, 0, steps));
     HIP64(hipDeviceSynchronize());
     tb->in_stride[which] = stride;
     tb->in_set[which] = true;
@@ -192,9 +148,7 @@ int gather_window64(TinyBatch64 *tb)
         HIP64(hipMalloc((void **)&tb->xwin, bytes));
         HIP64(hipMemsetAsync(tb->xwin, 0, bytes, 0));
     }
-    hipLaunchKernelGGL(gather_window64_kernel, dim3(grid64((long long)tb->batch * tb->N * tb->nx)), dim3(256), 0, 0, (const double *)tb->table,
-                       (const int *)tb->xref_start, tb->xwin, tb->table_rows, tb->N, tb->nx, tb->batch, tb->bpad);
-    HIP64(hipGetLastError());
+    HIP64(launch_gather_window64(tb->table, tb->xref_start, tb->xwin, tb->table_rows, tb->N, tb->nx, tb->batch, tb->bpad));
     tb->xwin_valid = true;
     return 0;
 }
@@ -386,9 +340,7 @@ int tiny_batch64_set_x0(TinyBatch64 *tb, const double *x0)
     HIP64(hipSetDevice(tb->device));
     HIP64(hipMemcpy(tb->staging, x0, (size_t)tb->batch * tb->nx * sizeof(double), hipMemcpyHostToDevice));
     // [B][1][nx] -> step 0 of x
-    hipLaunchKernelGGL(pack64_kernel, dim3(grid64((long long)tb->batch * tb->nx)), dim3(256), 0, 0, tb->staging, tb->arr[TINY_ARR_X], tb->batch, 1,
-                       tb->nx, tb->bpad, 0, 1);
-    HIP64(hipGetLastError());
+    HIP64(launch_pack64(tb->staging, tb->arr[TINY_ARR_X], tb->batch, 1, tb->nx, tb->bpad, 0, 1));
     HIP64(hipDeviceSynchronize());
     return 0;
 }
@@ -664,9 +616,7 @@ int tiny_batch64_get_first_columns(TinyBatch64 *tb, double *x0, double *u0)
         double *dst = w ? u0 : x0;
         if (!dst) continue;
         const int dim = w ? tb->nu : tb->nx;
-        hipLaunchKernelGGL(unpack64_kernel, dim3(grid64((long long)tb->batch * dim)), dim3(256), 0, 0, tb->arr[w ? TINY_ARR_U : TINY_ARR_X], tb->staging,
-                           tb->batch, 1, dim, tb->bpad);
-        HIP64(hipGetLastError());
+        HIP64(launch_unpack64(tb->arr[w ? TINY_ARR_U : TINY_ARR_X], tb->staging, tb->batch, 1, dim, tb->bpad));
         HIP64(hipMemcpy(dst, tb->staging, (size_t)tb->batch * dim * sizeof(double), hipMemcpyDeviceToHost));
     }
     return 0;
@@ -711,9 +661,7 @@ int tiny_batch64_set_array(TinyBatch64 *tb, int id, const double *src)
     HIP64(hipSetDevice(tb->device));
     const int steps = (int)steps_of(tb, id), dim = dim_of(tb, id);
     HIP64(hipMemcpy(tb->staging, src, (size_t)tb->batch * steps * dim * sizeof(double), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(pack64_kernel, dim3(grid64((long long)tb->batch * steps * dim)), dim3(256), 0, 0, tb->staging, tb->arr[id], tb->batch, steps, dim,
-                       tb->bpad, 0, steps);
-    HIP64(hipGetLastError());
+    HIP64(launch_pack64(tb->staging, tb->arr[id], tb->batch, steps, dim, tb->bpad, 0, steps));
     HIP64(hipDeviceSynchronize());
     return 0;
 }
@@ -724,9 +672,7 @@ int tiny_batch64_get_array(TinyBatch64 *tb, int id, double *dst)
     CHECK64(id >= 0 && id < TINY_ARR_COUNT, "bad array id %d", id);
     HIP64(hipSetDevice(tb->device));
     const int steps = (int)steps_of(tb, id), dim = dim_of(tb, id);
-    hipLaunchKernelGGL(unpack64_kernel, dim3(grid64((long long)tb->batch * steps * dim)), dim3(256), 0, 0, tb->arr[id], tb->staging, tb->batch, steps, dim,
-                       tb->bpad);
-    HIP64(hipGetLastError());
+    HIP64(launch_unpack64(tb->arr[id], tb->staging, tb->batch, steps, dim, tb->bpad));
     HIP64(hipMemcpy(dst, tb->staging, (size_t)tb->batch * steps * dim * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
 }
