@@ -181,10 +181,20 @@ class Oracle(_Solver):
 
     kind = "port"
 
-    def __init__(self, prob, dtype=np.float32, settings=None, allow_unpinned_dims=False):
+    def __init__(self, prob, dtype=np.float32, settings=None, allow_unpinned_dims=False, arith="exact"):
         """allow_unpinned_dims: accept dimensions for which this restatement is NOT bit-exact with the reference (see
-        below) — only for uses that need a precision yardstick, never for a parity claim."""
+        below) — only for uses that need a precision yardstick, never for a parity claim.
+        arith: "exact" = the reference's arithmetic; "fma" = the fma arithmetic of the row-family and tile16 GPU kernels
+        (fp32 and the fp16-storage types only; see "fma arithmetic" in tinympc_oracle_impl.h).  The fma order does not depend
+        on the dimensions, so every nx, nu is accepted there.  plant_step() is the reference's in both."""
         super().__init__(prob, dtype, settings)
+        assert arith in ("exact", "fma"), arith
+        self.arith = arith
+        self.fsuf = self.T.suf + ("fma" if arith == "fma" else "")   # suffix of the solve and the six step functions
+        if arith == "fma":
+            if self.T.suf == "f64":
+                raise ValueError("fma arithmetic is restated for fp32 and fp16 storage only")
+            allow_unpinned_dims = True
         ps = 2 if self.T.suf == "f64" else 4
         for name, rows in (("nx", self.nx), ("nu", self.nu)):
             if rows > ps and rows % ps and not allow_unpinned_dims:
@@ -199,7 +209,7 @@ class Oracle(_Solver):
         self.lib = _lib()
         self.PS = _problem_struct(self.T)
         self.BS = _batch_struct(self.T)
-        self.fn = getattr(self.lib, f"oracle_solve_batch_{self.T.suf}")
+        self.fn = getattr(self.lib, f"oracle_solve_batch_{self.fsuf}")
         self.fn.restype = C.c_int
         self.fn.argtypes = [C.POINTER(self.PS), C.POINTER(self.BS), C.c_int]
 
@@ -221,7 +231,7 @@ class Oracle(_Solver):
         assert fn in self.STEP_FUNCTIONS
         B, ins, (sx, su, sr) = self._prep(st, x_min, x_max, u_min, u_max, Xref)
         ct, WS = self.T.ct, _work_struct(self.T)
-        f = getattr(self.lib, f"oracle_{fn}_{self.T.suf}")
+        f = getattr(self.lib, f"oracle_{fn}_{self.fsuf}")
         f.argtypes, f.restype = [C.POINTER(self.PS), C.POINTER(WS)], C.c_int
         ps = self._pstruct()
         nxt, nut = self.nx * self.N, self.nu * (self.N - 1)

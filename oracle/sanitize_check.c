@@ -2,7 +2,7 @@
  * TEST INFRASTRUCTURE — NOT PRODUCT CODE.
  * AddressSanitizer / UndefinedBehaviorSanitizer run of the CPU restatement (sanitizers run on the CPU
  * build only; GPU sanitizers are not available on this pool).  Built and executed by `make -C oracle sanitize`:
- * a few batched solves of a small stable random system in fp32, fp64 and the fp16-storage instantiation, every array
+ * a few batched solves of a small stable random system in fp32, fp64, the fp16-storage instantiation and the fma-order mode, every array
  * exactly sized so that any out-of-bounds access of the restatement trips ASan.
  */
 #include "tinympc_oracle.c"
@@ -59,6 +59,10 @@ static double urand(unsigned *s) { *s = *s * 1664525u + 1013904223u; return (dou
 RUN(float, _f32)
 RUN(double, _f64)
 RUN(float, _h16)
+/* the fma-order mode (tinympc_oracle_impl.h, ORACLE_FMA): fp32, fp16 storage, fp16 storage with fp32 duals */
+RUN(float, _f32fma)
+RUN(float, _h16fma)
+RUN(float, _h16dfma)
 
 int main(void)
 {
@@ -66,5 +70,5 @@ int main(void)
     double K[2], P[4], Qi[1], Am[4], cd[2];
     const int it = oracle_riccati_f64(2, 1, A, B, Q, R, 1.0, K, P, Qi, Am, cd);
     printf("riccati iterations %d\n", it);
-    return run_f32() | run_f64() | run_h16() | (it > 0 && it < 1000 ? 0 : 1);
+    return run_f32() | run_f64() | run_h16() | run_f32fma() | run_h16fma() | run_h16dfma() | (it > 0 && it < 1000 ? 0 : 1);
 }

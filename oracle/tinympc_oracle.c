@@ -58,6 +58,7 @@ float oracle_round_h16(float f)
     return v.f;
 }
 
+#define ORACLE_FMA 0
 #define ST(x) (x)
 #define STD(x) (x)
 #define REAL float
@@ -102,6 +103,36 @@ float oracle_round_h16(float f)
 #undef REAL
 #undef SUF
 #undef PS
+
+/* fma arithmetic of the row-family and tile16 GPU kernels (see "fma arithmetic" in tinympc_oracle_impl.h): fp32, fp16
+ * storage, and fp16 storage with fp32 duals.  The structs have the layout of the _f32 ones. */
+#undef ORACLE_FMA
+#define ORACLE_FMA 1
+#define REAL float
+#define PS 4
+#define SUF(name) name##_f32fma
+#include "tinympc_oracle_impl.h"
+#undef SUF
+#undef ST
+#undef STD
+#define ST(x) oracle_round_h16(x)
+#define STD(x) oracle_round_h16(x)
+#define SUF(name) name##_h16fma
+#include "tinympc_oracle_impl.h"
+#undef SUF
+#undef STD
+#define STD(x) (x)
+#define SUF(name) name##_h16dfma
+#include "tinympc_oracle_impl.h"
+#undef REAL
+#undef SUF
+#undef PS
+#undef ST
+#undef STD
+#define ST(x) (x)
+#define STD(x) (x)
+#undef ORACLE_FMA
+#define ORACLE_FMA 0
 
 /* ---- small dense helpers (column-major, fp64) for the Riccati precompute ---- */
 

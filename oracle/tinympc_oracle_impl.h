@@ -14,6 +14,10 @@
  *   the _h16 instantiation is pinned only through the _f32 one it is textually identical to apart from ST().
  *   REAL=float  SUF(x)=x##_h16d: the same with the DUALS y, g kept in fp32 (STD(x) = x): "fp16 states, fp32 residual
  *   accumulation" read literally — the duals are the running sums of the primal residuals.
+ *   ORACLE_FMA = 1 (REAL=float only; SUF(x)=x##_f32fma, x##_h16fma, x##_h16dfma): the FMA ARITHMETIC of the row-family and
+ *   tile16 GPU kernels ("fast" mode), which is not the reference's: see "fma arithmetic" below.  The reference has no such
+ *   build; these instantiations are a second, independent statement of the operation sequence the kernels document
+ *   (rowlane_math.h, dpp_ops_gen.h), in plain loops with fmaf, which is correctly rounded on the CPU.
  *
  * Every function names the reference lines it restates (paths relative to
  * /root/reference).  All matrices are column-major, exactly like the Eigen
@@ -161,6 +165,56 @@ static inline REAL SUF(row_dot)(const REAL *M, int rows, int cols, int i, const 
     return SUF(dot_novec)(M + i, rows, xin, cols);
 }
 
+#if ORACLE_FMA
+/*
+ * fma arithmetic.  Every multiply-add of a gain x state product is ONE fused operation (fmaf: the exact product plus the
+ * accumulator, rounded once), the terms taken in ascending k.  Two chain forms exist:
+ *   fma_dot : acc = a0*b0 (a plain, separately rounded product), then acc = fmaf(ak, bk, acc) for k = 1..n-1
+ *   fma_acc : acc given, then acc = fmaf(ak, bk, acc) for k = 0..n-1
+ * The file is compiled with -ffp-contract=off: the only fused operations are the ones written here.
+ * What differs from the reference's arithmetic is confined to forward_pass, the linear cost, the terminal term,
+ * backward_pass_grad and the projection (a median that orders -0 below +0); the slack sum, the dual update, the residuals
+ * and the frame of tiny_solve are shared with it.
+ */
+static float SUF(fma_dot)(const float *a, int sa, const float *b, int n)
+{
+    float acc = a[0] * b[0];
+    for (int k = 1; k < n; k++) acc = __builtin_fmaf(a[(size_t)k * sa], b[k], acc);
+    return acc;
+}
+static float SUF(fma_acc)(float acc, const float *a, int sa, const float *b, int n)
+{
+    for (int k = 0; k < n; k++) acc = __builtin_fmaf(a[(size_t)k * sa], b[k], acc);
+    return acc;
+}
+/* the same two chains with every gain negated (the kernels are handed -Kinf; the negation of a float is exact) */
+static float SUF(fma_dot_neg)(const float *a, int sa, const float *b, int n)
+{
+    float acc = (-a[0]) * b[0];
+    for (int k = 1; k < n; k++) acc = __builtin_fmaf(-a[(size_t)k * sa], b[k], acc);
+    return acc;
+}
+static float SUF(fma_acc_neg)(float acc, const float *a, int sa, const float *b, int n)
+{
+    for (int k = 0; k < n; k++) acc = __builtin_fmaf(-a[(size_t)k * sa], b[k], acc);
+    return acc;
+}
+/* median of (t, min(lo, hi), hi) through max / min that order -0 below +0 and compare nothing else differently: the
+ * projection of the fma kernels (NaNs are out of scope).  med3(a, b, c) = max(min(a, b), min(max(a, b), c)) */
+static inline int SUF(below)(float a, float b)
+{
+    if (a == 0 && b == 0) return __builtin_signbit(a) && !__builtin_signbit(b);
+    return a < b;
+}
+static inline float SUF(min0)(float a, float b) { return SUF(below)(b, a) ? b : a; }
+static inline float SUF(max0)(float a, float b) { return SUF(below)(a, b) ? b : a; }
+static inline float SUF(median_project)(float t, float lo, float hi)
+{
+    lo = (lo < hi) ? lo : hi;
+    return SUF(max0)(SUF(min0)(t, lo), SUF(min0)(SUF(max0)(t, lo), hi));
+}
+#endif
+
 /* src/tinympc/admm.cpp:27-37 */
 void SUF(oracle_forward_pass)(const SUF(OracleProblem) * P, SUF(OracleWork) * W)
 {
@@ -171,6 +225,15 @@ void SUF(oracle_forward_pass)(const SUF(OracleProblem) * P, SUF(OracleWork) * W)
         REAL *ui = W->u + (size_t)i * nu;
         const REAL *di = W->d + (size_t)i * nu;
         REAL *xn = W->x + (size_t)(i + 1) * nx;
+#if ORACLE_FMA
+        /* u_i = (-Kinf)*x_i - d_i: one chain per input row, a plain product first */
+        for (int j = 0; j < nu; j++)
+            ui[j] = ST(SUF(fma_dot_neg)(P->Kinf + j, nu, xi, nx) - di[j]);
+        /* x_{i+1}: the chain over Adyn(j,:)*x_i, continued with one fma per input, Bdyn(j,m)*u_i(m) */
+        for (int j = 0; j < nx; j++)
+            xn[j] = ST(SUF(fma_acc)(SUF(fma_dot)(P->Adyn + j, nx, xi, nx), P->Bdyn + j, nx, ui, nu));
+        continue;
+#endif
         /* u_i = -Kinf*x_i - d_i   (admm.cpp:31) */
         for (int j = 0; j < nu; j++)
             ui[j] = ST(-SUF(row_dot)(P->Kinf, nu, nx, j, xi) - di[j]);
@@ -188,6 +251,13 @@ void SUF(oracle_update_slack)(const SUF(OracleProblem) * P, SUF(OracleWork) * W)
         W->znew[e] = ST(W->u[e] + W->y[e]); /* :47 */
     for (int e = 0; e < nxt; e++)
         W->vnew[e] = ST(W->x[e] + W->g[e]); /* :48 */
+#if ORACLE_FMA
+    if (P->en_input_bound)
+        for (int e = 0; e < nut; e++) W->znew[e] = SUF(median_project)(W->znew[e], W->u_min[e], W->u_max[e]);
+    if (P->en_state_bound)
+        for (int e = 0; e < nxt; e++) W->vnew[e] = SUF(median_project)(W->vnew[e], W->x_min[e], W->x_max[e]);
+    return;
+#endif
     if (P->en_input_bound)              /* :51-54  u_max.cwiseMin(u_min.cwiseMax(znew)) */
         for (int e = 0; e < nut; e++)
         {
@@ -223,6 +293,37 @@ void SUF(oracle_update_linear_cost)(const SUF(OracleProblem) * P, SUF(OracleWork
     const int nx = P->nx, nu = P->nu, N = P->N;
     const int nxt = nx * N, nut = nu * (N - 1);
     const REAL rho = P->rho;
+#if ORACLE_FMA
+    /* [q ; r] = fmaf(-rho, snew - dual, c) with c = -(Xref o Q) on the state rows and, on the input rows, NEGATIVE zero
+     * (so that a zero product keeps its sign) or -(Uref o R) */
+    for (int j = 0; j < N - 1; j++)
+        for (int i = 0; i < nu; i++)
+        {
+            const size_t e = (size_t)j * nu + i;
+            const float c = P->en_uref ? ST(-(W->Uref[e] * P->R[i])) : -0.0f;
+            W->r[e] = ST(__builtin_fmaf(-rho, W->znew[e] - W->y[e], c));
+        }
+    for (int j = 0; j < N; j++)
+        for (int i = 0; i < nx; i++)
+        {
+            const size_t e = (size_t)j * nx + i;
+            const float c = ST(-(W->Xref[e] * P->Q[i]));
+            W->q[e] = ST(__builtin_fmaf(-rho, W->vnew[e] - W->g[e], c));
+        }
+    {
+        /* p_j(N-1): -(Xref(0)*Pinf(0,j), then fmas over k), then the same fmaf with rho */
+        const REAL *xr = W->Xref + (size_t)(N - 1) * nx;
+        REAL *pN = W->p + (size_t)(N - 1) * nx;
+        for (int j = 0; j < nx; j++)
+        {
+            const size_t e = (size_t)(N - 1) * nx + j;
+            const float c = ST(-SUF(fma_dot)(P->Pinf + (size_t)j * nx, 1, xr, nx));
+            pN[j] = ST(__builtin_fmaf(-rho, W->vnew[e] - W->g[e], c));
+        }
+    }
+    (void)nxt; (void)nut;
+    return;
+#endif
     if (P->en_uref)
     {
         /* r = -(Uref.array().colwise() * R.array());  r.noalias() -= rho * (znew - y);   (cf. :81-82 for q) */
@@ -295,6 +396,22 @@ void SUF(oracle_backward_pass_grad)(const SUF(OracleProblem) * P, SUF(OracleWork
         REAL *di = W->d + (size_t)i * nu;
         REAL *pi = W->p + (size_t)i * nx;
         const REAL *qi = W->q + (size_t)i * nx;
+#if ORACLE_FMA
+        /* input rows: acc = r_i(m), then fmas with Bdyn(k,m)*p_{i+1}(k); d_i = Quu_inv(m,:) . acc as a product-first chain */
+        for (int j = 0; j < nu; j++)
+            tmp[j] = SUF(fma_acc)(ri[j], P->Bdyn + (size_t)j * nx, 1, pn, nx);
+        for (int j = 0; j < nu; j++)
+            di[j] = ST(SUF(fma_dot)(P->Quu_inv + j, nu, tmp, nu));
+        /* state rows: acc = q_i(j), then fmas with AmBKt(j,k)*p_{i+1}(k), continued with (-Kinf)(m,j)*r_i(m) */
+        for (int j = 0; j < nx; j++)
+            pi[j] = ST(SUF(fma_acc_neg)(SUF(fma_acc)(qi[j], P->AmBKt + j, nx, pn, nx), P->Kinf + (size_t)j * nu, 1, ri, nu));
+        /* "+ coeff_d2p * d.col(i)": the chain restarts from the STORED p_i */
+        if (P->en_coeff_d2p)
+            for (int j = 0; j < nx; j++)
+                pi[j] = ST(SUF(fma_acc)(pi[j], P->coeff_d2p + j, nx, di, nu));
+        (void)gemv; (void)p_packet;
+        continue;
+#endif
         /* d_i = Quu_inv * (Bdyn^T * p_{i+1} + r_i)   (admm.cpp:19): the inner product is evaluated
          * into a temporary first (column j of Bdyn is contiguous), then the nu x nu product. */
         for (int j = 0; j < nu; j++)

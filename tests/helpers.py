@@ -369,3 +369,34 @@ def projection_input(pr, O, key):
         prob = projection_problem(pr, O, nx, nu, N)
         _proj_cache[key] = (prob, projection_case(O, prob, B, dtype, PROJ_INPUTS.index(key), mode))
     return _proj_cache[key]
+
+
+# ---- inputs on which no operation rounds, shared by tests/test_fma_oracle_host.py and tests/test_fma_oracle_gpu.py --------------------------------------
+
+def _signed_selection(rng, rows, cols):
+    """one entry of +-1 per row, in a drawn column"""
+    m = np.zeros((rows, cols))
+    m[np.arange(rows), rng.integers(0, cols, size=rows)] = rng.choice([-1.0, 1.0], size=rows)
+    return m
+
+
+def rounding_free_case(nx, nu, N, B, seed, terms=False):
+    """(prob, settings, x0, xref, bnds, uref): small integers through signed selection matrices, rho = 1, tolerances 0.  Every product is then an
+    integer times +-1 and every sum an integer far below 2^24, so for one or two iterations no fp32 operation rounds: a fused multiply-add and a
+    multiply followed by an add give the same VALUE (not the same sign of a zero: negated gains flip those).  The caller sets max_iter and proves
+    the premise by comparing the fp32 with the fp64 exact oracle: with the optional terms on, the values grow faster along the horizon and about half
+    of the seeds round in the second iteration (seed 0 does not, at B = 8 and B = 37, for (12,4,10), (8,3,7), (4,1,10) and (2,2,3)).  terms: integer R and Uref and a signed selection coeff_d2p for the two optional terms."""
+    rng = np.random.default_rng(seed)
+    prob = dict(name=f"selection_{nx}_{nu}", nx=nx, nu=nu, N=N, rho=1.0, Kinf=_signed_selection(rng, nu, nx), Pinf=_signed_selection(rng, nx, nx),
+                Quu_inv=_signed_selection(rng, nu, nu), AmBKt=_signed_selection(rng, nx, nx), Adyn=_signed_selection(rng, nx, nx),
+                Bdyn=_signed_selection(rng, nx, nu), Q=rng.integers(1, 4, size=nx).astype(np.float64), u_min=-3.0, u_max=3.0, x_min=-50.0, x_max=50.0)
+    settings = dict(abs_pri_tol=0.0, abs_dua_tol=0.0, check_termination=1, en_state_bound=1, en_input_bound=1)
+    uref = None
+    if terms:
+        prob["R"] = rng.integers(1, 4, size=nu).astype(np.float64)
+        prob["coeff_d2p"] = _signed_selection(rng, nx, nu)
+        uref = rng.integers(-2, 3, size=(B, N - 1, nu)).astype(np.float32)
+        settings.update(en_uref=1, en_coeff_d2p=1)
+    x0 = rng.integers(-4, 5, size=(B, nx)).astype(np.float32)
+    xref = rng.integers(-2, 3, size=(B, N, nx)).astype(np.float32)
+    return prob, settings, x0, xref, bounds_of(prob, np.float32), uref

@@ -21,6 +21,9 @@ FAST arithmetic (fma chains: v_mfma_f32_16x16x4_f32 in the streaming kernel, v_f
     * fraction of instances whose iteration count differs from the fp32 reference <= max(1.5 x the
       fp64-vs-fp32 fraction, 2 %), and never by more than the fp64 spread + 2 termination checks;
     * hard cap regardless of the yardstick: u within 3e-4 of the reference relative to the input bound.
+  The fma kernels of the row family (rowlane, rowloop, rowstream, the step functions) and tile16 now ALSO have a bitwise bar: the
+  fma-order mode of the oracle, tests/test_fma_oracle_gpu.py.  The yardstick tests here stay as they are; they alone guard the fma
+  kernels that sum in an order of their own (quadlane, the wave kernels, tile48, stream).
 """
 import numpy as np
 import pytest
