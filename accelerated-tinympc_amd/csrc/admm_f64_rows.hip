@@ -1,6 +1,7 @@
-// admm_f64_rows.hip — the sixteen-lanes-per-instance kernel of the fp64 library, admm_f64_rows_kernel, with its launchers.  Compiled twice: as
-// itself (the one-solve and the MPC instantiations, launch_f64_rows) and, under TINY_F64SIM_UNIT, as admm_f64_rowsim.hip (the SIM instantiations,
-// launch_rows64_sim), so that the two families build side by side.
+// admm_f64_rows.hip — the sixteen-lanes-per-instance kernel of the fp64 library, admm_f64_rows_kernel, with its launchers.  Compiled four times: as
+// itself (the one-solve and the MPC instantiations, launch_f64_rows), under TINY_F64SIM_UNIT as admm_f64_rowsim.hip (the SIM instantiations,
+// launch_rows64_sim) and, under TINY_F64PM_UNIT = 1 / 2, as admm_f64_rows_pm.hip / admm_f64_rowsim_pm.hip (per-instance models: one solve,
+// launch_f64_rows_pm / the closed loop, launch_rows64_loop_pm), so that the families build side by side.
 #include "f64_math.h"
 
 namespace
@@ -13,6 +14,56 @@ __device__ __forceinline__ Mpc64 loop_args(const Mpc64 &l, const Sim64 &) { retu
 __device__ __forceinline__ Sim64 sim_args(const Mpc64 &, const Sim64 &s) { return s; }
 template <class... T>
 __device__ __forceinline__ Sim64 sim_args(const T &...) { return Sim64{}; }
+// per-instance models: a Models64 as the last trailing argument, alone (one solve) or behind Mpc64 and Sim64 (the closed loop)
+__device__ __forceinline__ Mpc64 loop_args(const Models64 &) { return Mpc64{}; }
+__device__ __forceinline__ Mpc64 loop_args(const Mpc64 &l, const Sim64 &, const Models64 &) { return l; }
+__device__ __forceinline__ Sim64 sim_args(const Mpc64 &, const Sim64 &s, const Models64 &) { return s; }
+__device__ __forceinline__ Models64 models_args(const Models64 &m) { return m; }
+__device__ __forceinline__ Models64 models_args(const Mpc64 &, const Sim64 &, const Models64 &m) { return m; }
+template <class... T>
+__device__ __forceinline__ Models64 models_args(const T &...) { return Models64{}; }
+
+// This lane's gain rows from its instance's record (Models64::rec), element for element what pack_row_gains lays out for the shared table: the x rows
+// read row r of Adyn, AmBKt, Bdyn, column r of Kinf and Pinf and Q(r), the u rows row m of Kinf, Quu_inv and column m of Bdyn; the other lanes zeros.
+template <int NX, int NU>
+struct Rec64
+{
+    static constexpr int K = 0, PINF = NU * NX, QUU = PINF + NX * NX, AM = QUU + NU * NU, A = AM + NX * NX, B = A + NX * NX, Q = B + NX * NU;
+};
+template <int NX, int NU>
+__device__ __forceinline__ void record_gains(const double *__restrict__ rec, bool is_x, bool is_u, int row, double (&M1)[NX], double (&M2)[NU],
+                                             double (&M3)[NX], double (&M45)[NU], double &qrow)
+{
+    using R = Rec64<NX, NU>;
+    const bool own = is_x || is_u; // (row = 0 on the lanes that own none: every address below stays inside the record)
+    const int o1 = is_x ? R::A + row : R::K + row, s1 = is_x ? NX : NU;          // Adyn(r,k) | Kinf(m,k)
+    const int o3 = is_x ? R::AM + row : R::B + row * NX, s3 = is_x ? NX : 1;     // AmBKt(r,k) | Bdyn(k,m)
+    const int o45 = is_x ? R::K + row * NU : R::QUU + row, s45 = is_x ? 1 : NU;  // Kinf(m,r) | Quu_inv(mr,m)
+#pragma unroll
+    for (int k = 0; k < NX; k++)
+    {
+        const double a = rec[o1 + k * s1], c = rec[o3 + k * s3];
+        M1[k] = own ? a : 0.0; M3[k] = own ? c : 0.0;
+    }
+#pragma unroll
+    for (int m = 0; m < NU; m++)
+    {
+        const double a = rec[R::B + row + m * NX], c = rec[o45 + m * s45];       // Bdyn(r,m)
+        M2[m] = is_x ? a : 0.0; M45[m] = own ? c : 0.0;
+    }
+    const double q = rec[R::Q + row];
+    qrow = is_x ? q : 0.0;
+}
+template <int NX, int NU>
+__device__ __forceinline__ void record_pinf_row(const double *__restrict__ rec, bool is_x, int row, double (&PT)[NX])
+{
+#pragma unroll
+    for (int k = 0; k < NX; k++)
+    {
+        const double a = rec[Rec64<NX, NU>::PINF + row * NX + k]; // Pinf(k,r)
+        PT[k] = is_x ? a : 0.0;
+    }
+}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // admm_f64_rows_kernel<NX,NU,N>: the 16-lanes-per-instance mapping of admm_rowlane.hip in double.  Lane r of a DPP row owns
@@ -42,11 +93,17 @@ constexpr int F64_AHEAD = 4; // bounds are fetched this many steps ahead of thei
 template <int NX, int NU, int N, bool RT = false, bool MPC = false, class... LOOP>
 __global__ __launch_bounds__(WAVE64, (N <= 12 ? 2 : 1)) void admm_f64_rows_kernel(const Params64 P, const double *__restrict__ gains, const LOOP... loop)
 {
-    constexpr bool SIM = sizeof...(LOOP) == 2;
-    static_assert(sizeof...(LOOP) == (MPC ? (SIM ? 2 : 1) : 0), "the closed-loop instantiations take one further argument, an Mpc64, the simulated ones a Sim64 behind it; the one-solve kernels none");
+    // PM (the ",pm" instantiations, admm_f64_rows_pm.hip and admm_f64_rowsim_pm.hip): a Models64 as the last trailing argument.  The gain rows and rho
+    // of a row are its instance's, read from the instance's record; `gains` is not read.  The closed loop with per-instance models is the SIM one
+    constexpr bool PM = (false || ... || std::is_same<LOOP, Models64>::value);
+    constexpr int NLOOP = (int)sizeof...(LOOP) - (PM ? 1 : 0);
+    constexpr bool SIM = NLOOP == 2;
+    static_assert(NLOOP == (MPC ? (SIM ? 2 : 1) : 0), "the closed-loop instantiations take one further argument, an Mpc64, the simulated ones a Sim64 behind it; the one-solve kernels none");
     static_assert(!SIM || MPC, "the simulated loop is the on-chip loop's");
+    static_assert(!PM || SIM == MPC, "per-instance models: one solve, or the simulated loop");
     [[maybe_unused]] const Mpc64 L = loop_args(loop...);
     [[maybe_unused]] const Sim64 S = sim_args(loop...);
+    [[maybe_unused]] const Models64 MO = models_args(loop...);
     static_assert(!MPC || !(RT && N > 32), "the on-chip loop takes the workspace's d from the registers of [p ; d]");
     static_assert(NX + NU <= 16 && !(NX >= 8 && NU >= 8), "16-lane mapping; both dims >= 8 would take Eigen's GEMV kernel");
     static_assert(!RT || N > 20, "the runtime-horizon variant indexes the slack by the horizon: it keeps it in LDS");
@@ -59,7 +116,10 @@ __global__ __launch_bounds__(WAVE64, (N <= 12 ? 2 : 1)) void admm_f64_rows_kerne
     const bool is_x = r16 < NX, is_u = r16 >= NX && r16 < NX + NU;
     const int row = is_x ? r16 : (is_u ? r16 - NX : 0);
     const size_t bp = (size_t)P.bpad;
-    const double rho = P.rho;
+    double rho_of_row;
+    if constexpr (PM) rho_of_row = MO.rho[b];
+    else rho_of_row = P.rho;
+    const double rho = rho_of_row;
     // element (step, this lane's row) of the pair [x-type array ; u-type array]; u-type arrays have N - 1 steps
     auto ld = [&](int idx, int idu, int i) -> double {
         if (is_x) return P.arr[idx][((size_t)i * NX + row) * bp + b];
@@ -87,12 +147,17 @@ __global__ __launch_bounds__(WAVE64, (N <= 12 ? 2 : 1)) void admm_f64_rows_kerne
         return;
     }
     // gains, one register per matrix column: [reg][16] doubles (pack_row_gains on the host)
-    double M1[NX], M2[NU], M3[NX], M45[NU];
+    double M1[NX], M2[NU], M3[NX], M45[NU], qrow_of_row;
+    if constexpr (PM) record_gains<NX, NU>(MO.rec + b * MO.stride, is_x, is_u, row, M1, M2, M3, M45, qrow_of_row);
+    else
+    {
 #pragma unroll
-    for (int k = 0; k < NX; k++) { M1[k] = gains[k * 16 + r16]; M3[k] = gains[(NX + NU + k) * 16 + r16]; }
+        for (int k = 0; k < NX; k++) { M1[k] = gains[k * 16 + r16]; M3[k] = gains[(NX + NU + k) * 16 + r16]; }
 #pragma unroll
-    for (int m = 0; m < NU; m++) { M2[m] = gains[(NX + m) * 16 + r16]; M45[m] = gains[(2 * NX + NU + m) * 16 + r16]; }
-    const double qrow = gains[(2 * NX + 2 * NU) * 16 + r16];
+        for (int m = 0; m < NU; m++) { M2[m] = gains[(NX + m) * 16 + r16]; M45[m] = gains[(2 * NX + NU + m) * 16 + r16]; }
+        qrow_of_row = gains[(2 * NX + 2 * NU) * 16 + r16];
+    }
+    const double qrow = qrow_of_row;
 
     // ---- live-in ----
     // long horizons keep the two slack words of a step in LDS (lane-linear, 1 KB per step and wave), short ones in registers
@@ -137,8 +202,12 @@ __global__ __launch_bounds__(WAVE64, (N <= 12 ? 2 : 1)) void admm_f64_rows_kerne
     double pterm;
     {
         double PT[NX], t[NX]; // p.col(N-1) = -(Xref.col(N-1)^T * Pinf)  (admm.cpp:83): a vectorised reduction over k
+        if constexpr (PM) record_pinf_row<NX, NU>(MO.rec + b * MO.stride, is_x, row, PT);
+        else
+        {
 #pragma unroll
-        for (int k = 0; k < NX; k++) PT[k] = gains[(2 * NX + 2 * NU + 1 + k) * 16 + r16];
+            for (int k = 0; k < NX; k++) PT[k] = gains[(2 * NX + 2 * NU + 1 + k) * 16 + r16];
+        }
         row_products<0, NX>(t, xrN, PT);
         pterm = -vec_sum(t);
     }
@@ -304,7 +373,19 @@ next_solve: // (a label, not a loop around the solve: the one-solve instantiatio
         int ozg;
         asm volatile("s_mov_b32 %0, 0" : "=s"(ozg));
         const double *const gains_again = gains + ozg;
-        const double qrow_again = gains_again[(2 * NX + 2 * NU) * 16 + r16];
+        // (per-instance models: the record's lane address is remade from `inst` the same way, as the plant rows' above)
+        [[maybe_unused]] const double *rec_again = nullptr;
+        double qrow_again;
+        if constexpr (PM)
+        {
+            int ig = inst;
+            asm volatile("" : "+v"(ig));
+            ig = valid ? ig : P.batch - 1;
+            rec_again = MO.rec + (size_t)ig * MO.stride;
+            const double q = rec_again[Rec64<NX, NU>::Q + row];
+            qrow_again = is_x ? q : 0.0;
+        }
+        else qrow_again = gains_again[(2 * NX + 2 * NU) * 16 + r16];
 #pragma unroll
         for (int i = 0; i < N; i++)
         {
@@ -323,8 +404,12 @@ next_solve: // (a label, not a loop around the solve: the one-solve instantiatio
         if (window) // admm.cpp:83 for the window's new last row, as at live-in
         {
             double PT[NX], tp[NX];
+            if constexpr (PM) record_pinf_row<NX, NU>(rec_again, is_x, row, PT);
+            else
+            {
 #pragma unroll
-            for (int k = 0; k < NX; k++) PT[k] = gains_again[(2 * NX + 2 * NU + 1 + k) * 16 + r16];
+                for (int k = 0; k < NX; k++) PT[k] = gains_again[(2 * NX + 2 * NU + 1 + k) * 16 + r16];
+            }
             row_products<0, NX>(tp, xrN, PT);
             pterm = -vec_sum(tp);
         }
@@ -383,7 +468,54 @@ next_solve: // (a label, not a loop around the solve: the one-solve instantiatio
 
 namespace tinympc64
 {
-#ifdef TINY_F64SIM_UNIT
+#if defined(TINY_F64PM_UNIT) && TINY_F64PM_UNIT == 1
+// per-instance models, one solve: an instantiation wherever launch_f64_rows has one
+hipError_t launch_f64_rows_pm(int nx, int nu, int N, const Params64 &P, const Models64 &M)
+{
+    const int nrow_blocks = (P.batch + 3) / 4;
+    const double *const no_gains = nullptr;
+#define TINY_F64ROWS_PM_LAUNCH(NX, NU, NN)                                                                                                         \
+    if (nx == NX && nu == NU && N == NN)                                                                                                           \
+    {                                                                                                                                              \
+        hipLaunchKernelGGL((admm_f64_rows_kernel<NX, NU, NN, false, false, Models64>), dim3(nrow_blocks), dim3(WAVE64), 0, 0, P, no_gains, M);     \
+        return hipGetLastError();                                                                                                                  \
+    }
+    TINY_FOR_EACH_F64ROWS(TINY_F64ROWS_PM_LAUNCH)
+#define TINY_F64ROWS_RT_PM_LAUNCH(NX, NU)                                                                                                          \
+    if (nx == NX && nu == NU && N >= 2 && N <= F64ROWS_RT_MAX_N)                                                                                   \
+    {                                                                                                                                              \
+        if (N <= 32) hipLaunchKernelGGL((admm_f64_rows_kernel<NX, NU, 32, true, false, Models64>), dim3(nrow_blocks), dim3(WAVE64), 0, 0, P, no_gains, M); \
+        else hipLaunchKernelGGL((admm_f64_rows_kernel<NX, NU, 64, true, false, Models64>), dim3(nrow_blocks), dim3(WAVE64), 0, 0, P, no_gains, M); \
+        return hipGetLastError();                                                                                                                  \
+    }
+    TINY_FOR_EACH_F64ROWS_RT(TINY_F64ROWS_RT_PM_LAUNCH)
+    return hipErrorInvalidValue;
+}
+#elif defined(TINY_F64PM_UNIT)
+// per-instance models, the on-chip closed loop: ONE family, the simulated one, wherever launch_rows64_sim has an instantiation.  A nominal run passes
+// S.plant = S.w = S.x_traj = NULL: the plant step on the row's own gain rows is the nominal step bit for bit.  mpc_steps = 1 is served too
+hipError_t launch_rows64_loop_pm(int nx, int nu, int N, const Params64 &P, const Mpc64 &L, const Sim64 &S, const Models64 &M)
+{
+    if (L.mpc_steps < 1 || P.max_iter < 1) return hipErrorInvalidValue;
+    const int nrow_blocks = (P.batch + 3) / 4;
+    const double *const no_gains = nullptr;
+#define TINY_F64ROWS_PM_LOOP_LAUNCH(NX, NU, NN)                                                                                                    \
+    if (nx == NX && nu == NU && N == NN)                                                                                                           \
+    {                                                                                                                                              \
+        hipLaunchKernelGGL((admm_f64_rows_kernel<NX, NU, NN, false, true, Mpc64, Sim64, Models64>), dim3(nrow_blocks), dim3(WAVE64), 0, 0, P, no_gains, L, S, M); \
+        return hipGetLastError();                                                                                                                  \
+    }
+    TINY_FOR_EACH_F64ROWS(TINY_F64ROWS_PM_LOOP_LAUNCH)
+#define TINY_F64ROWS_RT_PM_LOOP_LAUNCH(NX, NU)                                                                                                     \
+    if (nx == NX && nu == NU && N >= 2 && N <= 32)                                                                                                 \
+    {                                                                                                                                              \
+        hipLaunchKernelGGL((admm_f64_rows_kernel<NX, NU, 32, true, true, Mpc64, Sim64, Models64>), dim3(nrow_blocks), dim3(WAVE64), 0, 0, P, no_gains, L, S, M); \
+        return hipGetLastError();                                                                                                                  \
+    }
+    TINY_FOR_EACH_F64ROWS_RT(TINY_F64ROWS_RT_PM_LOOP_LAUNCH)
+    return hipErrorInvalidValue;
+}
+#elif defined(TINY_F64SIM_UNIT)
 // a SIM instantiation wherever there is an MPC one: the unrolled horizons and the capacity-32 body of every sixteen-lane class
 hipError_t launch_rows64_sim(int nx, int nu, int N, const Params64 &P, const double *gains, const Mpc64 &L, const Sim64 &S)
 {

@@ -1,5 +1,6 @@
 // admm_f64_thread.hip — the thread-per-instance kernels of the fp64 library: admm_f64_kernel (all ADMM iterations in one launch) and
-// admm_f64_step_kernel (the six functions tiny_solve() is made of, one launch each), with their launchers.
+// admm_f64_step_kernel (the six functions tiny_solve() is made of, one launch each), with their launchers.  Under TINY_F64PM_UNIT
+// (admm_f64_thread_pm.hip) the unit holds the per-instance-model instantiations of admm_f64_kernel and their launcher instead.
 //
 // One thread per instance, state in HBM.  Every per-instance array is stored instance-minor — element (step, row) of
 // instance b at ((step * dim + row) * Bpad + b) — so that the 64 instances of a wavefront read and write 512 contiguous
@@ -11,22 +12,40 @@ namespace
 {
 using namespace tinympc64;
 
-template <int NX, int NU>
-__global__ __launch_bounds__(WAVE64) void admm_f64_kernel(const Params64 P)
+__device__ __forceinline__ Models64 models_of(const Models64 &m) { return m; }
+
+// PM (one trailing argument, a Models64: the ",pm" instantiations of admm_f64_thread_pm.hip): a thread reads its own instance's record and rho from
+// device memory instead of the block's LDS copy of the one shared model; a thread past the batch addresses the last instance's and stores nothing.
+template <int NX, int NU, class... PMA>
+__global__ __launch_bounds__(WAVE64) void admm_f64_kernel(const Params64 P, const PMA... pma)
 {
     static_assert(!(NX >= 8 && NU >= 8), "both dims >= 8: Eigen switches to its GEMV kernel, not restated here");
+    constexpr bool PM = sizeof...(PMA) == 1;
+    static_assert(sizeof...(PMA) <= 1, "at most one trailing argument, the Models64");
     constexpr int NMAT = NU * NX + NX * NX + NU * NU + NX * NX + NX * NX + NX * NU + NX;
-    __shared__ double mats[NMAT];
-    for (int e = threadIdx.x; e < NMAT; e += WAVE64) mats[e] = P.mats[e];
-    __syncthreads();
-    const double *K = mats, *Pinf = K + NU * NX, *Quu = Pinf + NX * NX, *Am = Quu + NU * NU, *A = Am + NX * NX, *Bm = A + NX * NX,
+    __shared__ double mats[PM ? 1 : NMAT];
+    const double *mats_of_thread = mats;
+    double rho_of_thread = P.rho;
+    if constexpr (PM)
+    {
+        const Models64 MO = models_of(pma...);
+        const size_t me = blockIdx.x * WAVE64 + threadIdx.x, bm = me < (size_t)P.batch ? me : (size_t)P.batch - 1;
+        mats_of_thread = MO.rec + bm * MO.stride;
+        rho_of_thread = MO.rho[bm];
+    }
+    else
+    {
+        for (int e = threadIdx.x; e < NMAT; e += WAVE64) mats[e] = P.mats[e];
+        __syncthreads();
+    }
+    const double *K = mats_of_thread, *Pinf = K + NU * NX, *Quu = Pinf + NX * NX, *Am = Quu + NU * NU, *A = Am + NX * NX, *Bm = A + NX * NX,
                  *Q = Bm + NX * NU;
 
     const int b = blockIdx.x * WAVE64 + threadIdx.x;
     const bool valid = b < P.batch;
     const int N = P.N;
     const size_t bp = (size_t)P.bpad;
-    const double rho = P.rho;
+    const double rho = rho_of_thread;
     auto at = [&](int id, int step, int row, int dim) -> double & { return P.arr[id][((size_t)step * dim + row) * bp + b]; };
     auto in = [&](const double *base, int stride, int step, int row, int dim) {
         return base[((size_t)step * dim + row) * (size_t)stride + (stride > 1 ? b : 0)];
@@ -385,6 +404,19 @@ __global__ __launch_bounds__(WAVE64) void admm_f64_step_kernel(const Params64 P,
 
 namespace tinympc64
 {
+#ifdef TINY_F64PM_UNIT
+hipError_t launch_f64_thread_pm(int nx, int nu, const Params64 &P, const Models64 &M)
+{
+#define TINY_F64_PM_LAUNCH(NX, NU)                                                                                  \
+    if (nx == NX && nu == NU)                                                                                       \
+    {                                                                                                               \
+        hipLaunchKernelGGL((admm_f64_kernel<NX, NU, Models64>), dim3(P.bpad / WAVE64), dim3(WAVE64), 0, 0, P, M);   \
+        return hipGetLastError();                                                                                   \
+    }
+    TINY_FOR_EACH_F64DIMS(TINY_F64_PM_LAUNCH)
+    return hipErrorInvalidValue;
+}
+#else
 hipError_t launch_f64_thread(int nx, int nu, const Params64 &P)
 {
 #define TINY_F64_LAUNCH(NX, NU)                                                                        \
@@ -416,4 +448,5 @@ hipError_t launch_f64_step(int fn, int nx, int nu, const Params64 &P, int *conv)
     TINY_FOR_EACH_F64DIMS(TINY_F64_STEP_LAUNCH)
     return hipErrorInvalidValue;
 }
+#endif // TINY_F64PM_UNIT
 } // namespace tinympc64

@@ -41,6 +41,14 @@ struct Sim64
     const double *w;      // [mpc_steps][batch][nx] or NULL: no addition
     double *x_traj;       // [mpc_steps][batch][nx] or NULL; the kernel stores every step but the last
 };
+// per-instance models (tiny_batch64_set_models): the further argument of the ",pm" instantiations, the last of a kernel's trailing arguments.  A lane
+// (a thread) reads its instance's matrices straight from the record, once per solve: there is no packed per-lane form
+struct Models64
+{
+    const double *rec; // [batch][stride]: Kinf | Pinf | Quu_inv | AmBKt | Adyn | Bdyn | Q of every instance, column-major (the layout of Params64::mats)
+    size_t stride;     // doubles from one instance's record to the next
+    const double *rho; // [batch]
+};
 // arguments of plant64_sim_kernel: the plant step of one MPC step on the workspace's x.col(0) / u.col(0)
 struct PlantSim64
 {
@@ -91,6 +99,15 @@ hipError_t launch_f64_step(int fn, int nx, int nu, const Params64 &P, int *conv)
 hipError_t launch_f64_rows(int nx, int nu, int N, const Params64 &P, const double *gains, const Mpc64 *mpc);
 // admm_f64_rowsim.hip: mpc_steps > 1 solves of the SIM instantiation for (nx, nu, N) in one launch, wherever there is an MPC one
 hipError_t launch_rows64_sim(int nx, int nu, int N, const Params64 &P, const double *gains, const Mpc64 &mpc, const Sim64 &S);
+// admm_f64_rows_pm.hip / admm_f64_rowsim_pm.hip / admm_f64_thread_pm.hip: the same kernels with per-instance models.  One solve on the sixteen lanes
+// wherever launch_f64_rows has an instantiation; the on-chip closed loop (mpc.mpc_steps >= 1 solves; S.plant == NULL: every instance's own Adyn / Bdyn)
+// wherever launch_rows64_sim has one; one solve with a thread per instance.  launch_models64_gather: the caller's eight [batch] device arrays into
+// the records and rho (q_plus_rho != 0: Q + rho is stored, the code generator's convention)
+hipError_t launch_f64_rows_pm(int nx, int nu, int N, const Params64 &P, const Models64 &M);
+hipError_t launch_rows64_loop_pm(int nx, int nu, int N, const Params64 &P, const Mpc64 &mpc, const Sim64 &S, const Models64 &M);
+hipError_t launch_f64_thread_pm(int nx, int nu, const Params64 &P, const Models64 &M);
+hipError_t launch_models64_gather(const double *rho, const double *Kinf, const double *Pinf, const double *Quu_inv, const double *AmBKt, const double *Adyn,
+                                  const double *Bdyn, const double *Q, double *rec, double *rho_out, int batch, int nx, int nu, int q_plus_rho);
 // admm_f64_plant.hip: x.col(0) <- Adyn * x.col(0) + Bdyn * u.col(0) on the workspace; the same recording u.col(0) in u0_row and sliding the window
 // starts (either may be NULL); the same against a separate plant, with a disturbance and the state trajectory
 hipError_t launch_plant64(int nx, int nu, double *X, const double *U, const double *mats, int batch, int bpad);

@@ -2,7 +2,8 @@
 // src/tinympc/glob_opts.hpp:3): the handle, the device workspace, the choice of kernel and the C-ABI of include/tinympc_batch64.h.
 //
 // Host code only.  Every kernel lives in a translation unit of its own (admm_f64_thread.hip, admm_f64_rows.hip, admm_f64_rowsim.hip,
-// admm_f64_plant.hip; batch64_helpers.hip: the three that move arrays between the host's layout and the workspace's) and is reached through
+// admm_f64_plant.hip; admm_f64_rows_pm.hip, admm_f64_rowsim_pm.hip, admm_f64_thread_pm.hip: per-instance models; batch64_helpers.hip: the three
+// that move arrays between the host's layout and the workspace's) and is reached through
 // the typed launchers of f64_internal.h, so nothing in this file — not the order of its functions, not a name in it — has a bearing on
 // device code.
 //
@@ -70,6 +71,10 @@ struct TinyBatch64
     int plant_mode = 0;
     double *plant_A = nullptr, *plant_B = nullptr, *plant_rows = nullptr, *sim_w = nullptr, *sim_x = nullptr;
     size_t sim_w_cap = 0, sim_x_cap = 0;
+    // per-instance models (tiny_batch64_set_models): one record per instance in the layout of `mats` ([batch][rec_len()]) and rho [batch]; while pm
+    // is set they replace mats, row_gains and rho in every launch
+    bool pm = false;
+    double *pm_rec = nullptr, *pm_rho = nullptr;
     std::vector<double> hm; // host copy of the packed matrices
     bool have_cache = false, have_dyn = false, have_settings = false, mats_dirty = true;
     double rho = 0, abs_pri_tol = 0, abs_dua_tol = 0;
@@ -155,8 +160,8 @@ int gather_window64(TinyBatch64 *tb)
 // gathered_ref = false: the launch reads a window reference from the table itself (the on-chip closed loop)
 int prepare64(TinyBatch64 *tb, Params64 &P, bool gathered_ref = true)
 {
-    if (!tb->have_cache || !tb->have_dyn || !tb->have_settings)
-        return fail64(TINY_BATCH_ENOTREADY, "set_cache, set_dynamics and set_settings must be called first");
+    if (!(tb->pm || (tb->have_cache && tb->have_dyn)) || !tb->have_settings)
+        return fail64(TINY_BATCH_ENOTREADY, "set_cache, set_dynamics (or set_models) and set_settings must be called first");
     if (tb->in_stride[1] != tb->in_stride[2] || tb->in_stride[3] != tb->in_stride[4])
         return fail64(TINY_BATCH_EINVAL, "min and max bounds must both be shared or both be per-instance");
     HIP64(hipSetDevice(tb->device));
@@ -185,10 +190,15 @@ int prepare64(TinyBatch64 *tb, Params64 &P, bool gathered_ref = true)
     return 0;
 }
 
+size_t rec_len(const TinyBatch64 *tb) { return mat_off(tb, 6) + tb->nx; }
+Models64 models_of(const TinyBatch64 *tb) { return Models64{tb->pm_rec, rec_len(tb), tb->pm_rho}; }
+
 // one of the six step functions over the whole batch
 int run_step64(TinyBatch64 *tb, int fn, int *conv_dev)
 {
     CHECK64(tb, "NULL handle");
+    if (tb->pm)
+        return fail64(TINY_BATCH_EUNSUPPORTED, "the six single-function step kernels read one shared model: not available with per-instance models (tiny_batch64_clear_models())");
     Params64 P;
     int rc = prepare64(tb, P);
     if (rc < 0) return rc;
@@ -216,6 +226,13 @@ int launch_solve64(TinyBatch64 *tb, const Params64 &P, const Mpc64 *L = nullptr)
         return fail64(TINY_BATCH_EUNSUPPORTED, "the sixteen-lane fp64 kernel has no instantiation for nx=%d nu=%d N=%d", tb->nx, tb->nu, tb->N);
     if (mpc && !rows) return fail64(TINY_BATCH_EUNSUPPORTED, "the thread-per-instance kernel has no on-chip closed loop");
     if (mpc && !rows_unrolled(tb->nx, tb->nu, tb->N) && tb->N > 32) return fail64(TINY_BATCH_EUNSUPPORTED, "the capacity-64 body has no on-chip closed loop");
+    if (tb->pm)
+    {
+        if (mpc) return fail64(TINY_BATCH_EINVAL, "per-instance models: the on-chip closed loop is launched by the run itself");
+        if (rows) HIP64(launch_f64_rows_pm(tb->nx, tb->nu, tb->N, P, models_of(tb)));
+        else HIP64(launch_f64_thread_pm(tb->nx, tb->nu, P, models_of(tb)));
+        return 0;
+    }
     if (rows) HIP64(launch_f64_rows(tb->nx, tb->nu, tb->N, P, tb->row_gains, L));
     else HIP64(launch_f64_thread(tb->nx, tb->nu, P));
     return 0;
@@ -233,10 +250,11 @@ int grow64(double **buf, size_t *cap, size_t need)
 // The plant step of one MPC step against the handle's plant (the model's matrices without one): d_w / d_x / d_u0 are this step's device rows or NULL
 int enqueue_plant_sim64(TinyBatch64 *tb, const double *d_w, double *d_x, double *d_u0, int *start, int adv)
 {
-    const bool per = tb->plant_mode == 2;
-    const double *A = tb->plant_mode ? tb->plant_A : tb->mats + mat_off(tb, 4), *Bm = tb->plant_mode ? tb->plant_B : tb->mats + mat_off(tb, 5);
-    const PlantSim64 a{tb->arr[TINY_ARR_X], tb->arr[TINY_ARR_U], A, Bm, per ? (size_t)tb->nx * tb->nx : 0, per ? (size_t)tb->nx * tb->nu : 0,
-                       tb->batch, tb->bpad, d_w, d_x, d_u0, start, adv};
+    const bool per = tb->plant_mode == 2, own = tb->pm && !tb->plant_mode; // own: every instance's Adyn / Bdyn, inside its record
+    const double *const model = own ? tb->pm_rec : tb->mats;
+    const double *A = tb->plant_mode ? tb->plant_A : model + mat_off(tb, 4), *Bm = tb->plant_mode ? tb->plant_B : model + mat_off(tb, 5);
+    const PlantSim64 a{tb->arr[TINY_ARR_X], tb->arr[TINY_ARR_U], A, Bm, own ? rec_len(tb) : per ? (size_t)tb->nx * tb->nx : 0,
+                       own ? rec_len(tb) : per ? (size_t)tb->nx * tb->nu : 0, tb->batch, tb->bpad, d_w, d_x, d_u0, start, adv};
     HIP64(launch_plant64_sim(tb->nx, tb->nu, a));
     return 0;
 }
@@ -296,6 +314,7 @@ void tiny_batch64_destroy(TinyBatch64 *tb)
     (void)hipFree(tb->status); (void)hipFree(tb->iter); (void)hipFree(tb->n_unsolved);
     (void)hipFree(tb->table); (void)hipFree(tb->xwin); (void)hipFree(tb->u0_traj); (void)hipFree(tb->xref_start);
     (void)hipFree(tb->plant_A); (void)hipFree(tb->plant_B); (void)hipFree(tb->plant_rows); (void)hipFree(tb->sim_w); (void)hipFree(tb->sim_x);
+    (void)hipFree(tb->pm_rec); (void)hipFree(tb->pm_rho);
     delete tb;
 }
 
@@ -404,7 +423,7 @@ static int mpc_step64(TinyBatch64 *tb, const double *w)
     if (rc < 0) return rc;
     rc = tiny_batch64_solve(tb);                    // :104
     if (rc < 0) return rc;
-    if (tb->plant_mode || w)
+    if (tb->plant_mode || w || tb->pm) // (per-instance models: the plant kernel that takes a matrix pair per instance)
     {
         const size_t row = (size_t)tb->batch * tb->nx;
         if (w)
@@ -477,6 +496,112 @@ int tiny_batch64_plant_mode(TinyBatch64 *tb)
     return tb->plant_mode;
 }
 
+// ---- per-instance models ----------------------------------------------------------------------------------------------------
+static int install_models64(TinyBatch64 *tb, const double *const d[8], int q_plus_rho)
+{
+    if (!tb->pm_rec) HIP64(hipMalloc((void **)&tb->pm_rec, (size_t)tb->batch * rec_len(tb) * sizeof(double)));
+    if (!tb->pm_rho) HIP64(hipMalloc((void **)&tb->pm_rho, (size_t)tb->batch * sizeof(double)));
+    HIP64(launch_models64_gather(d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7], tb->pm_rec, tb->pm_rho, tb->batch, tb->nx, tb->nu, q_plus_rho));
+    tb->pm = true;
+    return 0;
+}
+
+int tiny_batch64_set_models_device(TinyBatch64 *tb, const double *d_rho, const double *d_Kinf, const double *d_Pinf, const double *d_Quu_inv,
+                                   const double *d_AmBKt, const double *d_Adyn, const double *d_Bdyn, const double *d_Q)
+{
+    CHECK64(tb && d_rho && d_Kinf && d_Pinf && d_Quu_inv && d_AmBKt && d_Adyn && d_Bdyn && d_Q, "NULL argument");
+    HIP64(hipSetDevice(tb->device));
+    const double *const d[8] = {d_rho, d_Kinf, d_Pinf, d_Quu_inv, d_AmBKt, d_Adyn, d_Bdyn, d_Q};
+    return install_models64(tb, d, 0);
+}
+
+int tiny_batch64_set_models(TinyBatch64 *tb, const double *rho, const double *Kinf, const double *Pinf, const double *Quu_inv, const double *AmBKt,
+                            const double *Adyn, const double *Bdyn, const double *Q)
+{
+    CHECK64(tb && rho && Kinf && Pinf && Quu_inv && AmBKt && Adyn && Bdyn && Q, "NULL argument");
+    HIP64(hipSetDevice(tb->device));
+    const size_t B = tb->batch, nx = tb->nx, nu = tb->nu;
+    const double *const src[8] = {rho, Kinf, Pinf, Quu_inv, AmBKt, Adyn, Bdyn, Q};
+    const size_t sz[8] = {B, B * nu * nx, B * nx * nx, B * nu * nu, B * nx * nx, B * nx * nx, B * nx * nu, B * nx};
+    size_t total = 0;
+    for (size_t z : sz) total += z;
+    double *buf = nullptr;
+    HIP64(hipMalloc((void **)&buf, total * sizeof(double)));
+    const double *d[8];
+    int rc = 0;
+    size_t o = 0;
+    for (int k = 0; k < 8; k++)
+    {
+        if (rc == 0 && hipMemcpy(buf + o, src[k], sz[k] * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) rc = fail64(TINY_BATCH_EHIP, "tiny_batch64_set_models: hipMemcpy failed");
+        d[k] = buf + o;
+        o += sz[k];
+    }
+    if (rc == 0) rc = install_models64(tb, d, 0);
+    if (hipDeviceSynchronize() != hipSuccess && rc == 0) rc = fail64(TINY_BATCH_EHIP, "tiny_batch64_set_models: hipDeviceSynchronize failed");
+    (void)hipFree(buf);
+    return rc;
+}
+
+int tiny_batch64_clear_models(TinyBatch64 *tb)
+{
+    CHECK64(tb, "NULL handle");
+    if (!tb->pm) return 0;
+    HIP64(hipSetDevice(tb->device));
+    HIP64(hipDeviceSynchronize()); // a launch still reading the records may be in flight
+    for (double **p : {&tb->pm_rec, &tb->pm_rho})
+    {
+        (void)hipFree(*p);
+        *p = nullptr;
+    }
+    tb->pm = false;
+    return 0;
+}
+
+int tiny_batch64_models_per_instance(TinyBatch64 *tb)
+{
+    CHECK64(tb, "NULL handle");
+    return tb->pm ? 1 : 0;
+}
+
+int tiny_batch64_set_systems(TinyBatch64 *tb, const double *A, const double *B, const double *Q, const double *R, const double *rho, int *iters)
+{
+    CHECK64(tb && A && B && Q && R && rho, "NULL argument");
+    HIP64(hipSetDevice(tb->device));
+    const size_t Bn = tb->batch, nx = tb->nx, nu = tb->nu;
+    // inputs A | B | Q | R | rho, then the outputs Kinf | Pinf | Quu_inv | AmBKt: all of it stays fp64 from the recursion into the records
+    const size_t sz[9] = {Bn * nx * nx, Bn * nx * nu, Bn * nx, Bn * nu, Bn, Bn * nu * nx, Bn * nx * nx, Bn * nu * nu, Bn * nx * nx};
+    const double *const in[5] = {A, B, Q, R, rho};
+    size_t nd = 0;
+    for (size_t z : sz) nd += z;
+    double *d = nullptr;
+    int *it = nullptr;
+    int rc = 0;
+    if (hipMalloc((void **)&d, nd * sizeof(double)) != hipSuccess || hipMalloc((void **)&it, Bn * sizeof(int)) != hipSuccess)
+        rc = fail64(TINY_BATCH_EHIP, "tiny_batch64_set_systems: allocation failed");
+    double *dp[9];
+    size_t o = 0;
+    for (int k = 0; k < 9; k++) { dp[k] = d + o; o += sz[k]; }
+    for (int k = 0; k < 5 && rc == 0; k++)
+        if (hipMemcpy(dp[k], in[k], sz[k] * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) rc = fail64(TINY_BATCH_EHIP, "tiny_batch64_set_systems: hipMemcpy failed");
+    int nfail = 0;
+    if (rc == 0)
+    {
+        nfail = tiny_batch_riccati_device(tb->nx, tb->nu, tb->batch, dp[0], dp[1], dp[2], dp[3], dp[4], dp[5], dp[6], dp[7], dp[8], nullptr, it, nullptr);
+        if (nfail < 0) rc = fail64(nfail, "tiny_batch64_set_systems: %s", tiny_batch_last_error());
+    }
+    if (rc == 0 && iters && hipMemcpy(iters, it, Bn * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) rc = fail64(TINY_BATCH_EHIP, "tiny_batch64_set_systems: hipMemcpy failed");
+    if (rc == 0 && nfail > 0)
+        rc = fail64(TINY_BATCH_EINVAL, "tiny_batch64_set_systems: the Riccati recursion is singular for %d of %zu systems (iters = -1); models unchanged", nfail, Bn);
+    if (rc == 0)
+    {
+        const double *const m[8] = {dp[4], dp[5], dp[6], dp[7], dp[8], dp[0], dp[1], dp[2]}; // rho, the cache, Adyn = A, Bdyn = B, Q (+ rho in the gather)
+        rc = install_models64(tb, m, 1);
+    }
+    if (hipDeviceSynchronize() != hipSuccess && rc == 0) rc = fail64(TINY_BATCH_EHIP, "tiny_batch64_set_systems: hipDeviceSynchronize failed");
+    (void)hipFree(d); (void)hipFree(it);
+    return rc;
+}
+
 int tiny_batch64_set_xref_window(TinyBatch64 *tb, const double *table, int rows, const int *start)
 {
     CHECK64(tb && table && start, "NULL argument");
@@ -524,7 +649,8 @@ int tiny_batch64_mpc_run_sim(TinyBatch64 *tb, int steps, int window_advance, con
     }
     const size_t row_len = (size_t)tb->batch * tb->nu, need = u0_traj_host ? (size_t)steps * row_len : 0;
     // a run is simulated when a plant is set or the call passes a disturbance or asks for the state trajectory; any other run enqueues what it always has
-    const bool sim = tb->plant_mode != 0 || w_host != nullptr || x_traj_host != nullptr;
+    // (with per-instance models every run is: the simulated kernels are the ones that take a plant per instance, here the instance's own model)
+    const bool sim = tb->plant_mode != 0 || w_host != nullptr || x_traj_host != nullptr || tb->pm;
     const size_t xrow = (size_t)tb->batch * tb->nx, need_w = w_host ? (size_t)steps * xrow : 0, need_x = x_traj_host ? (size_t)steps * xrow : 0;
     for (const int rg : {grow64(&tb->u0_traj, &tb->u0_traj_cap, need), grow64(&tb->sim_w, &tb->sim_w_cap, need_w), grow64(&tb->sim_x, &tb->sim_x_cap, need_x)})
         if (rg < 0) return rg;
@@ -550,7 +676,14 @@ int tiny_batch64_mpc_run_sim(TinyBatch64 *tb, int steps, int window_advance, con
         HIP64(hipMemsetAsync(tb->n_unsolved, 0, sizeof(int), 0));
         // y and g of the workspace are zero from the first solve on: the kernel starts from that without reading them
         const int k = steps - 1;
-        if (sim)
+        if (tb->pm)
+        {
+            const Sim64 S{tb->plant_mode ? tb->plant_rows : nullptr, tb->plant_mode == 2 ? (size_t)(tb->nx + tb->nu) * 16 : 0, d_w, d_x};
+            HIP64(launch_rows64_loop_pm(tb->nx, tb->nu, tb->N, P, L, S, models_of(tb)));
+            const int rc = plant_sim(k);
+            if (rc < 0) return rc;
+        }
+        else if (sim)
         {
             // (one step never reaches the kernel's plant step: the MPC instantiation serves it)
             if (steps > 1)
@@ -637,9 +770,10 @@ const char *tiny_batch64_kernel_name(TinyBatch64 *tb)
     static thread_local char nm[64];
     if (!tb) return "";
     const bool rows = rows_chosen(tb);
-    if (rows && !rows_unrolled(tb->nx, tb->nu, tb->N)) snprintf(nm, sizeof nm, "rows64<%d,%d,n<=%d>", tb->nx, tb->nu, tb->N <= 32 ? 32 : 64);
-    else if (rows) snprintf(nm, sizeof nm, "rows64<%d,%d,%d>", tb->nx, tb->nu, tb->N);
-    else snprintf(nm, sizeof nm, "thread64<%d,%d>", tb->nx, tb->nu);
+    const char *const pm = tb->pm ? ",pm" : "";
+    if (rows && !rows_unrolled(tb->nx, tb->nu, tb->N)) snprintf(nm, sizeof nm, "rows64<%d,%d,n<=%d%s>", tb->nx, tb->nu, tb->N <= 32 ? 32 : 64, pm);
+    else if (rows) snprintf(nm, sizeof nm, "rows64<%d,%d,%d%s>", tb->nx, tb->nu, tb->N, pm);
+    else snprintf(nm, sizeof nm, "thread64<%d,%d%s>", tb->nx, tb->nu, pm);
     return nm;
 }
 
@@ -650,7 +784,8 @@ const char *tiny_batch64_closed_loop_kernel_name(TinyBatch64 *tb)
     const char *solve = tiny_batch64_kernel_name(tb);
     if (!onchip64(tb)) return solve;
     // rows64<12,4,10> -> rows64<12,4,10,mpc>; while a plant is set ,sim> (a run that passes w or x_traj without one is simulated too: only the call knows)
-    snprintf(nm, sizeof nm, "%.*s,%s>", (int)strlen(solve) - 1, solve, tb->plant_mode ? "sim" : "mpc");
+    // with per-instance models ",pm" stays last: rows64<12,4,10,pm> -> rows64<12,4,10,mpc,pm>
+    snprintf(nm, sizeof nm, "%.*s,%s%s>", (int)strlen(solve) - (tb->pm ? 4 : 1), solve, tb->plant_mode ? "sim" : "mpc", tb->pm ? ",pm" : "");
     return nm;
 }
 

@@ -113,6 +113,9 @@ def load_library(build_if_missing: bool = False) -> C.CDLL:
         "tiny_batch64_mpc_run": [P, C.c_int, C.c_int], "tiny_batch64_mpc_run_traj": [P, C.c_int, C.c_int, D],
         "tiny_batch64_set_plant": [P, D, D, C.c_int], "tiny_batch64_clear_plant": [P], "tiny_batch64_plant_mode": [P],
         "tiny_batch64_mpc_step_sim": [P, D], "tiny_batch64_mpc_run_sim": [P, C.c_int, C.c_int, D, D, D],
+        "tiny_batch64_set_models": [P, D, D, D, D, D, D, D, D], "tiny_batch64_set_models_device": [P, P, P, P, P, P, P, P, P],
+        "tiny_batch64_clear_models": [P], "tiny_batch64_models_per_instance": [P],
+        "tiny_batch64_set_systems": [P, D, D, D, D, D, I],
     }
     for name, args in sig64.items():
         fn = getattr(lib, name)
@@ -761,6 +764,37 @@ class TinyBatchSolver64:
         self._check(self.lib.tiny_batch64_mpc_run_sim(self._h, int(steps), int(window_advance), None if a is None else self._dp(a), self._dp(u0),
                                                       None if xt is None else self._dp(xt)))
         return u0, xt
+
+    # -- per-instance models (tiny_batch64_set_models) ------------------------------------------------
+    def set_models(self, models: dict):
+        """Every instance its own model: `models` holds rho [B] and Kinf, Pinf, Quu_inv, AmBKt, Adyn, Bdyn [B][rows][cols], Q [B][nx], the keys and
+        the logical orientation of the prob dicts (Q as stored in work.Q).  Everything stays float64."""
+        B = self.B
+        rho = np.ascontiguousarray(np.asarray(models["rho"], np.float64).reshape(B))
+        arrs = [_colmajor_batch(models[k], np.float64) for k in ("Kinf", "Pinf", "Quu_inv", "AmBKt", "Adyn", "Bdyn")]
+        q = np.ascontiguousarray(np.asarray(models["Q"], np.float64).reshape(B, self.nx))
+        for k, a in zip(("Kinf", "Pinf", "Quu_inv", "AmBKt", "Adyn", "Bdyn"), arrs):
+            assert a.shape[0] == B, (k, a.shape)
+        self._check(self.lib.tiny_batch64_set_models(self._h, self._dp(rho), *[self._dp(a) for a in arrs], self._dp(q)))
+
+    def set_systems(self, A, B, Q, R, rho) -> np.ndarray:
+        """Per-instance models from fp64 systems: the Riccati cache of every instance on the GPU (tiny_batch64_set_systems), installed unrounded with
+        the conventions of problems.with_cache.  A [B][nx][nx], B [B][nx][nu], Q [B][nx], R [B][nu] (without rho), rho [B].  Returns iters [B]."""
+        n = self.B
+        a, b = _colmajor_batch(A, np.float64), _colmajor_batch(B, np.float64)
+        q = np.ascontiguousarray(np.asarray(Q, np.float64).reshape(n, self.nx))
+        r = np.ascontiguousarray(np.asarray(R, np.float64).reshape(n, self.nu))
+        rh = np.ascontiguousarray(np.asarray(rho, np.float64).reshape(n))
+        it = np.zeros(n, np.int32)
+        self._check(self.lib.tiny_batch64_set_systems(self._h, self._dp(a), self._dp(b), self._dp(q), self._dp(r), self._dp(rh), it.ctypes.data_as(C.POINTER(C.c_int))))
+        return it
+
+    def clear_models(self):
+        """Back to the batch-shared cache and dynamics."""
+        self._check(self.lib.tiny_batch64_clear_models(self._h))
+
+    def models_per_instance(self) -> bool:
+        return bool(self._check(self.lib.tiny_batch64_models_per_instance(self._h)))
 
     def first_columns(self):
         """(x.col(0), u.col(0)) as [B][nx], [B][nu]."""

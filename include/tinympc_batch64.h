@@ -114,6 +114,33 @@ extern "C"
     int tiny_batch64_mpc_run_sim(TinyBatch64 *tb, int steps, int window_advance, const double *w /*[steps][batch][nx] or NULL*/,
                                  double *u0_traj /*[steps][batch][nu] or NULL*/, double *x_traj /*[steps][batch][nx] or NULL*/);
 
+    /* Per-instance models (the float library's tiny_batch_set_models family, in double): every instance its own TinyCache{rho, Kinf, Pinf, Quu_inv,
+     * AmBKt} (types.hpp:26-34) and its own Adyn, Bdyn, Q (types.hpp:82-85), each array [batch][...] with every instance's matrix column-major.  This
+     * satisfies the "cache and dynamics set" readiness check of a solve and replaces the batch-shared cache / dynamics until
+     * tiny_batch64_clear_models(); settings stay per batch.  The records live on the device, one per instance in the layout Kinf | Pinf | Quu_inv |
+     * AmBKt | Adyn | Bdyn | Q (3 nx^2 + 2 nx nu + nu^2 + nx doubles: 4.4 KB for the quadrotor) with rho beside them; every kernel reads its
+     * instance's record directly.  _device takes DEVICE pointers on the handle's device: one gather kernel on the null stream, asynchronous, nothing
+     * passes through the host.
+     * Served: tiny_batch64_solve on both kernels (every sixteen-lane instantiation, every class of the thread-per-instance kernel), with shared or
+     * per-instance bounds and any reference, and every closed-loop call.  A run is ONE launch wherever it is without per-instance models; with no
+     * plant set every instance's plant step uses its own Adyn / Bdyn, and a plant that is set stays independent of the models in all three modes.
+     * tiny_batch64_kernel_name and _closed_loop_kernel_name carry ",pm" last inside the brackets ("rows64<12,4,10,pm>", "rows64<12,2,n<=32,pm>",
+     * "thread64<16,4,pm>", "rows64<12,4,10,mpc,pm>", "rows64<12,4,10,sim,pm>").  Refused with TINY_BATCH_EUNSUPPORTED and a message: the six
+     * single-function step calls, which read one shared model. */
+    int tiny_batch64_set_models(TinyBatch64 *tb, const double *rho /*[B]*/, const double *Kinf /*[B][nu*nx]*/, const double *Pinf /*[B][nx*nx]*/,
+                                const double *Quu_inv /*[B][nu*nu]*/, const double *AmBKt /*[B][nx*nx]*/, const double *Adyn /*[B][nx*nx]*/,
+                                const double *Bdyn /*[B][nx*nu]*/, const double *Q /*[B][nx]*/);
+    int tiny_batch64_set_models_device(TinyBatch64 *tb, const double *d_rho, const double *d_Kinf, const double *d_Pinf, const double *d_Quu_inv,
+                                       const double *d_AmBKt, const double *d_Adyn, const double *d_Bdyn, const double *d_Q);
+    /* back to the batch-shared cache / dynamics of tiny_batch64_set_cache / tiny_batch64_set_dynamics; the device memory of the records is released */
+    int tiny_batch64_clear_models(TinyBatch64 *tb);
+    /* 1 while per-instance models are in force, 0 otherwise */
+    int tiny_batch64_models_per_instance(TinyBatch64 *tb);
+    /* HOST fp64 systems in ([B][...] as above; Q, R without rho), tiny_batch_riccati_device on the handle's device, the result installed as the handle's
+     * per-instance models with the conventions of the code generator and NO rounding: Adyn = A, Bdyn = B, Q = Q + rho, the cache the fp64 result
+     * itself.  iters ([B], may be NULL) as tiny_batch_riccati_device.  Any failed system: TINY_BATCH_EINVAL and the handle's models are unchanged. */
+    int tiny_batch64_set_systems(TinyBatch64 *tb, const double *A, const double *B, const double *Q, const double *R, const double *rho, int *iters);
+
     /* Implementation: 0 = automatic (the second where (nx, nu, N) has an instantiation, else the first), 1 = one thread per
      * instance with the state in HBM (any N), 2 = sixteen lanes per instance with the state in registers for the whole solve
      * (instantiated (nx, nu, N): (12,4,10) as shipped, (12,4,20), (12,4,30), (4,1,10), (8,4,9)).  Identical results. */
