@@ -18,9 +18,26 @@ namespace tinympc
 // instantiations per class: (1, 3) for launches that queue more waves than the chip holds (occupancy hides the latency),
 // (4, 2) for launches of at most 2 048 instances, where every wave is resident anyway and a deeper look-ahead is worth
 // more than the third wave: 7.1 -> 5.7 ms at 2 048 instances of the nx = 32 class, 40.6 vs 43.9 ms at 16 384.
+// The kernel is compiled in two translation units from this one text.  Here it is admm_wavestream_kernel(P), one gain table and one rho for the launch.
+// Under TINY_WAVE_PM_UNIT (admm_wave_pm.hip) it is admm_wavestream_pm_kernel(P, M) with per-instance models: the instance is the wave, so its own gain
+// table is a wave-uniform base address and its rho a wave-uniform value.  M is the trailing argument there and an unused local here; it is read under
+// `if constexpr (PM)` only, and nothing else of the body differs.
+#ifdef TINY_WAVE_PM_UNIT
+#define TINY_WAVESTREAM_KERNEL admm_wavestream_pm_kernel
+#define TINY_WAVESTREAM_ARGS const RowParams P, const ModelParams M
+#else
+#define TINY_WAVESTREAM_KERNEL admm_wavestream_kernel
+#define TINY_WAVESTREAM_ARGS const RowParams P
+#endif
 template <int NX, int NU, int PF, int WPS>
-__global__ __launch_bounds__(WAVE, WPS) void admm_wavestream_kernel(const RowParams P)
+__global__ __launch_bounds__(WAVE, WPS) void TINY_WAVESTREAM_KERNEL(TINY_WAVESTREAM_ARGS)
 {
+#ifdef TINY_WAVE_PM_UNIT
+    constexpr bool PM = true;
+#else
+    constexpr bool PM = false;
+    [[maybe_unused]] const ModelParams M{};
+#endif
     using PL = WavePlans<NX, NU>;
     __shared__ __attribute__((aligned(16))) float vec[WAVE]; // broadcast buffer of lane_products
     const int lane = threadIdx.x;
@@ -28,11 +45,12 @@ __global__ __launch_bounds__(WAVE, WPS) void admm_wavestream_kernel(const RowPar
     const bool is_x = lane < NX, is_u = (lane >= NX) && (lane < NX + NU);
     const int N = P.N;
     const int rowbase = (inst * N) * WAVE + lane;
-    const float rho = P.rho;
+    const float rho = wave_rho<PM>(P, M, inst);
+    const float *const mats = wave_mats<PM>(P, M, inst);
     const float2 *bnd = reinterpret_cast<const float2 *>(P.bounds) + (size_t)inst * P.bounds_inst_stride; // shared or per instance
     WaveGains<NX, NU> G;
-    G.load(P.mats, lane);
-    const float qrow = P.mats[(2 * NX + 2 * NU) * WAVE + lane];
+    G.load(mats, lane);
+    const float qrow = mats[(2 * NX + 2 * NU) * WAVE + lane];
     const RowXref<false, WAVE> xref(P, inst, true, inst, lane);
     const float x0 = P.xu[rowbase];
     float pterm;
@@ -40,7 +58,7 @@ __global__ __launch_bounds__(WAVE, WPS) void admm_wavestream_kernel(const RowPar
         // -(Xref_{N-1}^T Pinf) (admm.cpp:83), x rows; PT[k] = Pinf(k, r)
         float PT[NX], t[NX];
 #pragma unroll
-        for (int k = 0; k < NX; k++) PT[k] = P.mats[(2 * NX + 2 * NU + 1 + k) * WAVE + lane];
+        for (int k = 0; k < NX; k++) PT[k] = mats[(2 * NX + 2 * NU + 1 + k) * WAVE + lane];
         lane_products<0, NX>(t, xref.at(P, N - 1, lane), PT, vec, lane);
         pterm = -wreduce<PL::TERM>(t);
     }
@@ -157,6 +175,23 @@ __global__ __launch_bounds__(WAVE, WPS) void admm_wavestream_kernel(const RowPar
     }
 }
 
+#ifdef TINY_WAVE_PM_UNIT
+// Per-instance models (tiny_batch_set_models with tiny_batch_set_row_kernel(tb, 6)): the launcher of the PM instantiations, compiled as admm_wave_pm.hip
+// (a translation unit of its own, so that admm_wave.hip keeps its code).  The gain table is the one admm_waveres_pm.hip packs.
+hipError_t launch_admm_wavestream_pm(int nx, int nu, const RowParams &P, const ModelParams &M, hipStream_t stream)
+{
+    if (!M.mats || !M.rho || M.mats_stride != (unsigned)pm_wave_floats(nx, nu)) return hipErrorInvalidValue;
+#define TINY_WAVE_PM_DISPATCH(NX, NU)                                                                         \
+    if (nx == NX && nu == NU)                                                                                 \
+    {                                                                                                         \
+        if (P.batch <= 2048) hipLaunchKernelGGL((admm_wavestream_pm_kernel<NX, NU, 4, 2>), dim3(P.batch), dim3(WAVE), 0, stream, P, M); \
+        else hipLaunchKernelGGL((admm_wavestream_pm_kernel<NX, NU, 1, 3>), dim3(P.batch), dim3(WAVE), 0, stream, P, M);                 \
+        return hipGetLastError();                                                                             \
+    }
+    TINY_FOR_EACH_WAVEDIMS(TINY_WAVE_PM_DISPATCH)
+    return hipErrorInvalidValue;
+}
+#else
 bool wavedims_supported(int nx, int nu)
 {
 #define TINY_WAVEDIMS_CHECK(NX, NU) \
@@ -177,5 +212,6 @@ hipError_t launch_admm_wavestream(int nx, int nu, const RowParams &P, hipStream_
     TINY_FOR_EACH_WAVEDIMS(TINY_WAVE_DISPATCH)
     return hipErrorInvalidValue;
 }
+#endif // TINY_WAVE_PM_UNIT
 
 } // namespace tinympc

@@ -43,9 +43,26 @@ struct StepRegs
     __device__ __forceinline__ float get(int i) const { return i < 32 ? lo[i] : (i < 48 ? mid[i - 32] : (i == 48 ? t0 : t1)); }
 };
 
+// The kernel is compiled in two translation units from this one text.  Here it is admm_waveres_kernel(P), one gain table and one rho for the launch.
+// Under TINY_WAVERES_PM_UNIT (admm_waveres_pm.hip) it is admm_waveres_pm_kernel(P, M) with per-instance models: the instance is the wave, so its own
+// gain table is a wave-uniform base address and its rho a wave-uniform value.  M is the trailing argument there and an unused local here; it is read
+// under `if constexpr (PM)` only, and nothing else of the body differs.
+#ifdef TINY_WAVERES_PM_UNIT
+#define TINY_WAVERES_KERNEL admm_waveres_pm_kernel
+#define TINY_WAVERES_ARGS const RowParams P, const ModelParams M
+#else
+#define TINY_WAVERES_KERNEL admm_waveres_kernel
+#define TINY_WAVERES_ARGS const RowParams P
+#endif
 template <int NX, int NU, bool EXACT>
-__global__ __launch_bounds__(WAVE, 2) void admm_waveres_kernel(const RowParams P)
+__global__ __launch_bounds__(WAVE, 2) void TINY_WAVERES_KERNEL(TINY_WAVERES_ARGS)
 {
+#ifdef TINY_WAVERES_PM_UNIT
+    constexpr bool PM = true;
+#else
+    constexpr bool PM = false;
+    [[maybe_unused]] const ModelParams M{};
+#endif
     using PL = WavePlans<NX, NU>;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float *const vec = lds;               // [64] x_i | u_i broadcast of the forward sweep (and of the terminal term)
@@ -58,9 +75,10 @@ __global__ __launch_bounds__(WAVE, 2) void admm_waveres_kernel(const RowParams P
     const bool is_x = lane < NX, is_u = (lane >= NX) && (lane < NX + NU);
     const int N = P.N;
     const int rowbase = (inst * N) * WAVE + lane;
-    const float rho = P.rho;
+    const float rho = wave_rho<PM>(P, M, inst);
+    const float *const mats = wave_mats<PM>(P, M, inst);
     const float2 *bnd = reinterpret_cast<const float2 *>(P.bounds) + (size_t)inst * P.bounds_inst_stride + lane; // bnd[i * WAVE]
-    const float qrow = P.mats[(2 * NX + 2 * NU) * WAVE + lane];
+    const float qrow = mats[(2 * NX + 2 * NU) * WAVE + lane];
     const RowXref<false, WAVE> xref(P, inst, true, inst, lane);
     const bool cold = P.cold_start != 0, zdual = cold || (P.duals_zero != 0);
 
@@ -90,7 +108,7 @@ __global__ __launch_bounds__(WAVE, 2) void admm_waveres_kernel(const RowParams P
     {
         float PT[NX], t[NX]; // -(Xref_{N-1}^T Pinf) (admm.cpp:83), x rows; PT[k] = Pinf(k, r)
 #pragma unroll
-        for (int k = 0; k < NX; k++) PT[k] = P.mats[(2 * NX + 2 * NU + 1 + k) * WAVE + lane];
+        for (int k = 0; k < NX; k++) PT[k] = mats[(2 * NX + 2 * NU + 1 + k) * WAVE + lane];
         if constexpr (EXACT)
         {
             lane_products<0, NX>(t, xrN, PT, vec, lane);
@@ -115,7 +133,7 @@ __global__ __launch_bounds__(WAVE, 2) void admm_waveres_kernel(const RowParams P
             WaveGainsF<NX, NU> GF;
             int oz; // an opaque zero: the loads are loop invariant, and hoisted out of the iteration loop they would be live across both sweeps again
             asm volatile("s_mov_b32 %0, 0" : "=s"(oz));
-            GF.load(P.mats + oz, lane);
+            GF.load(mats + oz, lane);
             float s = x0;
             float2 lh = bnd[0];
             float b_cur = b[0];
@@ -190,7 +208,7 @@ __global__ __launch_bounds__(WAVE, 2) void admm_waveres_kernel(const RowParams P
             WaveGainsB<NX, NU> GB;
             int oz;
             asm volatile("s_mov_b32 %0, 0" : "=s"(oz));
-            GB.load(P.mats + oz, lane);
+            GB.load(mats + oz, lane);
             const bool upd_d = is_u && !keep_d;
             const int top = N - 2;
             int o = rowbase + top * WAVE;
@@ -272,7 +290,7 @@ __global__ __launch_bounds__(WAVE, 2) void admm_waveres_kernel(const RowParams P
         WaveGains<NX, NU> G;
         int oz;
         asm volatile("s_mov_b32 %0, 0" : "=s"(oz));
-        G.load(P.mats + oz, lane);
+        G.load(mats + oz, lane);
         float s = x0;
         int o = rowbase;
 #pragma unroll 1
@@ -299,6 +317,69 @@ __global__ __launch_bounds__(WAVE, 2) void admm_waveres_kernel(const RowParams P
     }
 }
 
+#ifdef TINY_WAVERES_PM_UNIT
+// Per-instance models (tiny_batch_set_models with tiny_batch_set_row_kernel(tb, 7)): the launcher of the PM instantiations and the kernel that packs the
+// gain tables of both wave kernels, compiled as admm_waveres_pm.hip (a translation unit of its own, so that admm_waveres.hip keeps its code).
+hipError_t launch_admm_waveres_pm(int nx, int nu, bool exact, const RowParams &P, const ModelParams &M, hipStream_t stream)
+{
+    if (!M.mats || !M.rho || P.N > WAVERES_MAX_N || M.mats_stride != (unsigned)pm_wave_floats(nx, nu)) return hipErrorInvalidValue;
+    const size_t ldsb = (size_t)(4 * WAVE + P.N * WAVE) * sizeof(float);
+#define TINY_WAVERES_PM_DISPATCH(NX, NU)                                                                                     \
+    if (nx == NX && nu == NU)                                                                                                \
+    {                                                                                                                        \
+        if (exact) hipLaunchKernelGGL((admm_waveres_pm_kernel<NX, NU, true>), dim3(P.batch), dim3(WAVE), ldsb, stream, P, M);  \
+        else hipLaunchKernelGGL((admm_waveres_pm_kernel<NX, NU, false>), dim3(P.batch), dim3(WAVE), ldsb, stream, P, M);       \
+        return hipGetLastError();                                                                                            \
+    }
+    TINY_FOR_EACH_WAVEDIMS(TINY_WAVERES_PM_DISPATCH)
+    return hipErrorInvalidValue;
+}
+
+// The gain tables of both wave kernels' PM instantiations, from the handle's model records (Kinf | Pinf | Quu_inv | AmBKt | Adyn | Bdyn | Q, pm_gen_floats
+// apart): [batch][(3nx + 2nu + 1) * 64] floats, rows M1, M2, M3, M45, Q, PT — element for element what pack_gains writes for one shared model at row
+// width 64 (the optional-term rows are not instantiated with per-instance models).  fast = 1: the fma form (u rows of M1 and x rows of M45 hold -K; the
+// exact form holds +K and the kernel negates the sum), as models_pack_row_kernel does at width 16.  One table per arithmetic form, packed when a launch
+// first needs it: 14.6 KB per (16,4) instance, 33 KB per (32,16) instance — 541 MB at 16 384 instances of the latter.
+__global__ void models_pack_wave_kernel(const float *__restrict__ recs, float *__restrict__ dst, int batch, int nx, int nu, int fast)
+{
+    const int G = pm_gen_floats(nx, nu), R = pm_wave_floats(nx, nu);
+    const long long total = (long long)batch * R;
+    const float sg = fast ? -1.f : 1.f;
+    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x)
+    {
+        const long long b = e / R;
+        const int o = (int)(e % R), reg = o / WAVE, r = o % WAVE;
+        const float *K = recs + b * G, *Pf = K + nu * nx, *Qi = Pf + nx * nx, *Am = Qi + nu * nu, *A = Am + nx * nx, *Bm = A + nx * nx, *Q = Bm + nx * nu;
+        const bool isx = r < nx, isu = r >= nx && r < nx + nu;
+        const int mr = r - nx;
+        float v = 0.f;
+        if (reg < nx) v = isx ? A[reg * nx + r] : (isu ? sg * K[reg * nu + mr] : 0.f); // M1: A(r,k) | K(m,k) (exact), -K(m,k) (fast)
+        else if (reg < nx + nu) v = isx ? Bm[(reg - nx) * nx + r] : 0.f;                // M2: B(r,m)
+        else if (reg < 2 * nx + nu)
+        {
+            const int k = reg - nx - nu;                                                // M3: AmBKt(r,k) | B(k,m)
+            v = isx ? Am[k * nx + r] : (isu ? Bm[mr * nx + k] : 0.f);
+        }
+        else if (reg < 2 * nx + 2 * nu)
+        {
+            const int mm = reg - 2 * nx - nu;                                           // M45: K(m,r) (exact), -K(m,r) (fast) | Quu_inv(mr,m)
+            v = isx ? sg * K[r * nu + mm] : (isu ? Qi[mm * nu + mr] : 0.f);
+        }
+        else if (reg == 2 * nx + 2 * nu) v = isx ? Q[r] : 0.f;                          // Q(r)
+        else v = isx ? Pf[r * nx + (reg - 2 * nx - 2 * nu - 1)] : 0.f;                  // PT[k]: Pinf(k,r)
+        dst[e] = v;
+    }
+}
+
+hipError_t launch_models_pack_wave(const float *recs, float *dst, int batch, int nx, int nu, int fast, hipStream_t stream)
+{
+    const long long total = (long long)batch * pm_wave_floats(nx, nu);
+    if (!recs || !dst || total <= 0) return hipErrorInvalidValue;
+    const long long blocks = (total + 255) / 256;
+    hipLaunchKernelGGL(models_pack_wave_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, stream, recs, dst, batch, nx, nu, fast);
+    return hipGetLastError();
+}
+#else
 bool waveres_supported(int nx, int nu, int N) { return wavedims_supported(nx, nu) && N <= WAVERES_MAX_N; }
 
 hipError_t launch_admm_waveres(int nx, int nu, bool exact, const RowParams &P, hipStream_t stream)
@@ -314,5 +395,6 @@ hipError_t launch_admm_waveres(int nx, int nu, bool exact, const RowParams &P, h
     TINY_FOR_EACH_WAVEDIMS(TINY_WAVERES_DISPATCH)
     return hipErrorInvalidValue;
 }
+#endif // TINY_WAVERES_PM_UNIT
 
 } // namespace tinympc

@@ -201,10 +201,11 @@ struct TinyBatch
     bool iter_history = false;    // iter[] holds the counts of a solve of THIS workspace's instances (not a reset, not an upload): the history order's key
     // per-instance models (tiny_batch_set_models): one record per instance in the run-time-dimension kernel's form ([batch][pm_gen_floats]: Kinf | Pinf |
     // Quu_inv | AmBKt | Adyn | Bdyn | Q, which is also what the plant step reads), rho [batch]; the 16-lane kernel's two forms of the gain rows
-    // ([batch][pm_row_floats], [0] exact, [1] fma) are packed from the records on the device when a launch first needs one
+    // ([batch][pm_row_floats], [0] exact, [1] fma) are packed from the records on the device when a launch first needs one, and so are the two wave
+    // kernels' ([batch][pm_wave_floats]: the same rows at row width 64 — 33 KB per instance of the nx = 32 class and form)
     bool pm = false;
-    float *pm_src = nullptr, *pm_rho = nullptr, *pm_row[2] = {};
-    bool pm_row_dirty[2] = {true, true};
+    float *pm_src = nullptr, *pm_rho = nullptr, *pm_row[2] = {}, *pm_wave[2] = {};
+    bool pm_row_dirty[2] = {true, true}, pm_wave_dirty[2] = {true, true};
     // the simulated plant of the closed-loop calls (tiny_batch_set_plant): 0 the model's own Adyn / Bdyn, 1 one shared plant, 2 one per instance.  Column-major
     // copies for the plant kernel ([1 or batch][nx*nx], [1 or batch][nx*nu]) and, where the class has a 16-lane kernel, the rows of [A | B] packed for its
     // on-chip loop ([1 or batch][plant_row_floats]: SimParams)
@@ -823,7 +824,7 @@ struct KernelPlan
 {
     Kernel kernel = Kernel::Rowlane;
     bool exact = true;   // arithmetic: the reference's summation order, or fma
-    bool pm = false;     // per-instance models (the ",pm" instantiations of the 16-lane and the run-time-dimension kernel)
+    bool pm = false;     // per-instance models (the ",pm" instantiations of the 16-lane, the two wave and the run-time-dimension kernel)
     bool pi = false;     // tile16 with per-instance bounds / reference (admm_tile16_pi.hip)
     Tile16Pi pi_tables{}; // ... and which of its tables go through the rings
 };
@@ -896,14 +897,24 @@ int resolve_plan(const TinyBatch *tb, bool closed_loop, KernelPlan *out, bool si
     if (tb->pm)
     {
         // per-instance models: the unrolled 16-lane kernel where (nx, nu, N) is instantiated, the run-time-dimension kernel otherwise (both read a gain
-        // record per instance).  Every other kernel keeps ONE gain table for the whole launch — tile16's MFMA A operand is one gain matrix for all sixteen
-        // columns, the streaming and wave kernels stage theirs once per workgroup — and is never chosen.
+        // record per instance).  The two wave kernels (one wavefront = one workgroup = one instance: a per-instance gain table is a wave-uniform base
+        // address) serve them too, on request: a forced family 6 or 7 (tiny_batch_set_row_kernel) resolves the automatic choice and the row variants to
+        // that family's ",pm" instantiations; the automatic choice without one stays where tests/golden/kernel_choice.json records it.  Every other kernel
+        // keeps ONE gain table for the whole launch — tile16's and tile48's MFMA A operand is one gain matrix for all sixteen columns, the streaming
+        // kernels stage theirs once per workgroup of several instances — and is never chosen.
+        const bool wave_forced = tb->row_family_forced == Kernel::Wavestream || tb->row_family_forced == Kernel::Waveres;
         if (tb->h16)
             return fail(TINY_BATCH_EUNSUPPORTED, "per-instance models (tiny_batch_set_models) are implemented for fp32 storage only: tiny_batch_set_storage(tb, 32) or tiny_batch_clear_models()");
         if (tb->en_uref || tb->en_d2p)
             return fail(TINY_BATCH_EUNSUPPORTED, "the optional Uref / coeff_d2p terms are not implemented with per-instance models (tiny_batch_set_optional_terms(tb, 0, 0) or tiny_batch_clear_models())");
         if (v == VAR_STREAM)
             return fail(TINY_BATCH_EUNSUPPORTED, "the streaming MFMA kernel (variant 1) holds one gain matrix for the whole launch and cannot serve per-instance models");
+        if (wave_forced && v != VAR_GENERIC)
+        {
+            if (v == VAR_ROW_FAST && tb->row_family_forced != Kernel::Waveres)
+                return fail(TINY_BATCH_EUNSUPPORTED, "fma arithmetic for 16 < nx + nu <= 64 needs the state-on-chip wave kernel (N <= 50); beyond that it is the streaming MFMA kernel (variant 1)");
+            return plan_of(tb, v == VAR_AUTO ? VAR_ROW_EXACT : v, *tb->row_family_forced, out);
+        }
         if (v == VAR_AUTO)
         {
             if (!tb->row_dims_ok && !tb->generic_ok)
@@ -1059,11 +1070,21 @@ int run_step(TinyBatch *tb, int fn, int *converged_host, int *n_true)
 }
 
 // per-instance models: the 16-lane kernel's gain rows in the arithmetic the plan computes in, packed from the records when they changed (the
-// run-time-dimension kernel reads the records themselves)
+// run-time-dimension kernel reads the records themselves); the two wave kernels' tables likewise, at row width 64
+bool wave_family(Kernel k) { return k == Kernel::Wavestream || k == Kernel::Waveres; }
 int pack_models(TinyBatch *tb, const KernelPlan &pl)
 {
-    if (pl.kernel != Kernel::Rowlane) return 0;
     const int f = pl.exact ? 0 : 1;
+    if (wave_family(pl.kernel))
+    {
+        if (!tb->pm_wave_dirty[f]) return 0;
+        const size_t n = (size_t)tb->batch * pm_wave_floats(tb->nx, tb->nu);
+        if (!tb->pm_wave[f]) HIP_TRY(guarded_malloc((void **)&tb->pm_wave[f], n * sizeof(float)));
+        HIP_TRY(launch_models_pack_wave(tb->pm_src, tb->pm_wave[f], tb->batch, tb->nx, tb->nu, f, tb->stream));
+        tb->pm_wave_dirty[f] = false;
+        return 0;
+    }
+    if (pl.kernel != Kernel::Rowlane) return 0;
     if (!tb->pm_row_dirty[f]) return 0;
     const long long n = (long long)tb->batch * pm_row_floats(tb->nx, tb->nu);
     if (!tb->pm_row[f]) HIP_TRY(guarded_malloc((void **)&tb->pm_row[f], (size_t)n * sizeof(float)));
@@ -1077,6 +1098,7 @@ ModelParams model_params(const TinyBatch *tb, const KernelPlan &pl)
     ModelParams M;
     M.rho = tb->pm_rho;
     if (pl.kernel == Kernel::Generic) { M.mats = tb->pm_src; M.mats_stride = (unsigned)pm_gen_floats(tb->nx, tb->nu); }
+    else if (wave_family(pl.kernel)) { M.mats = tb->pm_wave[pl.exact ? 0 : 1]; M.mats_stride = (unsigned)pm_wave_floats(tb->nx, tb->nu); }
     else { M.mats = tb->pm_row[pl.exact ? 0 : 1]; M.mats_stride = (unsigned)pm_row_floats(tb->nx, tb->nu); }
     return M;
 }
@@ -1234,9 +1256,9 @@ hipError_t launch_kernel(const TinyBatch *tb, const KernelPlan &pl, RowParams &P
         return pl.pm ? launch_admm_rowlane_pm(nx, nu, N, pl.exact, P, model_params(tb, pl), tb->stream) : launch_admm_rowlane(nx, nu, N, pl.exact, tb->h16, P, tb->stream);
     case Kernel::Rowloop: return launch_admm_rowloop(nx, nu, pl.exact, tb->h16, P, tb->stream);
     case Kernel::Rowstream: return launch_admm_rowstream(nx, nu, pl.exact, tb->h16, P, tb->stream);
-    case Kernel::Wavestream: return launch_admm_wavestream(nx, nu, P, tb->stream);
+    case Kernel::Wavestream: return pl.pm ? launch_admm_wavestream_pm(nx, nu, P, model_params(tb, pl), tb->stream) : launch_admm_wavestream(nx, nu, P, tb->stream);
     case Kernel::Quadlane: return launch_admm_quadlane(N, pl.exact, tb->h16, P, tb->stream);
-    case Kernel::Waveres: return launch_admm_waveres(nx, nu, pl.exact, P, tb->stream);
+    case Kernel::Waveres: return pl.pm ? launch_admm_waveres_pm(nx, nu, pl.exact, P, model_params(tb, pl), tb->stream) : launch_admm_waveres(nx, nu, pl.exact, P, tb->stream);
     case Kernel::Tile48: return launch_admm_tile48(N, pl.exact, P, tb->stream);
     case Kernel::Tile16:
     {
@@ -1435,6 +1457,7 @@ void tiny_batch_destroy(TinyBatch *tb)
     (void)guarded_free(tb->res); (void)guarded_free(tb->status); (void)guarded_free(tb->iter); (void)guarded_free(tb->n_unsolved);
     (void)guarded_free(tb->opnd); (void)guarded_free(tb->qvec); (void)guarded_free(tb->gen_mats); (void)guarded_free(tb->mats_exact); (void)guarded_free(tb->mats_fast);
     (void)guarded_free(tb->pm_src); (void)guarded_free(tb->pm_rho); (void)guarded_free(tb->pm_row[0]); (void)guarded_free(tb->pm_row[1]);
+    (void)guarded_free(tb->pm_wave[0]); (void)guarded_free(tb->pm_wave[1]);
     (void)guarded_free(tb->plant_A); (void)guarded_free(tb->plant_B); (void)guarded_free(tb->plant_rows);
     for (float *p : tb->sim_stage) (void)guarded_free(p);
     (void)guarded_free(tb->dA); (void)guarded_free(tb->dB); (void)guarded_free(tb->x0buf); (void)guarded_free(tb->staging); (void)guarded_free(tb->conv_dev);
@@ -1502,7 +1525,7 @@ int tiny_batch_set_models_device(TinyBatch *tb, const float *d_rho, const float 
     if (!tb->pm_rho) HIP_TRY(guarded_malloc((void **)&tb->pm_rho, (size_t)tb->batch * sizeof(float)));
     HIP_TRY(launch_models_gather(d_rho, d_Kinf, d_Pinf, d_Quu_inv, d_AmBKt, d_Adyn, d_Bdyn, d_Q, tb->pm_src, tb->pm_rho, tb->batch, tb->nx, tb->nu, tb->stream));
     tb->pm = true;
-    tb->pm_row_dirty[0] = tb->pm_row_dirty[1] = true; // the packed rows follow the records
+    tb->pm_row_dirty[0] = tb->pm_row_dirty[1] = tb->pm_wave_dirty[0] = tb->pm_wave_dirty[1] = true; // the packed rows follow the records
     return 0;
 }
 
@@ -1556,13 +1579,14 @@ int tiny_batch_clear_models(TinyBatch *tb)
     TRY(set_device(tb));
     invalidate_graph(tb);
     HIP_TRY(hipStreamSynchronize(tb->stream)); // a launch still reading the records may be in flight
-    // the records and the packed rows are released (about 8 KB per quadrotor instance); a later set_models allocates them again
-    for (float **p : {&tb->pm_src, &tb->pm_rho, &tb->pm_row[0], &tb->pm_row[1]})
+    // the records and the packed rows are released (about 8 KB per quadrotor instance, 33 KB per wave table of the nx = 32 class); a later set_models
+    // allocates them again
+    for (float **p : {&tb->pm_src, &tb->pm_rho, &tb->pm_row[0], &tb->pm_row[1], &tb->pm_wave[0], &tb->pm_wave[1]})
     {
         (void)guarded_free(*p);
         *p = nullptr;
     }
-    tb->pm_row_dirty[0] = tb->pm_row_dirty[1] = true;
+    tb->pm_row_dirty[0] = tb->pm_row_dirty[1] = tb->pm_wave_dirty[0] = tb->pm_wave_dirty[1] = true;
     tb->pm = false;
     return 0;
 }
@@ -2235,10 +2259,10 @@ int mpc_run_sim(TinyBatch *tb, const char *who, int steps, int window_advance, c
     // (round 3: the signature is complete — rho, the shared / per-instance modes that set the strides, the bound flags and the
     // dispatch order are in it — so setters that only change buffer CONTENTS no longer drop the graph: `set_xref; mpc_run(k)`
     // in a loop replays one captured graph instead of re-capturing it every step)
-    char sig[680];
-    snprintf(sig, sizeof sig, "%d|%p|%p|%p|%p|%p|%p|%p|%d|%d|%d|%s|%d|%d|%g|%g|%d|%d|%p|%p|%p|%d|%p|%p|%p|%p|%d%d|%a|%d%d%d|%d%d|%d|%p|%p|%p|%d", tb->plant_mode, (void *)tb->plant_A,
+    char sig[720];
+    snprintf(sig, sizeof sig, "%d|%p|%p|%p|%p|%p|%p|%p|%p|%p|%d|%d|%d|%s|%d|%d|%g|%g|%d|%d|%p|%p|%p|%d|%p|%p|%p|%p|%d%d|%a|%d%d%d|%d%d|%d|%p|%p|%p|%d", tb->plant_mode, (void *)tb->plant_A,
              (void *)tb->plant_B, (const void *)d_w, (void *)d_x_traj, (void *)tb->pm_src, (void *)tb->pm_row[0],
-             (void *)tb->pm_row[1], steps, window_advance, tb->variant, kernel_name(tb, pl).c_str(), tb->max_iter,
+             (void *)tb->pm_row[1], (void *)tb->pm_wave[0], (void *)tb->pm_wave[1], steps, window_advance, tb->variant, kernel_name(tb, pl).c_str(), tb->max_iter,
              tb->check_termination, (double)tb->abs_pri_tol, (double)tb->abs_dua_tol, tb->xref_mode, tb->table_rows, (void *)tb->pair[0],
              (void *)tb->arr[0], (void *)tb->r_bounds, (int)tb->h16, (void *)tb->stream, (void *)d_u0_traj, (void *)tb->r_xref,
              (void *)tb->r_uref, (int)tb->en_uref, (int)tb->en_d2p, (double)tb->rho, (int)bounds_all_shared(tb),

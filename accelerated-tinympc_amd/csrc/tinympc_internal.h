@@ -144,7 +144,8 @@ __device__ __forceinline__ float box_project(float t, float lo, float hi, bool t
 
 // Per-instance models (tiny_batch_set_models): a kernel argument of its own beside RowParams / SolveParams, whose layouts stay as they are.
 //   mats: [batch][mats_stride] — the rowlane kernel: pack_gains' rows 0 .. 3nx + 2nu (M1, M2, M3, M45, Q, PT; no optional-term rows) of
-//         each instance, in the exact or the fma form; the run-time-dimension kernel: Kinf | Pinf | Quu_inv | AmBKt | Adyn | Bdyn | Q
+//         each instance, in the exact or the fma form; the two wave kernels: the same rows at row width 64 (pm_wave_floats);
+//         the run-time-dimension kernel: Kinf | Pinf | Quu_inv | AmBKt | Adyn | Bdyn | Q
 //   rho:  [batch]
 struct ModelParams
 {
@@ -169,6 +170,7 @@ struct SimParams
 __host__ __device__ inline int plant_row_floats(int nx, int nu) { return (nx + nu) * 16; }
 // floats of one instance's record in the two forms
 __host__ __device__ inline int pm_row_floats(int nx, int nu) { return (3 * nx + 2 * nu + 1) * 16; }
+__host__ __device__ inline int pm_wave_floats(int nx, int nu) { return (3 * nx + 2 * nu + 1) * WAVE; } // the wave kernels' form: the same rows at row width 64
 __host__ __device__ inline int pm_gen_floats(int nx, int nu) { return nu * nx + nx * nx + nu * nu + nx * nx + nx * nx + nx * nu + nx; }
 
 // batched fp64 Riccati (riccati_batch.hip): doubles of scratch per system, and the launch over systems [s0, min(s0 + n, count)) with scratch for n systems
@@ -237,6 +239,13 @@ hipError_t launch_admm_wavestream(int nx, int nu, const RowParams &P, hipStream_
 // the same classes with the loop-carried state on chip (admm_waveres.hip): N <= 50
 bool waveres_supported(int nx, int nu, int N);
 hipError_t launch_admm_waveres(int nx, int nu, bool exact, const RowParams &P, hipStream_t stream);
+// both wave kernels with per-instance models (admm_wave_pm.hip, admm_waveres_pm.hip): M.mats is one gain table per instance in the form the plan computes
+// in, M.mats_stride = pm_wave_floats(nx, nu); fp32 storage, shared or per-instance bounds, every reference kind, one solve per launch
+hipError_t launch_admm_wavestream_pm(int nx, int nu, const RowParams &P, const ModelParams &M, hipStream_t stream);
+hipError_t launch_admm_waveres_pm(int nx, int nu, bool exact, const RowParams &P, const ModelParams &M, hipStream_t stream);
+// ... and their tables from the handle's model records ([batch][pm_gen_floats] -> [batch][pm_wave_floats]; fast = 1: the fma form, which holds -K):
+// 14.6 KB per (16,4) instance, 33 KB per (32,16) instance and arithmetic form — 541 MB at 16 384 instances of the latter (admm_waveres_pm.hip)
+hipError_t launch_models_pack_wave(const float *recs, float *dst, int batch, int nx, int nu, int fast, hipStream_t stream);
 // nx = 32, nu = 16, N <= 50 with sixteen instances per workgroup on the matrix cores (admm_tile48.hip): exact and fma arithmetic
 bool tile48_supported(int nx, int nu, int N);
 hipError_t launch_admm_tile48(int N, bool exact, const RowParams &P, hipStream_t stream);

@@ -53,6 +53,22 @@ __device__ __forceinline__ RowResiduals wave_residuals(float pri, float dua, boo
     return now;
 }
 
+// The gain table and rho of the instance a wave solves.  PM = per-instance models (admm_wave_pm.hip, admm_waveres_pm.hip): the instance is the wave, so
+// its own table is a wave-uniform base address and its rho a wave-uniform value — two scalar loads, no per-lane addressing.  The offset is 64-bit before
+// it is scaled to bytes: a record of the nx = 32 class is 33 024 bytes, and 65 536 of them pass 2 GiB
+template <bool PM>
+__device__ __forceinline__ const float *wave_mats(const RowParams &P, [[maybe_unused]] const ModelParams &M, [[maybe_unused]] int inst)
+{
+    if constexpr (PM) return M.mats + (size_t)inst * M.mats_stride;
+    else return P.mats;
+}
+template <bool PM>
+__device__ __forceinline__ float wave_rho(const RowParams &P, [[maybe_unused]] const ModelParams &M, [[maybe_unused]] int inst)
+{
+    if constexpr (PM) return M.rho[inst];
+    else return P.rho;
+}
+
 template <int NX, int NU>
 struct WavePlans
 {

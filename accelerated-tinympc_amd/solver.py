@@ -274,7 +274,9 @@ class TinyBatchSolver:
     # -- per-instance models (tiny_batch_set_models) ----------------------------------------------
     def set_models(self, models: dict):
         """Every instance its own model: `models` holds rho [B] and Kinf, Pinf, Quu_inv, AmBKt, Adyn, Bdyn [B][rows][cols], Q [B][nx], the keys and
-        the logical orientation of set_cache / the prob dicts (Q as stored in work.Q)."""
+        the logical orientation of set_cache / the prob dicts (Q as stored in work.Q).  Served by rowlane<...,pm> where (nx, nu, N) has a 16-lane
+        instantiation and by generic<...,pm> otherwise; for 16 < nx + nu <= 64, set_row_kernel(7) / (6) moves such a handle to waveres<...,pm>
+        (N <= 50, exact or fma) / wavestream<...,pm> (any N, exact), which read one packed gain table per instance."""
         B = self.B
         rho = _f32(np.asarray(models["rho"]).reshape(B))
         arrs = [_colmajor_batch(models[k]) for k in ("Kinf", "Pinf", "Quu_inv", "AmBKt", "Adyn", "Bdyn")]
@@ -554,7 +556,8 @@ class TinyBatchSolver:
         """0 auto, 1 rowlane (unrolled), 2 rowloop (rolled, N <= 64), 3 rowstream (state in HBM), 4 quadlane (nx=4, nu=1),
         5 tile16 (16 instances per wave, products on the matrix cores; nx=12, nu=4, instantiated N; the auto choice for launches
         of >= 32768 instances), 6 wavestream / 7 waveres (one wavefront per instance, 16 < nx + nu <= 64), 8 tile48 (nx = 32, nu = 16, N <= 50: sixteen
-        instances per workgroup on the matrix cores; automatic for 2049 ... 4096 and from 6145 instances on)."""
+        instances per workgroup on the matrix cores; automatic for 2049 ... 4096 and from 6145 instances on).  With per-instance models (set_models)
+        6 and 7 select that family's ",pm" kernels; with 0 such a handle stays on generic<...,pm>."""
         self._check(self.lib.tiny_batch_set_row_kernel(self._h, family))
 
     def set_dispatch(self, mode: int):

@@ -270,6 +270,9 @@ extern "C"
      * N), 7 = waveres (state in registers/LDS, N <= 50; the auto choice up to 2 048 and for 4 097 ... 6 144 instances), 8 = tile48 (nx = 32, nu = 16,
      * N <= 50, fp32 storage: sixteen instances per workgroup as the columns of 16x16 MFMA tiles, duals in LDS;
      * the auto choice for 2 049 ... 4 096 and from 6 145 instances on (rounds of the launch)).  All of them compute identical results.
+     * With per-instance models (tiny_batch_set_models) 6 and 7 are a request, not only a preference: variants 0 and 2 then run that family's ",pm"
+     * instantiations in exact arithmetic and variant 3 with family 7 runs "waveres<...,fast,pm>" (variant 3 with family 6 is refused, as without
+     * models); with 0 such a handle stays on "generic<...,pm>", and 8 changes nothing there.
      * Zero bounds: the two matrix-core kernels (5, 8) project with v_med3_f32, which breaks a tie between zeros of opposite sign the other way than the
      * reference's u_max.cwiseMin(u_min.cwiseMax(t)) does (t = +0 on a lower bound of -0, t = -0 on an upper bound of +0).  In exact arithmetic a handle
      * whose stored bounds hold such a pair — a lower bound of -0 under a positive upper bound, an upper bound of +0 over a lower bound that is negative
@@ -373,8 +376,13 @@ extern "C"
      * replaces the batch-shared cache / dynamics until tiny_batch_clear_models(), and drops a captured closed-loop graph.  Settings stay per batch.
      * Kernels: the unrolled 16-lane kernel where (nx, nu, N) is instantiated (exact or fma arithmetic, shared or per-instance bounds, any
      * reference, the on-chip closed loop; kernel name "rowlane<nx,nu,N,exact,pm>"), the run-time-dimension exact kernel otherwise
-     * ("generic<nx,nu,exact,pm>").  Not available, TINY_BATCH_EUNSUPPORTED with a message: fp16 storage, the optional terms, a forced kernel
-     * that keeps one gain table per launch (streaming MFMA, tile16, quadlane, rowloop, rowstream, the wave kernels, tile48), the six
+     * ("generic<nx,nu,exact,pm>").  On request, for the classes with 16 < nx + nu <= 64: the two wave kernels — with
+     * tiny_batch_set_row_kernel(tb, 7) "waveres<nx,nu,exact,pm>" / "waveres<nx,nu,fast,pm>" (N <= 50), with (tb, 6) "wavestream<nx,nu,exact,pm>"
+     * (any N) — serve shared or per-instance bounds, every reference kind and the closed-loop calls (solve + plant kernel per step, replayed
+     * from one graph); they read one gain table per instance and arithmetic form, (3nx + 2nu + 1) * 256 bytes (33 KB for nx = 32, nu = 16),
+     * packed on the device when a launch first needs it.  Without that request these classes run on the run-time-dimension kernel, which is
+     * far slower.  Not available, TINY_BATCH_EUNSUPPORTED with a message: fp16 storage, the optional terms, a forced kernel
+     * that keeps one gain table per launch (streaming MFMA, tile16, quadlane, rowloop, rowstream, tile48), the six
      * single-function step calls.  The longest-first predictor (tiny_batch_set_dispatch mode 1) reads shared gains: such launches keep index
      * order, history order (mode 2) applies; tiny_batch_dispatch_applied() says which. */
     int tiny_batch_set_models(TinyBatch *tb, const float *rho /*[B]*/, const float *Kinf /*[B][nu*nx]*/, const float *Pinf /*[B][nx*nx]*/,
