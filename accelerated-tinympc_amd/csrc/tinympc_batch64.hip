@@ -3,9 +3,8 @@
 //
 // Host code only.  Every kernel lives in a translation unit of its own (admm_f64_thread.hip, admm_f64_rows.hip, admm_f64_rowsim.hip,
 // admm_f64_plant.hip; admm_f64_rows_pm.hip, admm_f64_rowsim_pm.hip, admm_f64_thread_pm.hip: per-instance models; batch64_helpers.hip: the three
-// that move arrays between the host's layout and the workspace's) and is reached through
-// the typed launchers of f64_internal.h, so nothing in this file — not the order of its functions, not a name in it — has a bearing on
-// device code.
+// that move arrays between the host's layout and the workspace's) and is reached through the typed launchers of f64_internal.h, so nothing in this
+// file — not the order of its functions, not a name in it — has a bearing on device code.
 //
 // Every per-instance array is stored instance-minor — element (step, row) of instance b at ((step * dim + row) * Bpad + b).  Results are
 // bitwise equal to the compiled reference (tests/test_parity_gpu.py: golden vectors of the as-shipped fp64 N = 10 hovering run).
@@ -42,6 +41,31 @@ int fail64(int code, const char *fmt, ...)
     } while (0)
 #define CHECK64(c, ...) \
     if (!(c)) return fail64(TINY_BATCH_EINVAL, __VA_ARGS__)
+// a negative return is an error, already worded; 1 (some instance unsolved) is a result
+#define TRY64(expr)              \
+    do                           \
+    {                            \
+        const int rc_ = (expr);  \
+        if (rc_ < 0) return rc_; \
+    } while (0)
+
+// a temporary device buffer: freed when it goes out of scope, unless release() has handed it on
+template <typename T>
+struct Scratch64
+{
+    T *p = nullptr;
+    Scratch64() = default;
+    Scratch64(const Scratch64 &) = delete;
+    Scratch64 &operator=(const Scratch64 &) = delete;
+    ~Scratch64() { (void)hipFree(p); }
+    hipError_t alloc(size_t n) { return hipMalloc((void **)&p, n * sizeof(T)); }
+    hipError_t upload(const T *src, size_t n)
+    {
+        const hipError_t e = alloc(n);
+        return e != hipSuccess ? e : hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice);
+    }
+    T *release() { T *q = p; p = nullptr; return q; }
+};
 
 bool xfam(int id) { return id == TINY_ARR_X || id == TINY_ARR_Q || id == TINY_ARR_P || id == TINY_ARR_V || id == TINY_ARR_VNEW || id == TINY_ARR_G; }
 
@@ -157,13 +181,76 @@ int gather_window64(TinyBatch64 *tb)
     tb->xwin_valid = true;
     return 0;
 }
-// gathered_ref = false: the launch reads a window reference from the table itself (the on-chip closed loop)
-int prepare64(TinyBatch64 *tb, Params64 &P, bool gathered_ref = true)
+size_t rec_len(const TinyBatch64 *tb) { return mat_off(tb, 6) + tb->nx; }
+
+// ---- what a call launches: resolved ONCE per call by resolve_plan64() and read by everything that names, prepares or launches (DESIGN.md 5.6 has the
+// table).  No other function looks at kernel_choice, the lists of instantiated classes, the capacities, max_iter or TINYMPC_F64_LOOP.
+enum class Family64 { Thread, Rows };         // one thread per instance (state in HBM, any N); sixteen lanes per instance (state in registers)
+enum class Body64 { Unrolled, Cap32, Cap64 }; // Rows only, which instantiation of admm_f64_rows_kernel: N compiled in; any N <= 32; any N <= 64
+enum class Loop64 { None, Sequence, OnChip }; // one solve; a run as launches per step; a run in one launch
+struct Plan64
 {
+    Family64 family = Family64::Thread;
+    Body64 body = Body64::Unrolled;
+    bool pm = false; // per-instance models: the ",pm" instantiations
+    Loop64 loop = Loop64::None;
+    bool sim = false; // the plant step is the simulated one: a plant is set, the call passes w or asks for x_traj — or pm: the simulated kernels are the
+                      // ones that take a matrix pair per instance, here the instance's own model.  Any other call enqueues what it always has
+};
+struct Call64
+{
+    enum Kind { StepFn, Solve, Run } kind; // one of the six step functions; one solve (with or without a plant step behind it); a closed-loop run
+    bool w = false, x_traj = false;        // the caller passed a disturbance / asks for the state trajectory
+};
+
+// Reads the handle and changes nothing.  The one refusal a resolution can meet is the step functions' under models: tiny_batch64_select_kernel refuses
+// the sixteen lanes where the class has none, so a stored choice can always be served.
+int resolve_plan64(const TinyBatch64 *tb, const Call64 &call, Plan64 *out)
+{
+    if (call.kind == Call64::StepFn && tb->pm)
+        return fail64(TINY_BATCH_EUNSUPPORTED, "the six single-function step kernels read one shared model: not available with per-instance models (tiny_batch64_clear_models())");
+    Plan64 p;
+    const bool rows = tb->kernel_choice == 2 || (tb->kernel_choice == 0 && rows_supported(tb->nx, tb->nu, tb->N));
+    if (rows && call.kind != Call64::StepFn) // (the step kernels are thread-per-instance ones)
+    {
+        p.family = Family64::Rows;
+        p.body = rows_unrolled(tb->nx, tb->nu, tb->N) ? Body64::Unrolled : tb->N <= 32 ? Body64::Cap32 : Body64::Cap64;
+    }
+    p.pm = tb->pm;
+    p.sim = tb->plant_mode != 0 || call.w || call.x_traj || tb->pm;
+    if (call.kind == Call64::Run)
+    {
+        // on chip where the sixteen-lane kernel holds [p ; d] in registers (the unrolled instantiations and the capacity-32 body).  max_iter <= 0 (tiny_solve
+        // sets status and iter only) is left to the launch sequence.  Developer aid, read on every resolution: TINYMPC_F64_LOOP=sequence sends every run
+        // through the launch sequence (tools/closed_loop64_time.py times the two against each other over the same solve kernel, in one process).
+        const char *force = getenv("TINYMPC_F64_LOOP");
+        const bool on_chip = p.family == Family64::Rows && p.body != Body64::Cap64 && tb->max_iter >= 1 && !(force && !strcmp(force, "sequence"));
+        p.loop = on_chip ? Loop64::OnChip : Loop64::Sequence;
+    }
+    *out = p;
+    return 0;
+}
+
+// every name, printed from the plan.  ",sim" says that a plant is set and nothing else: a run that passes w / x_traj without one, and every run with
+// models, takes the simulated family under the name ",mpc" (only the call knows the former; tests assert the latter)
+const char *name_of(const TinyBatch64 *tb, const Plan64 &p, char (&nm)[64])
+{
+    char body[16] = "";
+    if (p.family == Family64::Rows && p.body == Body64::Unrolled) snprintf(body, sizeof body, ",%d", tb->N);
+    else if (p.family == Family64::Rows) snprintf(body, sizeof body, ",n<=%d", p.body == Body64::Cap32 ? 32 : 64);
+    const char *const loop = p.loop != Loop64::OnChip ? "" : tb->plant_mode ? ",sim" : ",mpc";
+    snprintf(nm, sizeof nm, "%s<%d,%d%s%s%s>", p.family == Family64::Rows ? "rows64" : "thread64", tb->nx, tb->nu, body, loop, p.pm ? ",pm" : "");
+    return nm;
+}
+
+// How every call begins: its plan and its launch arguments.  The on-chip closed loop reads a window reference from the table itself; every other launch
+// reads it gathered
+int prepare64(TinyBatch64 *tb, const Call64 &call, Plan64 &plan, Params64 &P)
+{
+    TRY64(resolve_plan64(tb, call, &plan));
     if (!(tb->pm || (tb->have_cache && tb->have_dyn)) || !tb->have_settings)
         return fail64(TINY_BATCH_ENOTREADY, "set_cache, set_dynamics (or set_models) and set_settings must be called first");
-    if (tb->in_stride[1] != tb->in_stride[2] || tb->in_stride[3] != tb->in_stride[4])
-        return fail64(TINY_BATCH_EINVAL, "min and max bounds must both be shared or both be per-instance");
+    CHECK64(tb->in_stride[1] == tb->in_stride[2] && tb->in_stride[3] == tb->in_stride[4], "min and max bounds must both be shared or both be per-instance");
     HIP64(hipSetDevice(tb->device));
     if (tb->mats_dirty)
     {
@@ -181,61 +268,82 @@ int prepare64(TinyBatch64 *tb, Params64 &P, bool gathered_ref = true)
     P.xref = tb->in[0]; P.xmin = tb->in[1]; P.xmax = tb->in[2]; P.umin = tb->in[3]; P.umax = tb->in[4];
     P.xref_stride = tb->in_stride[0]; P.xb_stride = tb->in_stride[1]; P.ub_stride = tb->in_stride[3];
     P.mats = tb->mats; P.res = tb->res; P.status = tb->status; P.iter = tb->iter; P.n_unsolved = tb->n_unsolved;
-    if (tb->table_rows > 0 && gathered_ref)
+    if (tb->table_rows > 0 && plan.loop != Loop64::OnChip)
     {
-        const int rc = gather_window64(tb);
-        if (rc < 0) return rc;
+        TRY64(gather_window64(tb));
         P.xref = tb->xwin; P.xref_stride = tb->bpad;
     }
     return 0;
 }
 
-size_t rec_len(const TinyBatch64 *tb) { return mat_off(tb, 6) + tb->nx; }
-Models64 models_of(const TinyBatch64 *tb) { return Models64{tb->pm_rec, rec_len(tb), tb->pm_rho}; }
-
 // one of the six step functions over the whole batch
 int run_step64(TinyBatch64 *tb, int fn, int *conv_dev)
 {
     CHECK64(tb, "NULL handle");
-    if (tb->pm)
-        return fail64(TINY_BATCH_EUNSUPPORTED, "the six single-function step kernels read one shared model: not available with per-instance models (tiny_batch64_clear_models())");
+    Plan64 plan;
     Params64 P;
-    int rc = prepare64(tb, P);
-    if (rc < 0) return rc;
+    TRY64(prepare64(tb, Call64{Call64::StepFn}, plan, P));
     HIP64(launch_f64_step(fn, tb->nx, tb->nu, P, conv_dev));
     HIP64(hipDeviceSynchronize());
     return 0;
 }
 
-bool rows_chosen(const TinyBatch64 *tb) { return tb->kernel_choice == 2 || (tb->kernel_choice == 0 && rows_supported(tb->nx, tb->nu, tb->N)); }
-// whether a closed-loop run takes the on-chip loop: the sixteen-lane kernel with [p ; d] in registers (the unrolled instantiations and the capacity-32
-// body).  max_iter <= 0 (tiny_solve sets status and iter only) is left to the launch sequence.  Developer aid: TINYMPC_F64_LOOP=sequence sends
-// every run through the launch sequence (tools/closed_loop64_time.py times the two against each other over the same solve kernel).
-bool onchip64(const TinyBatch64 *tb)
+// The solve kernel of a plan, on the null stream: the one place a solve kernel is launched.  L: the loop arguments of a run on chip (L->mpc_steps solves);
+// d_w / d_x: such a run's device copies of w and x_traj or NULL
+int launch_solve64(TinyBatch64 *tb, const Plan64 &plan, const Params64 &P, const Mpc64 *L = nullptr, const double *d_w = nullptr, double *d_x = nullptr)
 {
-    const char *force = getenv("TINYMPC_F64_LOOP");
-    if (force && !strcmp(force, "sequence")) return false;
-    return rows_chosen(tb) && rows_supported(tb->nx, tb->nu, tb->N) && (rows_unrolled(tb->nx, tb->nu, tb->N) || tb->N <= 32) && tb->max_iter >= 1;
-}
-// the solve kernel the handle selects, on the null stream; mpc: the on-chip closed-loop instantiation (L->mpc_steps solves)
-int launch_solve64(TinyBatch64 *tb, const Params64 &P, const Mpc64 *L = nullptr)
-{
-    const bool mpc = L != nullptr;
-    const bool rows = rows_chosen(tb);
-    if (rows && !rows_supported(tb->nx, tb->nu, tb->N))
-        return fail64(TINY_BATCH_EUNSUPPORTED, "the sixteen-lane fp64 kernel has no instantiation for nx=%d nu=%d N=%d", tb->nx, tb->nu, tb->N);
-    if (mpc && !rows) return fail64(TINY_BATCH_EUNSUPPORTED, "the thread-per-instance kernel has no on-chip closed loop");
-    if (mpc && !rows_unrolled(tb->nx, tb->nu, tb->N) && tb->N > 32) return fail64(TINY_BATCH_EUNSUPPORTED, "the capacity-64 body has no on-chip closed loop");
-    if (tb->pm)
+    const int nx = tb->nx, nu = tb->nu, N = tb->N;
+    const bool rows = plan.family == Family64::Rows;
+    const Models64 M{tb->pm_rec, rec_len(tb), tb->pm_rho};
+    // a run on chip takes the simulated family with models (whose plant is at least every instance's own) and where the kernel's plant step, which one
+    // step never reaches, is to be a simulated one; the MPC instantiation serves the rest
+    if (plan.loop == Loop64::OnChip && (plan.pm || (plan.sim && L->mpc_steps > 1)))
     {
-        if (mpc) return fail64(TINY_BATCH_EINVAL, "per-instance models: the on-chip closed loop is launched by the run itself");
-        if (rows) HIP64(launch_f64_rows_pm(tb->nx, tb->nu, tb->N, P, models_of(tb)));
-        else HIP64(launch_f64_thread_pm(tb->nx, tb->nu, P, models_of(tb)));
-        return 0;
+        const Sim64 S{tb->plant_mode ? tb->plant_rows : nullptr, tb->plant_mode == 2 ? (size_t)(nx + nu) * 16 : 0, d_w, d_x};
+        if (plan.pm) HIP64(launch_rows64_loop_pm(nx, nu, N, P, *L, S, M));
+        else HIP64(launch_rows64_sim(nx, nu, N, P, tb->row_gains, *L, S));
     }
-    if (rows) HIP64(launch_f64_rows(tb->nx, tb->nu, tb->N, P, tb->row_gains, L));
-    else HIP64(launch_f64_thread(tb->nx, tb->nu, P));
+    else if (plan.pm)
+    {
+        if (rows) HIP64(launch_f64_rows_pm(nx, nu, N, P, M));
+        else HIP64(launch_f64_thread_pm(nx, nu, P, M));
+    }
+    else if (rows) HIP64(launch_f64_rows(nx, nu, N, P, tb->row_gains, plan.loop == Loop64::OnChip ? L : nullptr));
+    else HIP64(launch_f64_thread(nx, nu, P));
     return 0;
+}
+
+// The plant step behind a solve of a plan: the one place a plant kernel is launched.  d_w / d_x / d_u0: this step's device rows of w, x_traj and u0_traj or
+// NULL; start: the window starts to slide by adv, or NULL.  Simulated: against the handle's plant, else the model's matrices, with models every
+// instance's own, inside its record.  Else the model's: behind a lone solve the kernel that records and slides nothing, in a run the one that does
+int enqueue_plant64(TinyBatch64 *tb, const Plan64 &plan, const double *d_w, double *d_x, double *d_u0, int *start, int adv)
+{
+    double *const X = tb->arr[TINY_ARR_X];
+    const double *const U = tb->arr[TINY_ARR_U];
+    if (plan.sim)
+    {
+        const bool per = tb->plant_mode == 2, own = tb->pm && !tb->plant_mode;
+        const double *const model = own ? tb->pm_rec : tb->mats;
+        const double *A = tb->plant_mode ? tb->plant_A : model + mat_off(tb, 4), *Bm = tb->plant_mode ? tb->plant_B : model + mat_off(tb, 5);
+        const PlantSim64 a{X, U, A, Bm, own ? rec_len(tb) : per ? (size_t)tb->nx * tb->nx : 0, own ? rec_len(tb) : per ? (size_t)tb->nx * tb->nu : 0,
+                           tb->batch, tb->bpad, d_w, d_x, d_u0, start, adv};
+        HIP64(launch_plant64_sim(tb->nx, tb->nu, a));
+    }
+    else if (plan.loop == Loop64::None) HIP64(launch_plant64(tb->nx, tb->nu, X, U, tb->mats, tb->batch, tb->bpad)); // quadrotor_hovering.cpp:110-111
+    else HIP64(launch_plant64_run(tb->nx, tb->nu, X, U, tb->mats, tb->batch, tb->bpad, d_u0, start, adv));
+    return 0;
+}
+
+// tiny_solve over the batch: 1 where some instance is left unsolved
+int solve64(TinyBatch64 *tb, const Call64 &call, Plan64 &plan)
+{
+    Params64 P;
+    TRY64(prepare64(tb, call, plan, P));
+    HIP64(hipMemset(tb->n_unsolved, 0, sizeof(int)));
+    TRY64(launch_solve64(tb, plan, P));
+    int n = 0;
+    HIP64(hipMemcpy(&n, tb->n_unsolved, sizeof(int), hipMemcpyDeviceToHost));
+    return n > 0 ? 1 : 0;
 }
 
 // a device buffer kept on the handle between calls: re-allocated only when it has to grow
@@ -245,17 +353,6 @@ int grow64(double **buf, size_t *cap, size_t need)
     (void)hipFree(*buf); *buf = nullptr; *cap = 0;
     HIP64(hipMalloc((void **)buf, need * sizeof(double)));
     *cap = need;
-    return 0;
-}
-// The plant step of one MPC step against the handle's plant (the model's matrices without one): d_w / d_x / d_u0 are this step's device rows or NULL
-int enqueue_plant_sim64(TinyBatch64 *tb, const double *d_w, double *d_x, double *d_u0, int *start, int adv)
-{
-    const bool per = tb->plant_mode == 2, own = tb->pm && !tb->plant_mode; // own: every instance's Adyn / Bdyn, inside its record
-    const double *const model = own ? tb->pm_rec : tb->mats;
-    const double *A = tb->plant_mode ? tb->plant_A : model + mat_off(tb, 4), *Bm = tb->plant_mode ? tb->plant_B : model + mat_off(tb, 5);
-    const PlantSim64 a{tb->arr[TINY_ARR_X], tb->arr[TINY_ARR_U], A, Bm, own ? rec_len(tb) : per ? (size_t)tb->nx * tb->nx : 0,
-                       own ? rec_len(tb) : per ? (size_t)tb->nx * tb->nu : 0, tb->batch, tb->bpad, d_w, d_x, d_u0, start, adv};
-    HIP64(launch_plant64_sim(tb->nx, tb->nu, a));
     return 0;
 }
 } // namespace
@@ -388,54 +485,35 @@ int tiny_batch64_termination_condition(TinyBatch64 *tb, int *converged)
 {
     CHECK64(tb && converged, "NULL argument");
     HIP64(hipSetDevice(tb->device));
-    int *dev = nullptr;
-    HIP64(hipMalloc((void **)&dev, (size_t)tb->bpad * sizeof(int)));
-    int rc = run_step64(tb, F64_TERMINATION_CONDITION, dev);
-    if (rc >= 0 && hipMemcpy(converged, dev, (size_t)tb->batch * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
-        rc = fail64(TINY_BATCH_EHIP, "copying the termination flags back failed");
-    (void)hipFree(dev);
-    return rc;
+    Scratch64<int> dev;
+    HIP64(dev.alloc(tb->bpad));
+    TRY64(run_step64(tb, F64_TERMINATION_CONDITION, dev.p));
+    HIP64(hipMemcpy(converged, dev.p, (size_t)tb->batch * sizeof(int), hipMemcpyDeviceToHost));
+    return 0;
 }
 
 int tiny_batch64_solve(TinyBatch64 *tb)
 {
     CHECK64(tb, "NULL handle");
-    Params64 P;
-    {
-        const int rc = prepare64(tb, P);
-        if (rc < 0) return rc;
-    }
-    HIP64(hipMemset(tb->n_unsolved, 0, sizeof(int)));
-    {
-        const int rc = launch_solve64(tb, P);
-        if (rc < 0) return rc;
-    }
-    int n = 0;
-    HIP64(hipMemcpy(&n, tb->n_unsolved, sizeof(int), hipMemcpyDeviceToHost));
-    return n > 0 ? 1 : 0;
+    Plan64 plan;
+    return solve64(tb, Call64{Call64::Solve}, plan);
 }
 
 // tiny_batch64_mpc_step / _mpc_step_sim: with no plant and no disturbance the launches tiny_batch64_mpc_step has always made
 static int mpc_step64(TinyBatch64 *tb, const double *w)
 {
     CHECK64(tb, "NULL handle");
-    int rc = tiny_batch64_reset_dual_variables(tb); // quadrotor_hovering.cpp:100-101
+    TRY64(tiny_batch64_reset_dual_variables(tb)); // quadrotor_hovering.cpp:100-101
+    Plan64 plan;
+    const int rc = solve64(tb, Call64{Call64::Solve, w != nullptr}, plan); // :104
     if (rc < 0) return rc;
-    rc = tiny_batch64_solve(tb);                    // :104
-    if (rc < 0) return rc;
-    if (tb->plant_mode || w || tb->pm) // (per-instance models: the plant kernel that takes a matrix pair per instance)
+    if (w)
     {
         const size_t row = (size_t)tb->batch * tb->nx;
-        if (w)
-        {
-            const int rg = grow64(&tb->sim_w, &tb->sim_w_cap, row);
-            if (rg < 0) return rg;
-            HIP64(hipMemcpy(tb->sim_w, w, row * sizeof(double), hipMemcpyHostToDevice));
-        }
-        const int rp = enqueue_plant_sim64(tb, w ? tb->sim_w : nullptr, nullptr, nullptr, nullptr, 0);
-        return rp < 0 ? rp : rc;
+        TRY64(grow64(&tb->sim_w, &tb->sim_w_cap, row));
+        HIP64(hipMemcpy(tb->sim_w, w, row * sizeof(double), hipMemcpyHostToDevice));
     }
-    HIP64(launch_plant64(tb->nx, tb->nu, tb->arr[TINY_ARR_X], tb->arr[TINY_ARR_U], tb->mats, tb->batch, tb->bpad)); // :110-111
+    TRY64(enqueue_plant64(tb, plan, w ? tb->sim_w : nullptr, nullptr, nullptr, nullptr, 0));
     return rc;
 }
 int tiny_batch64_mpc_step(TinyBatch64 *tb) { return mpc_step64(tb, nullptr); }
@@ -447,11 +525,7 @@ int tiny_batch64_clear_plant(TinyBatch64 *tb)
     if (!tb->plant_mode) return 0;
     HIP64(hipSetDevice(tb->device));
     HIP64(hipDeviceSynchronize()); // a plant kernel still reading the matrices may be in flight
-    for (double **p : {&tb->plant_A, &tb->plant_B, &tb->plant_rows})
-    {
-        (void)hipFree(*p);
-        *p = nullptr;
-    }
+    for (double **p : {&tb->plant_A, &tb->plant_B, &tb->plant_rows}) { (void)hipFree(*p); *p = nullptr; }
     tb->plant_mode = 0;
     return 0;
 }
@@ -460,10 +534,7 @@ int tiny_batch64_set_plant(TinyBatch64 *tb, const double *A, const double *B, in
 {
     CHECK64(tb && A && B, "NULL argument");
     HIP64(hipSetDevice(tb->device));
-    {
-        const int rc = tiny_batch64_clear_plant(tb); // releases the previous copies
-        if (rc < 0) return rc;
-    }
+    TRY64(tiny_batch64_clear_plant(tb)); // releases the previous copies
     const size_t nx = tb->nx, nu = tb->nu, cnt = shared ? 1 : (size_t)tb->batch, rl = (nx + nu) * 16;
     // the sixteen-lane kernel's form: entry (k, r) of [A | B] at k * 16 + r, lane r of a row reads 128 contiguous bytes per column with its row
     std::vector<double> packed;
@@ -477,17 +548,14 @@ int tiny_batch64_set_plant(TinyBatch64 *tb, const double *A, const double *B, in
                 for (size_t m = 0; m < nu; m++) packed[c * rl + (nx + m) * 16 + r] = B[c * nx * nu + m * nx + r];
             }
     }
-    int rc = 0;
-    auto up = [&](double **dst, const double *src, size_t n) {
-        if (rc == 0 && hipMalloc((void **)dst, n * sizeof(double)) != hipSuccess) rc = fail64(TINY_BATCH_EHIP, "tiny_batch64_set_plant: device allocation failed");
-        if (rc == 0 && hipMemcpy(*dst, src, n * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) rc = fail64(TINY_BATCH_EHIP, "tiny_batch64_set_plant: hipMemcpy failed");
-    };
-    up(&tb->plant_A, A, cnt * nx * nx);
-    up(&tb->plant_B, B, cnt * nx * nu);
-    if (!packed.empty()) up(&tb->plant_rows, packed.data(), packed.size());
+    // the handle takes the copies once all of them stand: a failure leaves it without a plant
+    Scratch64<double> dA, dB, dRows;
+    HIP64(dA.upload(A, cnt * nx * nx));
+    HIP64(dB.upload(B, cnt * nx * nu));
+    if (!packed.empty()) HIP64(dRows.upload(packed.data(), packed.size()));
+    tb->plant_A = dA.release(); tb->plant_B = dB.release(); tb->plant_rows = dRows.release();
     tb->plant_mode = shared ? 1 : 2;
-    if (rc) (void)tiny_batch64_clear_plant(tb);
-    return rc;
+    return 0;
 }
 
 int tiny_batch64_plant_mode(TinyBatch64 *tb)
@@ -525,21 +593,19 @@ int tiny_batch64_set_models(TinyBatch64 *tb, const double *rho, const double *Ki
     const size_t sz[8] = {B, B * nu * nx, B * nx * nx, B * nu * nu, B * nx * nx, B * nx * nx, B * nx * nu, B * nx};
     size_t total = 0;
     for (size_t z : sz) total += z;
-    double *buf = nullptr;
-    HIP64(hipMalloc((void **)&buf, total * sizeof(double)));
+    Scratch64<double> buf;
+    HIP64(buf.alloc(total));
     const double *d[8];
-    int rc = 0;
     size_t o = 0;
     for (int k = 0; k < 8; k++)
     {
-        if (rc == 0 && hipMemcpy(buf + o, src[k], sz[k] * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) rc = fail64(TINY_BATCH_EHIP, "tiny_batch64_set_models: hipMemcpy failed");
-        d[k] = buf + o;
+        HIP64(hipMemcpy(buf.p + o, src[k], sz[k] * sizeof(double), hipMemcpyHostToDevice));
+        d[k] = buf.p + o;
         o += sz[k];
     }
-    if (rc == 0) rc = install_models64(tb, d, 0);
-    if (hipDeviceSynchronize() != hipSuccess && rc == 0) rc = fail64(TINY_BATCH_EHIP, "tiny_batch64_set_models: hipDeviceSynchronize failed");
-    (void)hipFree(buf);
-    return rc;
+    TRY64(install_models64(tb, d, 0));
+    HIP64(hipDeviceSynchronize()); // the gather has read the buffer
+    return 0;
 }
 
 int tiny_batch64_clear_models(TinyBatch64 *tb)
@@ -548,11 +614,7 @@ int tiny_batch64_clear_models(TinyBatch64 *tb)
     if (!tb->pm) return 0;
     HIP64(hipSetDevice(tb->device));
     HIP64(hipDeviceSynchronize()); // a launch still reading the records may be in flight
-    for (double **p : {&tb->pm_rec, &tb->pm_rho})
-    {
-        (void)hipFree(*p);
-        *p = nullptr;
-    }
+    for (double **p : {&tb->pm_rec, &tb->pm_rho}) { (void)hipFree(*p); *p = nullptr; }
     tb->pm = false;
     return 0;
 }
@@ -573,33 +635,23 @@ int tiny_batch64_set_systems(TinyBatch64 *tb, const double *A, const double *B, 
     const double *const in[5] = {A, B, Q, R, rho};
     size_t nd = 0;
     for (size_t z : sz) nd += z;
-    double *d = nullptr;
-    int *it = nullptr;
-    int rc = 0;
-    if (hipMalloc((void **)&d, nd * sizeof(double)) != hipSuccess || hipMalloc((void **)&it, Bn * sizeof(int)) != hipSuccess)
-        rc = fail64(TINY_BATCH_EHIP, "tiny_batch64_set_systems: allocation failed");
+    Scratch64<double> d;
+    Scratch64<int> it;
+    HIP64(d.alloc(nd));
+    HIP64(it.alloc(Bn));
     double *dp[9];
     size_t o = 0;
-    for (int k = 0; k < 9; k++) { dp[k] = d + o; o += sz[k]; }
-    for (int k = 0; k < 5 && rc == 0; k++)
-        if (hipMemcpy(dp[k], in[k], sz[k] * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) rc = fail64(TINY_BATCH_EHIP, "tiny_batch64_set_systems: hipMemcpy failed");
-    int nfail = 0;
-    if (rc == 0)
-    {
-        nfail = tiny_batch_riccati_device(tb->nx, tb->nu, tb->batch, dp[0], dp[1], dp[2], dp[3], dp[4], dp[5], dp[6], dp[7], dp[8], nullptr, it, nullptr);
-        if (nfail < 0) rc = fail64(nfail, "tiny_batch64_set_systems: %s", tiny_batch_last_error());
-    }
-    if (rc == 0 && iters && hipMemcpy(iters, it, Bn * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) rc = fail64(TINY_BATCH_EHIP, "tiny_batch64_set_systems: hipMemcpy failed");
-    if (rc == 0 && nfail > 0)
-        rc = fail64(TINY_BATCH_EINVAL, "tiny_batch64_set_systems: the Riccati recursion is singular for %d of %zu systems (iters = -1); models unchanged", nfail, Bn);
-    if (rc == 0)
-    {
-        const double *const m[8] = {dp[4], dp[5], dp[6], dp[7], dp[8], dp[0], dp[1], dp[2]}; // rho, the cache, Adyn = A, Bdyn = B, Q (+ rho in the gather)
-        rc = install_models64(tb, m, 1);
-    }
-    if (hipDeviceSynchronize() != hipSuccess && rc == 0) rc = fail64(TINY_BATCH_EHIP, "tiny_batch64_set_systems: hipDeviceSynchronize failed");
-    (void)hipFree(d); (void)hipFree(it);
-    return rc;
+    for (int k = 0; k < 9; k++) { dp[k] = d.p + o; o += sz[k]; }
+    for (int k = 0; k < 5; k++) HIP64(hipMemcpy(dp[k], in[k], sz[k] * sizeof(double), hipMemcpyHostToDevice));
+    const int nfail = tiny_batch_riccati_device(tb->nx, tb->nu, tb->batch, dp[0], dp[1], dp[2], dp[3], dp[4], dp[5], dp[6], dp[7], dp[8], nullptr, it.p, nullptr);
+    if (nfail < 0) return fail64(nfail, "tiny_batch64_set_systems: %s", tiny_batch_last_error());
+    if (iters) HIP64(hipMemcpy(iters, it.p, Bn * sizeof(int), hipMemcpyDeviceToHost));
+    if (nfail > 0)
+        return fail64(TINY_BATCH_EINVAL, "tiny_batch64_set_systems: the Riccati recursion is singular for %d of %zu systems (iters = -1); models unchanged", nfail, Bn);
+    const double *const m[8] = {dp[4], dp[5], dp[6], dp[7], dp[8], dp[0], dp[1], dp[2]}; // rho, the cache, Adyn = A, Bdyn = B, Q (+ rho in the gather)
+    TRY64(install_models64(tb, m, 1));
+    HIP64(hipDeviceSynchronize()); // the gather has read the buffer
+    return 0;
 }
 
 int tiny_batch64_set_xref_window(TinyBatch64 *tb, const double *table, int rows, const int *start)
@@ -641,91 +693,43 @@ int tiny_batch64_mpc_run_sim(TinyBatch64 *tb, int steps, int window_advance, con
     const bool window = tb->table_rows > 0;
     const int adv = window ? window_advance : 0; // without a window there is nothing to slide
     CHECK64((long long)steps * adv + tb->table_rows + tb->N < 0x7fffffffLL, "steps * window_advance = %lld overflows the window start", (long long)steps * adv);
-    const bool onchip = onchip64(tb);
+    Plan64 plan;
     Params64 P;
-    {
-        const int rc = prepare64(tb, P, !onchip);
-        if (rc < 0) return rc;
-    }
+    TRY64(prepare64(tb, Call64{Call64::Run, w_host != nullptr, x_traj_host != nullptr}, plan, P));
     const size_t row_len = (size_t)tb->batch * tb->nu, need = u0_traj_host ? (size_t)steps * row_len : 0;
-    // a run is simulated when a plant is set or the call passes a disturbance or asks for the state trajectory; any other run enqueues what it always has
-    // (with per-instance models every run is: the simulated kernels are the ones that take a plant per instance, here the instance's own model)
-    const bool sim = tb->plant_mode != 0 || w_host != nullptr || x_traj_host != nullptr || tb->pm;
     const size_t xrow = (size_t)tb->batch * tb->nx, need_w = w_host ? (size_t)steps * xrow : 0, need_x = x_traj_host ? (size_t)steps * xrow : 0;
-    for (const int rg : {grow64(&tb->u0_traj, &tb->u0_traj_cap, need), grow64(&tb->sim_w, &tb->sim_w_cap, need_w), grow64(&tb->sim_x, &tb->sim_x_cap, need_x)})
-        if (rg < 0) return rg;
+    TRY64(grow64(&tb->u0_traj, &tb->u0_traj_cap, need));
+    TRY64(grow64(&tb->sim_w, &tb->sim_w_cap, need_w));
+    TRY64(grow64(&tb->sim_x, &tb->sim_x_cap, need_x));
     if (w_host) HIP64(hipMemcpy(tb->sim_w, w_host, need_w * sizeof(double), hipMemcpyHostToDevice));
     double *const traj = u0_traj_host ? tb->u0_traj : nullptr;
     const double *const d_w = w_host ? tb->sim_w : nullptr;
     double *const d_x = x_traj_host ? tb->sim_x : nullptr;
-    // step k's plant step against the handle's plant, with its rows of w and the two trajectories
-    auto plant_sim = [&](int k) {
-        return enqueue_plant_sim64(tb, d_w ? d_w + (size_t)k * xrow : nullptr, d_x ? d_x + (size_t)k * xrow : nullptr, traj ? traj + (size_t)k * row_len : nullptr,
-                                   window ? tb->xref_start : nullptr, adv);
+    // step k's plant step, with its rows of w and the two trajectories
+    auto plant = [&](int k) {
+        return enqueue_plant64(tb, plan, d_w ? d_w + (size_t)k * xrow : nullptr, d_x ? d_x + (size_t)k * xrow : nullptr, traj ? traj + (size_t)k * row_len : nullptr,
+                               window ? tb->xref_start : nullptr, adv);
     };
-    // step k's plant step of a run that is not simulated: the model's, recording u.col(0) and sliding the window
-    auto plant_run = [&](int k) {
-        HIP64(launch_plant64_run(tb->nx, tb->nu, tb->arr[TINY_ARR_X], tb->arr[TINY_ARR_U], tb->mats, tb->batch, tb->bpad,
-                                 traj ? traj + (size_t)k * row_len : nullptr, window ? tb->xref_start : nullptr, adv));
-        return 0;
-    };
-    if (onchip)
+    if (plan.loop == Loop64::OnChip)
     {
-        // all solves and the plant steps between them in one launch; the last plant step, u.col(0) of the last solve and the last slide follow
+        // all solves and the plant steps between them in one launch; the last plant step (the same plant, its own rows of w and x_traj), u.col(0) of the
+        // last solve and the last slide follow.  y and g of the workspace are zero from the first solve on: the kernel starts from that without reading them
         const Mpc64 L{steps, adv, tb->table_rows, tb->table, tb->xref_start, traj};
         HIP64(hipMemsetAsync(tb->n_unsolved, 0, sizeof(int), 0));
-        // y and g of the workspace are zero from the first solve on: the kernel starts from that without reading them
-        const int k = steps - 1;
-        if (tb->pm)
-        {
-            const Sim64 S{tb->plant_mode ? tb->plant_rows : nullptr, tb->plant_mode == 2 ? (size_t)(tb->nx + tb->nu) * 16 : 0, d_w, d_x};
-            HIP64(launch_rows64_loop_pm(tb->nx, tb->nu, tb->N, P, L, S, models_of(tb)));
-            const int rc = plant_sim(k);
-            if (rc < 0) return rc;
-        }
-        else if (sim)
-        {
-            // (one step never reaches the kernel's plant step: the MPC instantiation serves it)
-            if (steps > 1)
-            {
-                const Sim64 S{tb->plant_mode ? tb->plant_rows : nullptr, tb->plant_mode == 2 ? (size_t)(tb->nx + tb->nu) * 16 : 0, d_w, d_x};
-                HIP64(launch_rows64_sim(tb->nx, tb->nu, tb->N, P, tb->row_gains, L, S));
-            }
-            else
-            {
-                const int rc = launch_solve64(tb, P, &L);
-                if (rc < 0) return rc;
-            }
-            const int rc = plant_sim(k); // the last plant step is the host's: the same plant, its own rows of w and x_traj
-            if (rc < 0) return rc;
-        }
-        else
-        {
-            int rc = launch_solve64(tb, P, &L);
-            if (rc < 0) return rc;
-            rc = plant_run(k);
-            if (rc < 0) return rc;
-        }
+        TRY64(launch_solve64(tb, plan, P, &L, d_w, d_x));
+        TRY64(plant(steps - 1));
     }
     else
-    {
         for (int k = 0; k < steps; k++)
         {
-            if (window)
-            {
-                const int rc = gather_window64(tb);
-                if (rc < 0) return rc;
-            }
+            if (window) TRY64(gather_window64(tb));
             HIP64(hipMemsetAsync(tb->arr[TINY_ARR_Y], 0, (size_t)(tb->N - 1) * tb->nu * tb->bpad * sizeof(double), 0));
             HIP64(hipMemsetAsync(tb->arr[TINY_ARR_G], 0, (size_t)tb->N * tb->nx * tb->bpad * sizeof(double), 0));
             HIP64(hipMemsetAsync(tb->n_unsolved, 0, sizeof(int), 0));
-            const int rc = launch_solve64(tb, P);
-            if (rc < 0) return rc;
-            const int rp = sim ? plant_sim(k) : plant_run(k);
-            if (rp < 0) return rp;
+            TRY64(launch_solve64(tb, plan, P));
+            TRY64(plant(k));
             if (adv) tb->xwin_valid = false;
         }
-    }
     if (adv) tb->xwin_valid = false;
     int n = 0;
     HIP64(hipMemcpy(&n, tb->n_unsolved, sizeof(int), hipMemcpyDeviceToHost)); // the only host synchronisation of the run
@@ -734,10 +738,7 @@ int tiny_batch64_mpc_run_sim(TinyBatch64 *tb, int steps, int window_advance, con
     return n > 0 ? 1 : 0;
 }
 
-int tiny_batch64_mpc_run_traj(TinyBatch64 *tb, int steps, int window_advance, double *u0_traj_host)
-{
-    return tiny_batch64_mpc_run_sim(tb, steps, window_advance, nullptr, u0_traj_host, nullptr);
-}
+int tiny_batch64_mpc_run_traj(TinyBatch64 *tb, int steps, int adv, double *u0_traj_host) { return tiny_batch64_mpc_run_sim(tb, steps, adv, nullptr, u0_traj_host, nullptr); }
 int tiny_batch64_mpc_run(TinyBatch64 *tb, int steps, int window_advance) { return tiny_batch64_mpc_run_sim(tb, steps, window_advance, nullptr, nullptr, nullptr); }
 
 int tiny_batch64_get_first_columns(TinyBatch64 *tb, double *x0, double *u0)
@@ -765,28 +766,23 @@ int tiny_batch64_select_kernel(TinyBatch64 *tb, int which)
     return 0;
 }
 
+static const char *plan_name64(TinyBatch64 *tb, Call64::Kind kind, char (&nm)[64])
+{
+    if (!tb) return "";
+    Plan64 plan;
+    (void)resolve_plan64(tb, Call64{kind}, &plan); // (neither a solve's nor a run's resolution refuses anything)
+    return name_of(tb, plan, nm);
+}
 const char *tiny_batch64_kernel_name(TinyBatch64 *tb)
 {
     static thread_local char nm[64];
-    if (!tb) return "";
-    const bool rows = rows_chosen(tb);
-    const char *const pm = tb->pm ? ",pm" : "";
-    if (rows && !rows_unrolled(tb->nx, tb->nu, tb->N)) snprintf(nm, sizeof nm, "rows64<%d,%d,n<=%d%s>", tb->nx, tb->nu, tb->N <= 32 ? 32 : 64, pm);
-    else if (rows) snprintf(nm, sizeof nm, "rows64<%d,%d,%d%s>", tb->nx, tb->nu, tb->N, pm);
-    else snprintf(nm, sizeof nm, "thread64<%d,%d%s>", tb->nx, tb->nu, pm);
-    return nm;
+    return plan_name64(tb, Call64::Solve, nm);
 }
-
+// the kernel a run launches: the solve kernel's name where the run is a launch sequence.  It knows the handle alone, not a call's w / x_traj
 const char *tiny_batch64_closed_loop_kernel_name(TinyBatch64 *tb)
 {
     static thread_local char nm[64];
-    if (!tb) return "";
-    const char *solve = tiny_batch64_kernel_name(tb);
-    if (!onchip64(tb)) return solve;
-    // rows64<12,4,10> -> rows64<12,4,10,mpc>; while a plant is set ,sim> (a run that passes w or x_traj without one is simulated too: only the call knows)
-    // with per-instance models ",pm" stays last: rows64<12,4,10,pm> -> rows64<12,4,10,mpc,pm>
-    snprintf(nm, sizeof nm, "%.*s,%s%s>", (int)strlen(solve) - (tb->pm ? 4 : 1), solve, tb->plant_mode ? "sim" : "mpc", tb->pm ? ",pm" : "");
-    return nm;
+    return plan_name64(tb, Call64::Run, nm);
 }
 
 int tiny_batch64_set_array(TinyBatch64 *tb, int id, const double *src)
