@@ -234,6 +234,7 @@ __global__ __launch_bounds__(WAVE) void admm_quadlane_kernel(const RowParams P)
         float u0v, x1;
         lqr(x0, dd[0], u0v, x1); // u_0 of the solve that just finished, in the solver's own arithmetic
         if (P.u0_traj && valid && lead) P.u0_traj[(long long)ms * P.batch + inst] = u0v;
+        if (valid && lead) F.log(P, ms, inst);
         if constexpr (MPC)
         {
             // plant step x_1 = Adyn x0 + Bdyn u_0 in the plant kernel's (sequential, separately rounded) arithmetic

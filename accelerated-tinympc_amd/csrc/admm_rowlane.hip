@@ -254,6 +254,10 @@ __device__ __forceinline__ void rowlane_body(const RowParams &P, const ModelPara
         float sv0, x1;
         lqr(x0, c[0], sv0, x1); // [x_0 ; u_0] of the solve that just finished, in the solver's own arithmetic
         if (P.u0_traj && valid && is_u) P.u0_traj[((long long)ms * P.batch + inst) * NU + (r16 - NX)] = sv0;
+        // iter and status of the solve that just finished: row ms of the logs.  (Not with per-instance models: their N = 50 fma loops sit at 256 registers
+        // and the store moved their pinned scratch; the host replays such a run step by step when it asks for a log.)
+        if constexpr (!PM)
+            if (valid && r16 == 0) F.log(P, ms, inst);
         if constexpr (SIM)
         {
             // x_1 = (A_p x0 + B_p u_0) + w: the same DPP groups and sums with the plant's rows, then one separately rounded add.

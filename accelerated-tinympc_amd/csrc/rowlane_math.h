@@ -452,6 +452,8 @@ struct SolveFrame
         return judge(P, it, now);
     }
     __device__ __forceinline__ bool solved() const { return st == TINY_STATUS_SOLVED_; }
+    // step boundary of the on-chip closed loop: iter and status of the solve that just finished into row ms of the logs (one lane per instance calls)
+    __device__ __forceinline__ void log(const RowParams &P, int ms, int inst) const { log_step(P, ms, inst, itn, st); }
     // max_iter <= 0: tiny_solve only sets status and iter (admm.cpp:114-117,151).  true: the kernel returns, nothing else is written
     __device__ __forceinline__ bool no_iterations(const RowParams &P, int inst, bool lead) const
     {

@@ -211,8 +211,8 @@ struct TinyBatch
     // on-chip loop ([1 or batch][plant_row_floats]: SimParams)
     int plant_mode = 0;
     float *plant_A = nullptr, *plant_B = nullptr, *plant_rows = nullptr;
-    float *sim_stage[3] = {};      // tiny_batch_mpc_run_sim's device copies of w, u0_traj, x_traj: kept between calls (sized_buffer), so that their
-    size_t sim_stage_n[3] = {};    // addresses, which the captured graph bakes in, hold from call to call
+    float *sim_stage[5] = {};      // tiny_batch_mpc_run_log's device copies of w, u0_traj, x_traj, iter_log, status_log: kept between calls (sized_buffer), so that their
+    size_t sim_stage_n[5] = {};    // addresses, which the captured graph bakes in, hold from call to call
     bool h16 = false; // ROW-layout arrays, Xref and bounds stored as IEEE binary16 (tiny_batch_set_storage)
     bool dual32 = false; // with h16: the duals pair gy IS fp32 right now (the state of the array)
     bool dual32_pref = false;   // tiny_batch_set_storage(tb, 16): fp32 duals wherever the kernel a call resolves to implements them, 16-bit duals elsewhere
@@ -1023,6 +1023,7 @@ void fill_row_params(TinyBatch *tb, RowParams &P, bool exact)
     P.dual32 = (tb->h16 && tb->dual32) ? 1 : 0;
     P.inst_map = nullptr; // enqueue_dispatch_order sets it for the one launch that reads it
     P.exact_ties = tb->zero_ties ? 1 : 0;
+    P.iter_log = P.status_log = nullptr; // mpc_run_sim sets them for the on-chip closed loop
 }
 
 int check_optional_terms(const TinyBatch *tb)
@@ -2188,7 +2189,8 @@ int tiny_batch_mpc_step_async(TinyBatch *tb, int window_advance)
 //    replayed, which removes the per-launch overhead that dominates small batches with short warm-started solves.
 namespace
 {
-int mpc_run_sim(TinyBatch *tb, const char *who, int steps, int window_advance, const float *d_w, float *d_u0_traj, float *d_x_traj);
+int mpc_run_sim(TinyBatch *tb, const char *who, int steps, int window_advance, const float *d_w, float *d_u0_traj, float *d_x_traj, int *d_iter_log = nullptr,
+                int *d_status_log = nullptr);
 }
 
 // ... against the plant of tiny_batch_set_plant, with a disturbance d_w and the state trajectory d_x_traj (both DEVICE [steps][B][nx], may be NULL).  A run
@@ -2200,6 +2202,16 @@ int tiny_batch_mpc_run_sim_async(TinyBatch *tb, int steps, int window_advance, c
     return mpc_run_sim(tb, "tiny_batch_mpc_run_sim_async", steps, window_advance, d_w, d_u0_traj, d_x_traj);
 }
 
+// ... and the per-step solver log: d_iter_log / d_status_log (DEVICE [steps][B] ints, either may be NULL) receive iter[] and status[] after the solve
+// of every step — what a step-by-step loop reads with tiny_batch_get_status after step k.  A log does not make a run simulated: kernel and results are those
+// of the same call without it.  The 16-lane and quad loops store rows 0 .. steps - 2 on chip, every replayed kernel copies per step — the matrix-core
+// kernel and the 16-lane kernel with per-instance models among them: with a log their run is replayed step by step
+int tiny_batch_mpc_run_log_async(TinyBatch *tb, int steps, int window_advance, const float *d_w, float *d_u0_traj, float *d_x_traj, int *d_iter_log, int *d_status_log)
+{
+    CHECK_TB(tb);
+    return mpc_run_sim(tb, "tiny_batch_mpc_run_log_async", steps, window_advance, d_w, d_u0_traj, d_x_traj, d_iter_log, d_status_log);
+}
+
 int tiny_batch_mpc_run_traj_async(TinyBatch *tb, int steps, int window_advance, float *d_u0_traj)
 {
     CHECK_TB(tb);
@@ -2209,7 +2221,9 @@ int tiny_batch_mpc_run_traj_async(TinyBatch *tb, int steps, int window_advance, 
 namespace
 {
 // who: the public call, for its messages
-int mpc_run_sim(TinyBatch *tb, const char *who, int steps, int window_advance, const float *d_w, float *d_u0_traj, float *d_x_traj)
+// d_iter_log / d_status_log: the per-step solver log (DEVICE [steps][B] ints, may be NULL): row k = iter[] / status[] after the solve of MPC step k.  They
+// do not make a run simulated and choose no kernel
+int mpc_run_sim(TinyBatch *tb, const char *who, int steps, int window_advance, const float *d_w, float *d_u0_traj, float *d_x_traj, int *d_iter_log, int *d_status_log)
 {
     if (steps < 1) return fail(TINY_BATCH_EINVAL, "%s: steps must be >= 1", who);
     if (window_advance < 0) return fail(TINY_BATCH_EINVAL, "%s: window_advance must be >= 0 (got %d): the window gather clamps at the last table row only", who, window_advance);
@@ -2227,11 +2241,25 @@ int mpc_run_sim(TinyBatch *tb, const char *who, int steps, int window_advance, c
     // the rows of MPC step k
     auto w_at = [&](int k) { return d_w ? d_w + (size_t)k * x0n : nullptr; };
     auto xt_at = [&](int k) { return d_x_traj ? d_x_traj + (size_t)k * x0n : nullptr; };
-    if (traits(pl.kernel).onchip_mpc && !tb->h16 && steps > 1 && bounds_all_shared(tb) && (!sim || pl.kernel == Kernel::Rowlane))
+    // row k of the logs: iter[] / status[] as the solve before it left them (two device-to-device copies on the handle's stream: captured with the rest)
+    auto log_row = [&](int k) {
+        const size_t o = (size_t)k * tb->batch, bytes = (size_t)tb->batch * sizeof(int);
+        hipError_t e = hipSuccess;
+        if (d_iter_log) e = hipMemcpyAsync(d_iter_log + o, tb->iter, bytes, hipMemcpyDeviceToDevice, tb->stream);
+        if (e == hipSuccess && d_status_log) e = hipMemcpyAsync(d_status_log + o, tb->status, bytes, hipMemcpyDeviceToDevice, tb->stream);
+        return e;
+    };
+    // (the matrix-core kernel's loop and the 16-lane loops with per-instance models do not log: their largest instantiations sit at the register
+    //  allocator's cliff, and the store moved their pinned scratch whichever way it was written.  A run that asks for a log there replays the same
+    //  kernel step by step, with the same bits)
+    const bool logs = d_iter_log != nullptr || d_status_log != nullptr;
+    if (traits(pl.kernel).onchip_mpc && !tb->h16 && steps > 1 && bounds_all_shared(tb) && (!sim || pl.kernel == Kernel::Rowlane) &&
+        !(logs && (pl.kernel == Kernel::Tile16 || pl.pm)))
     {
         RowParams P;
         fill_row_params(tb, P, pl.exact);
         P.mpc_steps = steps; P.window_advance = window_advance; P.u0_traj = d_u0_traj;
+        P.iter_log = d_iter_log; P.status_log = d_status_log;
         SimParams S;
         if (tb->plant_mode) { S.plant = tb->plant_rows; S.plant_stride = tb->plant_mode == 2 ? (unsigned)plant_row_floats(tb->nx, tb->nu) : 0u; }
         S.w = d_w; S.x_traj = d_x_traj;
@@ -2243,6 +2271,7 @@ int mpc_run_sim(TinyBatch *tb, const char *who, int steps, int window_advance, c
         const hipError_t e = launch_kernel(tb, pl, P, sim ? &S : nullptr);
         if (e != hipSuccess) return fail(TINY_BATCH_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
         if (d_u0_traj) TRY(launch_unpack(tb, work_ptr(tb, TINY_ARR_U), d_u0_traj + (size_t)(steps - 1) * u0n, tb->layout, 1, tb->batch, 0, 1));
+        HIP_TRY(log_row(steps - 1)); // the last row of the logs is the host's too: iter[] / status[] as the kernel's live-out left them
         TRY(enqueue_plant_step(tb, window_advance, w_at(steps - 1), xt_at(steps - 1))); // the last step's plant step is the host's: the same plant, its own rows
         tb->duals_zero_pending = tb->cold_pending = false;
         tb->iter_history = true; // iter[] = the counts of the run's last solve
@@ -2259,15 +2288,16 @@ int mpc_run_sim(TinyBatch *tb, const char *who, int steps, int window_advance, c
     // (round 3: the signature is complete — rho, the shared / per-instance modes that set the strides, the bound flags and the
     // dispatch order are in it — so setters that only change buffer CONTENTS no longer drop the graph: `set_xref; mpc_run(k)`
     // in a loop replays one captured graph instead of re-capturing it every step)
-    char sig[720];
-    snprintf(sig, sizeof sig, "%d|%p|%p|%p|%p|%p|%p|%p|%p|%p|%d|%d|%d|%s|%d|%d|%g|%g|%d|%d|%p|%p|%p|%d|%p|%p|%p|%p|%d%d|%a|%d%d%d|%d%d|%d|%p|%p|%p|%d", tb->plant_mode, (void *)tb->plant_A,
+    char sig[768];
+    snprintf(sig, sizeof sig, "%d|%p|%p|%p|%p|%p|%p|%p|%p|%p|%d|%d|%d|%s|%d|%d|%g|%g|%d|%d|%p|%p|%p|%d|%p|%p|%p|%p|%d%d|%a|%d%d%d|%d%d|%d|%p|%p|%p|%d|%p|%p", tb->plant_mode, (void *)tb->plant_A,
              (void *)tb->plant_B, (const void *)d_w, (void *)d_x_traj, (void *)tb->pm_src, (void *)tb->pm_row[0],
              (void *)tb->pm_row[1], (void *)tb->pm_wave[0], (void *)tb->pm_wave[1], steps, window_advance, tb->variant, kernel_name(tb, pl).c_str(), tb->max_iter,
              tb->check_termination, (double)tb->abs_pri_tol, (double)tb->abs_dua_tol, tb->xref_mode, tb->table_rows, (void *)tb->pair[0],
              (void *)tb->arr[0], (void *)tb->r_bounds, (int)tb->h16, (void *)tb->stream, (void *)d_u0_traj, (void *)tb->r_xref,
              (void *)tb->r_uref, (int)tb->en_uref, (int)tb->en_d2p, (double)tb->rho, (int)bounds_all_shared(tb),
              (int)(tb->in_xref.set && tb->in_xref.shared), (int)(tb->in_uref.set && tb->in_uref.shared), tb->en_state_bound, tb->en_input_bound,
-             tb->dispatch_mode, (void *)tb->order_dev, (void *)tb->mats_exact, (void *)tb->xref_start, (int)tb->zero_ties);
+             tb->dispatch_mode, (void *)tb->order_dev, (void *)tb->mats_exact, (void *)tb->xref_start, (int)tb->zero_ties,
+             (void *)d_iter_log, (void *)d_status_log);
     if (!tb->graph_exec || tb->graph_sig != sig)
     {
         if (tb->graph_exec) { (void)hipGraphExecDestroy(tb->graph_exec); tb->graph_exec = nullptr; }
@@ -2279,6 +2309,7 @@ int mpc_run_sim(TinyBatch *tb, const char *who, int steps, int window_advance, c
             tb->duals_zero_pending = true;
             rc = enqueue_solve(tb, pl, false);
             if (rc == 0 && d_u0_traj) rc = launch_unpack(tb, work_ptr(tb, TINY_ARR_U), d_u0_traj + (size_t)k * u0n, tb->layout, 1, tb->batch, 0, 1);
+            if (rc == 0 && log_row(k) != hipSuccess) rc = fail(TINY_BATCH_EHIP, "%s: the copy of a log row failed", who);
             if (rc == 0) rc = enqueue_plant_step(tb, window_advance, w_at(k), xt_at(k));
         }
         hipError_t ec = hipStreamEndCapture(tb->stream, &graph);
@@ -2323,19 +2354,22 @@ int tiny_batch_mpc_run_traj(TinyBatch *tb, int steps, int window_advance, float 
     return rc;
 }
 
-// host-array variant of tiny_batch_mpc_run_sim_async (any of the three may be NULL): the device buffers live on the HANDLE's device for the call
-int tiny_batch_mpc_run_sim(TinyBatch *tb, int steps, int window_advance, const float *w, float *u0_traj, float *x_traj)
+namespace
 {
-    CHECK_TB(tb);
-    if (steps < 1) return fail(TINY_BATCH_EINVAL, "tiny_batch_mpc_run_sim: steps must be >= 1");
+// host-array variant of tiny_batch_mpc_run_log_async (any of the five may be NULL): the device buffers live on the HANDLE's device for the call.
+// who: the public call, for its messages
+int mpc_run_log_host(TinyBatch *tb, const char *who, int steps, int window_advance, const float *w, float *u0_traj, float *x_traj, int *iter_log, int *status_log)
+{
+    if (!tb) return fail(TINY_BATCH_EINVAL, "%s: NULL TinyBatch handle", who);
+    if (steps < 1) return fail(TINY_BATCH_EINVAL, "%s: steps must be >= 1", who);
     TRY(set_device(tb));
     // device copies kept on the handle and re-allocated only when their size changes: on the replayed paths the captured graph bakes their addresses
-    // in (they are in its signature), and a loop of equal calls must replay one graph
-    const size_t nxf = (size_t)steps * tb->batch * tb->nx, nuf = (size_t)steps * tb->batch * tb->nu;
-    const void *host[3] = {w, u0_traj, x_traj};
-    const size_t nf[3] = {nxf, nuf, nxf};
-    float *dev[3] = {};
-    for (int k = 0; k < 3; k++)
+    // in (they are in its signature), and a loop of equal calls must replay one graph.  (The two logs are ints in float-sized words.)
+    const size_t nxf = (size_t)steps * tb->batch * tb->nx, nuf = (size_t)steps * tb->batch * tb->nu, nlf = (size_t)steps * tb->batch;
+    const void *host[5] = {w, u0_traj, x_traj, iter_log, status_log};
+    const size_t nf[5] = {nxf, nuf, nxf, nlf, nlf};
+    float *dev[5] = {};
+    for (int k = 0; k < 5; k++)
         if (host[k])
         {
             if (tb->sim_stage[k] && tb->sim_stage_n[k] != nf[k]) HIP_TRY(hipStreamSynchronize(tb->stream)); // a run still using the old buffer may be in flight
@@ -2343,11 +2377,24 @@ int tiny_batch_mpc_run_sim(TinyBatch *tb, int steps, int window_advance, const f
             dev[k] = tb->sim_stage[k];
         }
     if (w) HIP_TRY(hipMemcpy(dev[0], w, nxf * sizeof(float), hipMemcpyHostToDevice));
-    TRY(mpc_run_sim(tb, "tiny_batch_mpc_run_sim", steps, window_advance, dev[0], dev[1], dev[2]));
+    TRY(mpc_run_sim(tb, who, steps, window_advance, dev[0], dev[1], dev[2], (int *)dev[3], (int *)dev[4]));
     HIP_TRY(hipStreamSynchronize(tb->stream));
     if (u0_traj) HIP_TRY(hipMemcpy(u0_traj, dev[1], nuf * sizeof(float), hipMemcpyDeviceToHost));
     if (x_traj) HIP_TRY(hipMemcpy(x_traj, dev[2], nxf * sizeof(float), hipMemcpyDeviceToHost));
+    if (iter_log) HIP_TRY(hipMemcpy(iter_log, dev[3], nlf * sizeof(int), hipMemcpyDeviceToHost));
+    if (status_log) HIP_TRY(hipMemcpy(status_log, dev[4], nlf * sizeof(int), hipMemcpyDeviceToHost));
     return 0;
+}
+} // namespace
+
+int tiny_batch_mpc_run_log(TinyBatch *tb, int steps, int window_advance, const float *w, float *u0_traj, float *x_traj, int *iter_log, int *status_log)
+{
+    return mpc_run_log_host(tb, "tiny_batch_mpc_run_log", steps, window_advance, w, u0_traj, x_traj, iter_log, status_log);
+}
+
+int tiny_batch_mpc_run_sim(TinyBatch *tb, int steps, int window_advance, const float *w, float *u0_traj, float *x_traj)
+{
+    return mpc_run_log_host(tb, "tiny_batch_mpc_run_sim", steps, window_advance, w, u0_traj, x_traj, nullptr, nullptr);
 }
 
 int tiny_batch_get_x0(TinyBatch *tb, float *x0)

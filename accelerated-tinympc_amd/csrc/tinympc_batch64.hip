@@ -95,6 +95,9 @@ struct TinyBatch64
     int plant_mode = 0;
     double *plant_A = nullptr, *plant_B = nullptr, *plant_rows = nullptr, *sim_w = nullptr, *sim_x = nullptr;
     size_t sim_w_cap = 0, sim_x_cap = 0;
+    // the device copies of a call's per-step solver log (tiny_batch64_mpc_run_log): [steps][batch] ints each, grow only
+    int *log_iter = nullptr, *log_status = nullptr;
+    size_t log_iter_cap = 0, log_status_cap = 0;
     // per-instance models (tiny_batch64_set_models): one record per instance in the layout of `mats` ([batch][rec_len()]) and rho [batch]; while pm
     // is set they replace mats, row_gains and rho in every launch
     bool pm = false;
@@ -201,6 +204,7 @@ struct Call64
 {
     enum Kind { StepFn, Solve, Run } kind; // one of the six step functions; one solve (with or without a plant step behind it); a closed-loop run
     bool w = false, x_traj = false;        // the caller passed a disturbance / asks for the state trajectory
+    bool log = false;                      // ... asks for the per-step solver log (tiny_batch64_mpc_run_log)
 };
 
 // Reads the handle and changes nothing.  The one refusal a resolution can meet is the step functions' under models: tiny_batch64_select_kernel refuses
@@ -224,7 +228,9 @@ int resolve_plan64(const TinyBatch64 *tb, const Call64 &call, Plan64 *out)
         // sets status and iter only) is left to the launch sequence.  Developer aid, read on every resolution: TINYMPC_F64_LOOP=sequence sends every run
         // through the launch sequence (tools/closed_loop64_time.py times the two against each other over the same solve kernel, in one process).
         const char *force = getenv("TINYMPC_F64_LOOP");
-        const bool on_chip = p.family == Family64::Rows && p.body != Body64::Cap64 && tb->max_iter >= 1 && !(force && !strcmp(force, "sequence"));
+        // A run that asks for the per-step solver log is a launch sequence as well: the on-chip loops do not log (their instruction streams are pinned,
+        // tests/test_isa_sim64.py), the sequence copies iter[] / status[] behind each solve of the same solve kernel, with the same bits.
+        const bool on_chip = p.family == Family64::Rows && p.body != Body64::Cap64 && tb->max_iter >= 1 && !(force && !strcmp(force, "sequence")) && !call.log;
         p.loop = on_chip ? Loop64::OnChip : Loop64::Sequence;
     }
     *out = p;
@@ -347,11 +353,12 @@ int solve64(TinyBatch64 *tb, const Call64 &call, Plan64 &plan)
 }
 
 // a device buffer kept on the handle between calls: re-allocated only when it has to grow
-int grow64(double **buf, size_t *cap, size_t need)
+template <typename T>
+int grow64(T **buf, size_t *cap, size_t need)
 {
     if (need <= *cap) return 0;
     (void)hipFree(*buf); *buf = nullptr; *cap = 0;
-    HIP64(hipMalloc((void **)buf, need * sizeof(double)));
+    HIP64(hipMalloc((void **)buf, need * sizeof(T)));
     *cap = need;
     return 0;
 }
@@ -410,6 +417,7 @@ void tiny_batch64_destroy(TinyBatch64 *tb)
     (void)hipFree(tb->mats); (void)hipFree(tb->res); (void)hipFree(tb->staging); (void)hipFree(tb->row_gains);
     (void)hipFree(tb->status); (void)hipFree(tb->iter); (void)hipFree(tb->n_unsolved);
     (void)hipFree(tb->table); (void)hipFree(tb->xwin); (void)hipFree(tb->u0_traj); (void)hipFree(tb->xref_start);
+    (void)hipFree(tb->log_iter); (void)hipFree(tb->log_status);
     (void)hipFree(tb->plant_A); (void)hipFree(tb->plant_B); (void)hipFree(tb->plant_rows); (void)hipFree(tb->sim_w); (void)hipFree(tb->sim_x);
     (void)hipFree(tb->pm_rec); (void)hipFree(tb->pm_rho);
     delete tb;
@@ -685,7 +693,8 @@ int tiny_batch64_get_xref_start(TinyBatch64 *tb, int *start)
     return 0;
 }
 
-int tiny_batch64_mpc_run_sim(TinyBatch64 *tb, int steps, int window_advance, const double *w_host, double *u0_traj_host, double *x_traj_host)
+int tiny_batch64_mpc_run_log(TinyBatch64 *tb, int steps, int window_advance, const double *w_host, double *u0_traj_host, double *x_traj_host, int *iter_log_host,
+                             int *status_log_host)
 {
     CHECK64(tb, "NULL handle");
     CHECK64(steps >= 1, "steps must be >= 1 (got %d)", steps);
@@ -695,12 +704,23 @@ int tiny_batch64_mpc_run_sim(TinyBatch64 *tb, int steps, int window_advance, con
     CHECK64((long long)steps * adv + tb->table_rows + tb->N < 0x7fffffffLL, "steps * window_advance = %lld overflows the window start", (long long)steps * adv);
     Plan64 plan;
     Params64 P;
-    TRY64(prepare64(tb, Call64{Call64::Run, w_host != nullptr, x_traj_host != nullptr}, plan, P));
+    TRY64(prepare64(tb, Call64{Call64::Run, w_host != nullptr, x_traj_host != nullptr, iter_log_host != nullptr || status_log_host != nullptr}, plan, P));
     const size_t row_len = (size_t)tb->batch * tb->nu, need = u0_traj_host ? (size_t)steps * row_len : 0;
     const size_t xrow = (size_t)tb->batch * tb->nx, need_w = w_host ? (size_t)steps * xrow : 0, need_x = x_traj_host ? (size_t)steps * xrow : 0;
     TRY64(grow64(&tb->u0_traj, &tb->u0_traj_cap, need));
     TRY64(grow64(&tb->sim_w, &tb->sim_w_cap, need_w));
     TRY64(grow64(&tb->sim_x, &tb->sim_x_cap, need_x));
+    // the per-step solver log: neither the plan nor the plant step knows of it
+    const size_t lrow = (size_t)tb->batch, need_l = (size_t)steps * lrow;
+    TRY64(grow64(&tb->log_iter, &tb->log_iter_cap, iter_log_host ? need_l : 0));
+    TRY64(grow64(&tb->log_status, &tb->log_status_cap, status_log_host ? need_l : 0));
+    int *const d_il = iter_log_host ? tb->log_iter : nullptr, *const d_sl = status_log_host ? tb->log_status : nullptr;
+    // row k of the logs: iter[] / status[] as the solve before it left them
+    auto log_row = [&](int k) {
+        if (d_il) HIP64(hipMemcpyAsync(d_il + (size_t)k * lrow, tb->iter, lrow * sizeof(int), hipMemcpyDeviceToDevice, 0));
+        if (d_sl) HIP64(hipMemcpyAsync(d_sl + (size_t)k * lrow, tb->status, lrow * sizeof(int), hipMemcpyDeviceToDevice, 0));
+        return 0;
+    };
     if (w_host) HIP64(hipMemcpy(tb->sim_w, w_host, need_w * sizeof(double), hipMemcpyHostToDevice));
     double *const traj = u0_traj_host ? tb->u0_traj : nullptr;
     const double *const d_w = w_host ? tb->sim_w : nullptr;
@@ -727,6 +747,7 @@ int tiny_batch64_mpc_run_sim(TinyBatch64 *tb, int steps, int window_advance, con
             HIP64(hipMemsetAsync(tb->arr[TINY_ARR_G], 0, (size_t)tb->N * tb->nx * tb->bpad * sizeof(double), 0));
             HIP64(hipMemsetAsync(tb->n_unsolved, 0, sizeof(int), 0));
             TRY64(launch_solve64(tb, plan, P));
+            TRY64(log_row(k));
             TRY64(plant(k));
             if (adv) tb->xwin_valid = false;
         }
@@ -735,7 +756,14 @@ int tiny_batch64_mpc_run_sim(TinyBatch64 *tb, int steps, int window_advance, con
     HIP64(hipMemcpy(&n, tb->n_unsolved, sizeof(int), hipMemcpyDeviceToHost)); // the only host synchronisation of the run
     if (u0_traj_host) HIP64(hipMemcpy(u0_traj_host, tb->u0_traj, need * sizeof(double), hipMemcpyDeviceToHost));
     if (x_traj_host) HIP64(hipMemcpy(x_traj_host, tb->sim_x, need_x * sizeof(double), hipMemcpyDeviceToHost));
+    if (iter_log_host) HIP64(hipMemcpy(iter_log_host, d_il, need_l * sizeof(int), hipMemcpyDeviceToHost));
+    if (status_log_host) HIP64(hipMemcpy(status_log_host, d_sl, need_l * sizeof(int), hipMemcpyDeviceToHost));
     return n > 0 ? 1 : 0;
+}
+
+int tiny_batch64_mpc_run_sim(TinyBatch64 *tb, int steps, int window_advance, const double *w_host, double *u0_traj_host, double *x_traj_host)
+{
+    return tiny_batch64_mpc_run_log(tb, steps, window_advance, w_host, u0_traj_host, x_traj_host, nullptr, nullptr);
 }
 
 int tiny_batch64_mpc_run_traj(TinyBatch64 *tb, int steps, int adv, double *u0_traj_host) { return tiny_batch64_mpc_run_sim(tb, steps, adv, nullptr, u0_traj_host, nullptr); }

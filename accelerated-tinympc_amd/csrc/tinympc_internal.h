@@ -120,7 +120,31 @@ struct RowParams
                                  // shared-table instantiations of admm_tile16.hip and by the tile key kernel only; NULL for every other launch
     int exact_ties;              // the bounds table holds lo = -0 under hi > 0 or hi = +0 over lo <= -0 (prepare_inputs): the rolled-loop, quad and state-on-chip wave kernels
                                  // then project by box_project's compare-selects instead of v_med3_f32 in exact arithmetic.  Appended: no other argument moves
+    int *iter_log, *status_log;  // [mpc_steps][batch] or NULL: iter / status of every solve of the on-chip closed loop (tiny_batch_mpc_run_log_async).  Like
+                                 // u0_traj the kernel writes rows 0 .. mpc_steps - 2, the host the last one.  Appended: no other argument moves
 };
+
+// Row `ms` of the per-step solver log at the step boundary of an on-chip closed loop: one lane per instance calls it with the frame's iter and status.
+// The two pointers are read from the kernel-argument segment HERE (RowParams is the first argument of every kernel that logs), through an offset the
+// compiler cannot see through: as members of P they are loaded at the kernel's entry and held in four scalar registers across every iteration loop,
+// which are then spilled or push vector registers out (the quad kernel's closed loop: 169 -> 173 registers as members, 170 this way).  The row
+// offset ms * batch is a scalar.
+__device__ __forceinline__ void log_step([[maybe_unused]] const RowParams &P, [[maybe_unused]] int ms, [[maybe_unused]] int inst, [[maybe_unused]] int itn,
+                                         [[maybe_unused]] int st)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(inst)); // (the lane offset is made here too, not ahead of the MPC loop)
+    int oz;
+    asm volatile("s_mov_b32 %0, 0" : "=s"(oz));
+    typedef const char __attribute__((address_space(4))) karg_byte; // the constant address space: scalar loads
+    typedef int *const __attribute__((address_space(4))) karg_int_ptr;
+    karg_byte *const ka = (karg_byte *)__builtin_amdgcn_kernarg_segment_ptr() + oz;
+    int *const il = *(karg_int_ptr *)(ka + offsetof(RowParams, iter_log)), *const sl = *(karg_int_ptr *)(ka + offsetof(RowParams, status_log));
+    const size_t row = (size_t)ms * P.batch;
+    if (il) (il + row)[(unsigned)inst] = itn;
+    if (sl) (sl + row)[(unsigned)inst] = st;
+#endif
+}
 
 // The box projection of the slack update, u_max.cwiseMin(u_min.cwiseMax(t)) (admm.cpp:51-60), on a {lo, hi} whose lo the host folded to min(lo, hi).
 // v_med3_f32 returns the VALUE of the reference's two compare-selects for every t, but it orders -0 below +0 where they compare the two equal and

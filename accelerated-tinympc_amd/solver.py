@@ -91,6 +91,7 @@ def load_library(build_if_missing: bool = False) -> C.CDLL:
         "tiny_batch_set_plant": [P, F, F, C.c_int], "tiny_batch_clear_plant": [P], "tiny_batch_plant_mode": [P],
         "tiny_batch_mpc_step_sim_async": [P, C.c_int, P], "tiny_batch_mpc_run_sim_async": [P, C.c_int, C.c_int, P, P, P],
         "tiny_batch_mpc_run_sim": [P, C.c_int, C.c_int, F, F, F],
+        "tiny_batch_mpc_run_log_async": [P, C.c_int, C.c_int, P, P, P, P, P], "tiny_batch_mpc_run_log": [P, C.c_int, C.c_int, F, F, F, I, I],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)
@@ -113,6 +114,7 @@ def load_library(build_if_missing: bool = False) -> C.CDLL:
         "tiny_batch64_mpc_run": [P, C.c_int, C.c_int], "tiny_batch64_mpc_run_traj": [P, C.c_int, C.c_int, D],
         "tiny_batch64_set_plant": [P, D, D, C.c_int], "tiny_batch64_clear_plant": [P], "tiny_batch64_plant_mode": [P],
         "tiny_batch64_mpc_step_sim": [P, D], "tiny_batch64_mpc_run_sim": [P, C.c_int, C.c_int, D, D, D],
+        "tiny_batch64_mpc_run_log": [P, C.c_int, C.c_int, D, D, D, I, I],
         "tiny_batch64_set_models": [P, D, D, D, D, D, D, D, D], "tiny_batch64_set_models_device": [P, P, P, P, P, P, P, P, P],
         "tiny_batch64_clear_models": [P], "tiny_batch64_models_per_instance": [P],
         "tiny_batch64_set_systems": [P, D, D, D, D, D, I],
@@ -519,6 +521,22 @@ class TinyBatchSolver:
         self._check(self.lib.tiny_batch_mpc_run_sim(self._h, int(steps), window_advance, None if a is None else _fp(a), _fp(u0), None if xt is None else _fp(xt)))
         return u0, xt
 
+    def mpc_run_log(self, steps: int, window_advance: int = 0, w=None, record_x: bool = False) -> dict:
+        """tiny_batch_mpc_run_log: mpc_run_sim with the per-step solver log.  Returns a dict: u0 (steps, B, nu), x (steps, B, nx) or None, and iter,
+        status (steps, B) int32 — row k is what get_status() returns after MPC step k (status 1 solved, 11 max_iter reached).  The log does not make
+        the run simulated: without a plant, w and record_x it is the nominal run, on the kernel closed_loop_kernel_name() names."""
+        n = max(int(steps), 0)
+        a = None
+        if w is not None:
+            a = _f32(w); assert a.shape == (n, self.B, self.nx), a.shape
+        u0 = np.zeros((n, self.B, self.nu), np.float32)
+        xt = np.zeros((n, self.B, self.nx), np.float32) if record_x else None
+        it, st = np.zeros((n, self.B), np.int32), np.zeros((n, self.B), np.int32)
+        ip = C.POINTER(C.c_int)
+        self._check(self.lib.tiny_batch_mpc_run_log(self._h, int(steps), window_advance, None if a is None else _fp(a), _fp(u0), None if xt is None else _fp(xt),
+                                                    it.ctypes.data_as(ip), st.ctypes.data_as(ip)))
+        return {"u0": u0, "x": xt, "iter": it, "status": st}
+
     def get_x0(self):
         out = np.empty((self.B, self.nx), np.float32)
         self._check(self.lib.tiny_batch_get_x0(self._h, _fp(out)))
@@ -767,6 +785,21 @@ class TinyBatchSolver64:
         self._check(self.lib.tiny_batch64_mpc_run_sim(self._h, int(steps), int(window_advance), None if a is None else self._dp(a), self._dp(u0),
                                                       None if xt is None else self._dp(xt)))
         return u0, xt
+
+    def mpc_run_log(self, steps: int, window_advance: int = 0, w=None, record_x: bool = False) -> dict:
+        """tiny_batch64_mpc_run_log: mpc_run_sim with the per-step solver log.  Returns a dict: u0 (steps, B, nu), x (steps, B, nx) or None, and iter,
+        status (steps, B) int32 — row k is what get_status() returns after MPC step k.  The log does not make the run simulated."""
+        n = max(int(steps), 0)
+        a = None
+        if w is not None:
+            a = np.ascontiguousarray(w, np.float64); assert a.shape == (n, self.B, self.nx), a.shape
+        u0 = np.zeros((n, self.B, self.nu), np.float64)
+        xt = np.zeros((n, self.B, self.nx), np.float64) if record_x else None
+        it, st = np.zeros((n, self.B), np.int32), np.zeros((n, self.B), np.int32)
+        ip = C.POINTER(C.c_int)
+        self._check(self.lib.tiny_batch64_mpc_run_log(self._h, int(steps), int(window_advance), None if a is None else self._dp(a), self._dp(u0),
+                                                      None if xt is None else self._dp(xt), it.ctypes.data_as(ip), st.ctypes.data_as(ip)))
+        return {"u0": u0, "x": xt, "iter": it, "status": st}
 
     # -- per-instance models (tiny_batch64_set_models) ------------------------------------------------
     def set_models(self, models: dict):

@@ -8,8 +8,9 @@
 // The controller is the 20 Hz quadrotor's (one cache for the batch, the problem data file of quadrotor_tracking_batched.cpp).  Every instance
 // gets its own plant around that model — the columns of Bdyn scaled by 0.9 ... 1.1 (mass and motor gain), the non-zero entries of Adyn by
 // 0.98 ... 1.02 — and a random disturbance on the velocities at every step.  All instances track the y_axis_line trajectory from the same
-// start; the whole closed loop is ONE call (tiny_batch_mpc_run_sim: on the 16-lane kernel one launch), which returns the state trajectory, and
-// the study prints the mean and the worst final tracking error over the plants.
+// start; the whole closed loop is ONE call (tiny_batch_mpc_run_log: on the 16-lane kernel one launch), which returns the state trajectory and
+// iter / status of every solve, and the study prints the mean and the worst final tracking error over the plants and, per step, how many
+// instances returned unsolved.
 #include "tinympc_batch.h"
 
 #include <algorithm>
@@ -106,7 +107,20 @@ int main(int argc, char **argv)
                 tiny_batch_closed_loop_kernel_name(tb), B, tiny_batch_plant_mode(tb), steps);
 
     std::vector<float> xs((size_t)steps * B * NX);
-    CHECK(tiny_batch_mpc_run_sim(tb, steps, /*window_advance=*/1, w.data(), /*u0_traj=*/nullptr, xs.data()));
+    std::vector<int> iters((size_t)steps * B), status((size_t)steps * B);
+    CHECK(tiny_batch_mpc_run_log(tb, steps, /*window_advance=*/1, w.data(), /*u0_traj=*/nullptr, xs.data(), iters.data(), status.data()));
+
+    // the per-step solver log: a trajectory is to be trusted only where its solves converged within max_iter
+    for (int k : {0, steps / 2, steps - 1})
+    {
+        int unsolved = 0, most = 0;
+        for (int b = 0; b < B; b++)
+        {
+            unsolved += status[(size_t)k * B + b] == TINY_STATUS_UNSOLVED;
+            most = std::max(most, iters[(size_t)k * B + b]);
+        }
+        std::printf("step %3d: %d of %d instances unsolved, at most %d iterations\n", k, unsolved, B, most);
+    }
 
     // row k of the state trajectory is the state after step k: it is compared with row k + 1 of the table
     for (int k : {0, steps / 2, steps - 1})

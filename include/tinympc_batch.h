@@ -213,6 +213,18 @@ extern "C"
      * them between calls and re-allocates one only when its size (steps) changes, so a loop of equal calls on a replayed kernel replays ONE
      * captured graph; alternating step counts re-captures it. */
     int tiny_batch_mpc_run_sim(TinyBatch *tb, int steps, int window_advance, const float *w, float *u0_traj, float *x_traj);
+    /* The per-step solver log of a run: two int arrays [steps][batch]; row k holds work.iter and work.status of every instance after the solve of MPC
+     * step k — what a step-by-step loop reads with tiny_batch_get_status after step k (status: 1 solved, 11 max_iter reached).  iter_log / status_log
+     * and every other array may be NULL; with both logs NULL the call is tiny_batch_mpc_run_sim_async / _sim, and every tiny_batch_mpc_run_* is this call
+     * with NULL logs.  A log does not make a run simulated and picks no kernel (tiny_batch_closed_loop_kernel_name() does not change): results are
+     * bitwise those of the same run without it.  steps == 1 is served.  The 16-lane and quad-lane on-chip loops store the rows at the step boundary, beside
+     * u0_traj; every replayed kernel copies iter[] / status[] behind each solve inside the captured graph (the two pointers are in its signature).  The
+     * matrix-core kernel's on-chip loop and the 16-lane loops with per-instance models do not log: a run that asks for a log there is replayed on the
+     * same kernel step by step, with the same bits.  The blocking form keeps its device buffers on the handle as tiny_batch_mpc_run_sim does: a loop of equal calls replays one graph. */
+    int tiny_batch_mpc_run_log_async(TinyBatch *tb, int steps, int window_advance, const float *d_w, float *d_u0_traj, float *d_x_traj,
+                                     int *d_iter_log, int *d_status_log); /* device pointers, any may be NULL */
+    int tiny_batch_mpc_run_log(TinyBatch *tb, int steps, int window_advance, const float *w, float *u0_traj, float *x_traj,
+                               int *iter_log, int *status_log);           /* host arrays, blocking */
 
     /* ---- measurement ------------------------------------------------------------------------- */
     /* When enabled, every solve records hipEvents around its kernel launches on the stream. */

@@ -113,6 +113,13 @@ extern "C"
     int tiny_batch64_mpc_step_sim(TinyBatch64 *tb, const double *w /*[batch][nx] or NULL*/);
     int tiny_batch64_mpc_run_sim(TinyBatch64 *tb, int steps, int window_advance, const double *w /*[steps][batch][nx] or NULL*/,
                                  double *u0_traj /*[steps][batch][nu] or NULL*/, double *x_traj /*[steps][batch][nx] or NULL*/);
+    /* tiny_batch64_mpc_run_sim with the per-step solver log: row k of iter_log / status_log ([steps][batch] ints, either may be NULL) holds work.iter and
+     * work.status of every instance after the solve of step k, as tiny_batch64_get_status would return them there.  A log does not make a run simulated
+     * and picks no kernel; with both NULL the call is tiny_batch64_mpc_run_sim.  A run that asks for a log is enqueued as the launch sequence — the
+     * solve kernel tiny_batch64_kernel_name() names, per step, with iter[] / status[] copied behind each solve — also where the run without a log is ONE
+     * launch: the on-chip loops do not log.  tiny_batch64_closed_loop_kernel_name, which knows the handle alone, does not change. */
+    int tiny_batch64_mpc_run_log(TinyBatch64 *tb, int steps, int window_advance, const double *w, double *u0_traj, double *x_traj,
+                                 int *iter_log /*[steps][batch] or NULL*/, int *status_log /*[steps][batch] or NULL*/);
 
     /* Per-instance models (the float library's tiny_batch_set_models family, in double): every instance its own TinyCache{rho, Kinf, Pinf, Quu_inv,
      * AmBKt} (types.hpp:26-34) and its own Adyn, Bdyn, Q (types.hpp:82-85), each array [batch][...] with every instance's matrix column-major.  This
