@@ -256,24 +256,20 @@ constexpr const KernelTraits &traits(Kernel k) { return kKernelTraits[(int)k]; }
 
 Geo geo(const TinyBatch *tb) { return Geo{tb->nx, tb->nu, tb->N, tb->NXC, tb->NUC, tb->rw}; }
 
-// The hipGraph cached by tiny_batch_mpc_run_traj_async bakes in every kernel ARGUMENT of its launches (RowParams /
-// SolveParams are passed by value): rho, tolerances, bound flags, array pointers and strides, window advance.  Anything
-// that can change one of them drops the graph; the next mpc_run captures a fresh one.
-void invalidate_graph(TinyBatch *tb)
-{
-    if (tb->graph_exec)
-    {
-        (void)hipSetDevice(tb->device);
-        (void)hipStreamSynchronize(tb->stream); // a replay may still be in flight
-        (void)hipGraphExecDestroy(tb->graph_exec);
-        tb->graph_exec = nullptr;
-    }
-    tb->graph_sig.clear();
-}
-
 int set_device(TinyBatch *tb)
 {
     HIP_TRY(hipSetDevice(tb->device));
+    return 0;
+}
+
+// a handle left on the null stream gets a stream of its own
+int leave_null_stream(TinyBatch *tb)
+{
+    if (tb->stream) return 0;
+    TRY(set_device(tb));
+    HIP_TRY(hipStreamSynchronize(nullptr)); // work already queued on the null stream (uploads) comes first
+    if (!tb->own_stream) HIP_TRY(hipStreamCreateWithFlags(&tb->own_stream, hipStreamNonBlocking));
+    tb->stream = tb->own_stream;
     return 0;
 }
 
@@ -743,29 +739,6 @@ bool tile16_auto_size(const TinyBatch *tb) { return dispatch_effective(tb) == 1 
 constexpr int kTile16ClosedLoopPerCu = 160;
 bool tile16_closed_loop_size(const TinyBatch *tb) { return tb->batch >= kTile16ClosedLoopPerCu * tb->n_cu; }
 
-// fp16 storage: bring the duals pair to the width the coming launch implements.  Under tiny_batch_set_storage(tb, 16) fp32 duals are a
-// PREFERENCE (the register-resident 16-lane and quad kernels keep them — KernelTraits::fp32_duals — every other kernel — streamed state, per-instance
-// bounds under fp16, the optional terms, the six single-function kernels — stores binary16 duals): the array is converted in place of being refused.
-// An explicit tiny_batch_set_storage_ex(tb, 16, 32) stays a requirement (the caller is told when a kernel cannot honour it).
-int settle_dual_width(TinyBatch *tb, bool kernel_keeps_fp32_duals)
-{
-    if (!tb->h16 || tb->dual32_forced) return 0;
-    const bool want32 = tb->dual32_pref && kernel_keeps_fp32_duals;
-    if (tb->dual32 == want32) return 0;
-    if (tb->layout == LAYOUT_ROW && tb->pair[5])
-    {
-        float *nw = nullptr;
-        TRY(dev_alloc_zero(&nw, want32 ? tb->pair_floats : (tb->pair_floats + 1) / 2));
-        HIP_TRY(launch_dual_width(tb->pair[5], nw, (long long)tb->pair_floats, want32 ? 1 : 0, tb->stream));
-        HIP_TRY(hipStreamSynchronize(tb->stream));
-        (void)guarded_free(tb->pair[5]);
-        tb->pair[5] = nw;
-    }
-    tb->dual32 = want32;
-    invalidate_graph(tb); // the array pointer is a kernel argument
-    return 0;
-}
-
 // admm_tile16.hip needs fp32 storage, a reference it does not have to keep resident (a window of a trajectory table that
 // fits its LDS share, or one shared reference) and — checked by the caller — batch-shared bounds and no optional terms
 // Round 4: per-instance bounds and a per-instance reference are served by the PI instantiations (rows fetched by LDS-DMA into per-wave rings,
@@ -795,11 +768,19 @@ bool tile16_pi_auto(const TinyBatch *tb) { return !tb->order_dev && tile16_auto_
 bool zero_ties_hand_over(const TinyBatch *tb) { return tb->zero_ties && tb->variant != VAR_ROW_FAST; }
 // A closed-loop run is simulated when a plant is set or the call passes a disturbance or asks for the state trajectory: its on-chip loop exists on the
 // 16-lane kernel only (admm_rowsim.hip), so tile16 hands such a run over as it does one with per-instance tables; the quad kernel's is replayed.
-// `sim` travels beside `closed_loop` from the call down to here (a question about the handle alone, such as the closed-loop kernel's name, knows the plant only)
-bool tile16_applies(const TinyBatch *tb, bool closed_loop, bool sim = false)
+// What a call asks of the handle.  Solve: one solve per launch (tiny_batch_solve_*, the step functions, a run of ONE step); Run: tiny_batch_mpc_run_*(steps > 1).
+// sim: the run is simulated (a question about the handle alone, such as the closed-loop kernel's name, knows the plant only); logs: it asks for the per-step log
+struct Call
 {
-    if (!tb->tile16_ok || tb->h16 || zero_ties_hand_over(tb) || (closed_loop && sim)) return false;
-    if (tile16_per_instance(tb)) return !closed_loop && tile16_pi_plan(tb).fits;
+    enum Kind { Solve, Run } kind;
+    bool sim, logs;
+    bool run() const { return kind == Run; }
+};
+constexpr Call kLoneSolve{Call::Solve, false, false};
+bool tile16_applies(const TinyBatch *tb, const Call &call)
+{
+    if (!tb->tile16_ok || tb->h16 || zero_ties_hand_over(tb) || (call.run() && call.sim)) return false;
+    if (tile16_per_instance(tb)) return !call.run() && tile16_pi_plan(tb).fits;
     if (tb->xref_mode == 1) return tb->table_rows <= tile16_max_table_rows();
     return true;
 }
@@ -819,7 +800,9 @@ bool tile48_pays(int batch, int n_cu)
     return rounds_t * kTileRoundInWaveRounds <= rounds_w * 0.93;
 }
 
-// What one solve launches: resolved ONCE per call by resolve_plan(), read by everything that names, prepares, orders or launches the kernel.
+// What a call launches: resolved ONCE per call by resolve_plan(), read by everything that names, prepares, orders or launches the kernel.  loop: None, the call is
+// one solve; OnChip, all the steps of a run inside one launch; Replay, solve + plant kernel per step, captured once into a hipGraph and replayed
+enum class Loop { None, Replay, OnChip };
 struct KernelPlan
 {
     Kernel kernel = Kernel::Rowlane;
@@ -827,10 +810,12 @@ struct KernelPlan
     bool pm = false;     // per-instance models (the ",pm" instantiations of the 16-lane, the two wave and the run-time-dimension kernel)
     bool pi = false;     // tile16 with per-instance bounds / reference (admm_tile16_pi.hip)
     Tile16Pi pi_tables{}; // ... and which of its tables go through the rings
+    Loop loop = Loop::None;
+    bool sim{};          // the call's: an on-chip loop then takes the SIM instantiations (admm_rowsim.hip)
 };
 
 // the row / wave kernel a row variant launches for this handle (resolve_plan's second half; `forced`: tiny_batch_set_row_kernel)
-Kernel row_kernel_for(const TinyBatch *tb, bool closed_loop, bool sim = false)
+Kernel row_kernel_for(const TinyBatch *tb, const Call &call)
 {
     const std::optional<Kernel> forced = tb->row_family_forced;
     // one wavefront per instance: state on chip where the horizon fits (admm_waveres.hip), else streamed through HBM (admm_wave.hip)
@@ -846,12 +831,12 @@ Kernel row_kernel_for(const TinyBatch *tb, bool closed_loop, bool sim = false)
     // the optional terms (Uref, coeff_d2p): on the unrolled register-resident kernel since round 4 (fp32 storage, batch-shared bounds, one solve per
     // launch); every other combination — fp16 storage, per-instance bounds, a closed-loop run, another forced family — on the streaming row kernel
     const bool optional_terms = tb->en_uref || tb->en_d2p;
-    if (optional_terms && tb->row_dims_ok && !tb->h16 && bounds_all_shared(tb) && !closed_loop && (!forced || forced == Kernel::Rowlane))
+    if (optional_terms && tb->row_dims_ok && !tb->h16 && bounds_all_shared(tb) && !call.run() && (!forced || forced == Kernel::Rowlane))
         return Kernel::Rowlane;
     if (!bounds_all_shared(tb))
     {
         if (optional_terms) return Kernel::Rowstream;
-        if (tile16_applies(tb, closed_loop, sim) && (forced == Kernel::Tile16 || (!forced && tile16_pi_auto(tb)))) return Kernel::Tile16;
+        if (tile16_applies(tb, call) && (forced == Kernel::Tile16 || (!forced && tile16_pi_auto(tb)))) return Kernel::Tile16;
         const std::optional<Kernel> ff = forced == Kernel::Tile16 ? std::nullopt : forced; // tile16 asked for but not applicable (closed-loop run): like auto
         if (tb->row_dims_ok && !tb->h16 && (!ff || ff == Kernel::Rowlane)) return Kernel::Rowlane;
         if (tb->rowloop_ok && (!ff || ff == Kernel::Rowloop)) return Kernel::Rowloop; // one step ahead from global memory
@@ -861,7 +846,7 @@ Kernel row_kernel_for(const TinyBatch *tb, bool closed_loop, bool sim = false)
     // sixteen instances per wave, products on the matrix cores (admm_tile16.hip): on request only; needs fp32 storage and
     // a reference it does not have to keep resident (window of a table, or one shared reference)
     if (forced == Kernel::Tile16)
-        return tile16_applies(tb, closed_loop, sim) ? Kernel::Tile16 : (tb->row_dims_ok ? Kernel::Rowlane : (tb->rowloop_ok ? Kernel::Rowloop : Kernel::Rowstream));
+        return tile16_applies(tb, call) ? Kernel::Tile16 : (tb->row_dims_ok ? Kernel::Rowlane : (tb->rowloop_ok ? Kernel::Rowloop : Kernel::Rowstream));
     if (forced) return *forced;
     if (tb->quad_ok) return Kernel::Quadlane; // four lanes per instance (admm_quadlane.hip): nx = 4, nu = 1
     // auto (round 3): sixteen instances per wave on the matrix cores where the launch is at least two rounds deep for its one
@@ -872,26 +857,33 @@ Kernel row_kernel_for(const TinyBatch *tb, bool closed_loop, bool sim = false)
     // (round 4: tile16's MPC loop stays on chip too — tiny_batch_set_row_kernel(tb, 5) — but the warm-started solves of a closed loop are short and
     //  uneven, and sixteen instances in lock step lose more there than the matrix cores gain: measured 1.02 ms per MPC step of 65 536 tracking
     //  instances against 0.97 ms on the 16-lane kernel, so the automatic choice of a closed-loop run stays with the latter)
-    if (tile16_applies(tb, closed_loop, sim) && !tb->order_dev && (closed_loop ? tile16_closed_loop_size(tb) : tile16_auto_size(tb))) return Kernel::Tile16;
+    if (tile16_applies(tb, call) && !tb->order_dev && (call.run() ? tile16_closed_loop_size(tb) : tile16_auto_size(tb))) return Kernel::Tile16;
     if (tb->row_dims_ok) return Kernel::Rowlane; // unrolled register-resident (fastest, one instantiation per (nx, nu, N))
     if (tb->rowloop_ok) return Kernel::Rowloop;  // rolled-loop register-resident (any N <= 64)
     return Kernel::Rowstream;                    // any N with the state in HBM
 }
 
-// the plan of a resolved variant v (not VAR_AUTO) whose row variants launch `row`
-int plan_of(const TinyBatch *tb, int v, Kernel row, KernelPlan *out)
+// the plan of a resolved variant v (not VAR_AUTO) whose row variants launch `row` (resolve_plan's last step, called from nowhere else)
+int plan_of(const TinyBatch *tb, const Call &call, int v, Kernel row, KernelPlan *out)
 {
-    out->kernel = v == VAR_STREAM ? Kernel::Stream : (v == VAR_GENERIC ? Kernel::Generic : row);
+    const Kernel k = out->kernel = v == VAR_STREAM ? Kernel::Stream : (v == VAR_GENERIC ? Kernel::Generic : row);
     out->exact = v == VAR_ROW_EXACT || v == VAR_GENERIC;
     out->pm = tb->pm;
-    out->pi = out->kernel == Kernel::Tile16 && tile16_per_instance(tb);
+    out->pi = k == Kernel::Tile16 && tile16_per_instance(tb);
     if (out->pi) out->pi_tables = tile16_pi_plan(tb);
+    out->sim = call.sim;
+    // A run of several steps stays on chip where the kernel has the loop, under fp32 storage and batch-shared bounds; simulated, on the 16-lane kernel only
+    // (admm_rowsim.hip); and not with a log on the matrix-core kernel or with per-instance models: their largest instantiations sit at the register allocator's
+    // cliff, and the log's store moved their pinned scratch whichever way it was written — such a run replays the same kernel, with the same bits
+    const bool on_chip = traits(k).onchip_mpc && !tb->h16 && bounds_all_shared(tb) && (!call.sim || k == Kernel::Rowlane) &&
+                         !(call.logs && (k == Kernel::Tile16 || out->pm));
+    out->loop = !call.run() ? Loop::None : (on_chip ? Loop::OnChip : Loop::Replay);
     return 0;
 }
 
-// THE policy: which kernel serves this handle, in which arithmetic.  `closed_loop`: the call is a tiny_batch_mpc_run_*(steps > 1) — the automatic choice
-// then keeps the kernel with the on-chip MPC loop.  Reads the handle and changes nothing; the answer depends on rows_vary, which prepare_inputs() fills.
-int resolve_plan(const TinyBatch *tb, bool closed_loop, KernelPlan *out, bool sim = false)
+// THE policy: which kernel serves this call on this handle, in which arithmetic, and how a run loops.  Reads the handle and changes nothing; the answer
+// depends on rows_vary, which prepare_inputs() fills.
+int resolve_plan(const TinyBatch *tb, const Call &call, KernelPlan *out)
 {
     int v = tb->variant;
     if (tb->pm)
@@ -913,7 +905,7 @@ int resolve_plan(const TinyBatch *tb, bool closed_loop, KernelPlan *out, bool si
         {
             if (v == VAR_ROW_FAST && tb->row_family_forced != Kernel::Waveres)
                 return fail(TINY_BATCH_EUNSUPPORTED, "fma arithmetic for 16 < nx + nu <= 64 needs the state-on-chip wave kernel (N <= 50); beyond that it is the streaming MFMA kernel (variant 1)");
-            return plan_of(tb, v == VAR_AUTO ? VAR_ROW_EXACT : v, *tb->row_family_forced, out);
+            return plan_of(tb, call, v == VAR_AUTO ? VAR_ROW_EXACT : v, *tb->row_family_forced, out);
         }
         if (v == VAR_AUTO)
         {
@@ -933,13 +925,13 @@ int resolve_plan(const TinyBatch *tb, bool closed_loop, KernelPlan *out, bool si
         }
         if (v == VAR_GENERIC && !tb->generic_ok)
             return fail(TINY_BATCH_EUNSUPPORTED, "the run-time-dimension exact kernel (variant 4) needs nx, nu each <= 4 or a multiple of 4 (nx=%d nu=%d)", tb->nx, tb->nu);
-        return plan_of(tb, v, Kernel::Rowlane, out);
+        return plan_of(tb, call, v, Kernel::Rowlane, out);
     }
     // row variants: register-resident kernel when (nx,nu,N) is instantiated, else the any-N row kernel with the state in HBM
     // per-instance bounds: the streaming row kernel and the wave kernel read them per instance; the register-resident
     // kernels stage ONE table in LDS and need batch-shared bounds
     const bool row_ok = tb->row_dims_ok || tb->rowmath_ok || tb->wave_ok;
-    const Kernel row = row_kernel_for(tb, closed_loop, sim);
+    const Kernel row = row_kernel_for(tb, call);
     if (v == VAR_ROW_FAST && tb->wave_ok && row != Kernel::Waveres && row != Kernel::Tile48)
         return fail(TINY_BATCH_EUNSUPPORTED, "fma arithmetic for 16 < nx + nu <= 64 needs the state-on-chip wave kernel (N <= 50); beyond that it is the streaming MFMA kernel (variant 1)");
     if (v == VAR_AUTO)
@@ -965,7 +957,7 @@ int resolve_plan(const TinyBatch *tb, bool closed_loop, KernelPlan *out, bool si
         return fail(TINY_BATCH_EUNSUPPORTED, "no streaming kernel instantiation for nx=%d nu=%d", tb->nx, tb->nu);
     if (v == VAR_STREAM && tb->h16)
         return fail(TINY_BATCH_EUNSUPPORTED, "fp16 storage is implemented by the row kernels only (nx + nu <= 16)");
-    return plan_of(tb, v, row, out);
+    return plan_of(tb, call, v, row, out);
 }
 
 // the name tiny_batch_kernel_name() reports: "<family><nx,nu[,N],arithmetic[,h16 | ,h16d | ,pi | ,pm]>"; the streaming kernel is named by its chunk counts
@@ -986,16 +978,95 @@ std::string kernel_name(const TinyBatch *tb, const KernelPlan &pl)
     return nm;
 }
 
-// the name of the kernel a lone solve (closed_loop = false) or a closed-loop run of several steps launches; "unsupported" where no kernel would run.
+// the name of the kernel a lone solve or a closed-loop run of several steps launches; "unsupported" where no kernel would run.
 // One buffer per question and handle: the pointer holds until the same question is asked of the same handle again
-const char *plan_name(TinyBatch *tb, bool closed_loop, bool sim = false)
+const char *plan_name(TinyBatch *tb, const Call &call)
 {
-    std::string &name = tb->name_buf[closed_loop ? 1 : 0];
+    std::string &name = tb->name_buf[call.run() ? 1 : 0];
     const std::string keep = g_err;
     KernelPlan pl;
-    name = resolve_plan(tb, closed_loop, &pl, sim) ? "unsupported" : kernel_name(tb, pl);
+    name = resolve_plan(tb, call, &pl) ? "unsupported" : kernel_name(tb, pl);
     g_err = keep;
     return name.c_str();
+}
+
+// A closed-loop run as the public call states it (tiny_batch_mpc_run_*): every pointer is DEVICE memory and may be NULL
+struct RunArgs
+{
+    const char *who; // the public call, for its messages
+    int steps, window_advance;
+    const float *d_w;               // [steps][B][nx] disturbance
+    float *d_u0_traj, *d_x_traj;    // [steps][B][nu] u.col(0) of every step; [steps][B][nx] the plant's state after every step
+    int *d_iter_log, *d_status_log; // [steps][B] the per-step solver log: row k = iter[] / status[] after the solve of MPC step k
+    bool from_reset = false;        // the run starts from a reset workspace (mpc_run_sim notes it before it materialises the zeros)
+    // the rows of MPC step k; log_row: iter[] / status[] as the solve before it left them (two device-to-device copies on the handle's stream: captured with the rest)
+    const float *w_at(const TinyBatch *tb, int k) const { return d_w ? d_w + (size_t)k * tb->batch * tb->nx : nullptr; }
+    float *x_at(const TinyBatch *tb, int k) const { return d_x_traj ? d_x_traj + (size_t)k * tb->batch * tb->nx : nullptr; }
+    float *u0_at(const TinyBatch *tb, int k) const { return d_u0_traj ? d_u0_traj + (size_t)k * tb->batch * tb->nu : nullptr; }
+    hipError_t log_row(const TinyBatch *tb, int k) const
+    {
+        const size_t o = (size_t)k * tb->batch, bytes = (size_t)tb->batch * sizeof(int);
+        hipError_t e = hipSuccess;
+        if (d_iter_log) e = hipMemcpyAsync(d_iter_log + o, tb->iter, bytes, hipMemcpyDeviceToDevice, tb->stream);
+        if (e == hipSuccess && d_status_log) e = hipMemcpyAsync(d_status_log + o, tb->status, bytes, hipMemcpyDeviceToDevice, tb->stream);
+        return e;
+    }
+};
+
+// The hipGraph cached by tiny_batch_mpc_run_traj_async bakes in every kernel ARGUMENT of its launches (RowParams /
+// SolveParams are passed by value): rho, tolerances, bound flags, array pointers and strides, window advance.  Anything
+// that can change one of them drops the graph; the next mpc_run captures a fresh one.
+void invalidate_graph(TinyBatch *tb)
+{
+    if (tb->graph_exec)
+    {
+        (void)hipSetDevice(tb->device);
+        (void)hipStreamSynchronize(tb->stream); // a replay may still be in flight
+        (void)hipGraphExecDestroy(tb->graph_exec);
+        tb->graph_exec = nullptr;
+    }
+    tb->graph_sig.clear();
+}
+
+// ... and a run whose signature equals the cached graph's replays it.  The signature is complete (round 3) — rho, the shared / per-instance modes that set the
+// strides, the bound flags and the dispatch order are in it — so setters that only change buffer CONTENTS do not drop the graph: `set_xref; mpc_run(k)` in a loop
+// replays one captured graph
+std::string graph_signature(const TinyBatch *tb, const KernelPlan &pl, const RunArgs &run)
+{
+    char sig[768];
+    snprintf(sig, sizeof sig, "%d|%p|%p|%p|%p|%p|%p|%p|%p|%p|%d|%d|%d|%s|%d|%d|%g|%g|%d|%d|%p|%p|%p|%d|%p|%p|%p|%p|%d%d|%a|%d%d%d|%d%d|%d|%p|%p|%p|%d|%p|%p", tb->plant_mode, (void *)tb->plant_A,
+             (void *)tb->plant_B, (const void *)run.d_w, (void *)run.d_x_traj, (void *)tb->pm_src, (void *)tb->pm_row[0],
+             (void *)tb->pm_row[1], (void *)tb->pm_wave[0], (void *)tb->pm_wave[1], run.steps, run.window_advance, tb->variant, kernel_name(tb, pl).c_str(), tb->max_iter,
+             tb->check_termination, (double)tb->abs_pri_tol, (double)tb->abs_dua_tol, tb->xref_mode, tb->table_rows, (void *)tb->pair[0],
+             (void *)tb->arr[0], (void *)tb->r_bounds, (int)tb->h16, (void *)tb->stream, (void *)run.d_u0_traj, (void *)tb->r_xref,
+             (void *)tb->r_uref, (int)tb->en_uref, (int)tb->en_d2p, (double)tb->rho, (int)bounds_all_shared(tb),
+             (int)(tb->in_xref.set && tb->in_xref.shared), (int)(tb->in_uref.set && tb->in_uref.shared), tb->en_state_bound, tb->en_input_bound,
+             tb->dispatch_mode, (void *)tb->order_dev, (void *)tb->mats_exact, (void *)tb->xref_start, (int)tb->zero_ties,
+             (void *)run.d_iter_log, (void *)run.d_status_log);
+    return sig;
+}
+
+// fp16 storage: bring the duals pair to the width the coming launch implements.  Under tiny_batch_set_storage(tb, 16) fp32 duals are a
+// PREFERENCE (the register-resident 16-lane and quad kernels keep them — KernelTraits::fp32_duals — every other kernel — streamed state, per-instance
+// bounds under fp16, the optional terms, the six single-function kernels — stores binary16 duals): the array is converted in place of being refused.
+// An explicit tiny_batch_set_storage_ex(tb, 16, 32) stays a requirement (the caller is told when a kernel cannot honour it).
+int settle_dual_width(TinyBatch *tb, bool kernel_keeps_fp32_duals)
+{
+    if (!tb->h16 || tb->dual32_forced) return 0;
+    const bool want32 = tb->dual32_pref && kernel_keeps_fp32_duals;
+    if (tb->dual32 == want32) return 0;
+    if (tb->layout == LAYOUT_ROW && tb->pair[5])
+    {
+        float *nw = nullptr;
+        TRY(dev_alloc_zero(&nw, want32 ? tb->pair_floats : (tb->pair_floats + 1) / 2));
+        HIP_TRY(launch_dual_width(tb->pair[5], nw, (long long)tb->pair_floats, want32 ? 1 : 0, tb->stream));
+        HIP_TRY(hipStreamSynchronize(tb->stream));
+        (void)guarded_free(tb->pair[5]);
+        tb->pair[5] = nw;
+    }
+    tb->dual32 = want32;
+    invalidate_graph(tb); // the array pointer is a kernel argument
+    return 0;
 }
 
 void fill_row_params(TinyBatch *tb, RowParams &P, bool exact)
@@ -1023,7 +1094,7 @@ void fill_row_params(TinyBatch *tb, RowParams &P, bool exact)
     P.dual32 = (tb->h16 && tb->dual32) ? 1 : 0;
     P.inst_map = nullptr; // enqueue_dispatch_order sets it for the one launch that reads it
     P.exact_ties = tb->zero_ties ? 1 : 0;
-    P.iter_log = P.status_log = nullptr; // mpc_run_sim sets them for the on-chip closed loop
+    P.iter_log = P.status_log = nullptr; // enqueue_solve sets them for the on-chip closed loop
 }
 
 int check_optional_terms(const TinyBatch *tb)
@@ -1131,7 +1202,7 @@ int ensure_tile_map(TinyBatch *tb, const KernelPlan &pl)
 }
 
 // everything a solve needs that may allocate, copy or synchronise (not capturable in a hipGraph); *plan: what the solve launches
-int prepare_solve(TinyBatch *tb, bool closed_loop, KernelPlan *plan, bool sim = false)
+int prepare_solve(TinyBatch *tb, const Call &call, KernelPlan *plan)
 {
     if (!(tb->pm || (tb->have_cache && tb->have_dyn)) || !tb->have_settings)
         return fail(TINY_BATCH_ENOTREADY, "tiny_batch_solve: set_cache, set_dynamics (or set_models) and set_settings must be called first");
@@ -1148,7 +1219,7 @@ int prepare_solve(TinyBatch *tb, bool closed_loop, KernelPlan *plan, bool sim = 
     // differ only between tile16 and another kernel of the ROW layout, in the same arithmetic, under fp32 storage (rows_vary enters through the pi
     // tables' LDS fit alone, and fp16 storage excludes tile16), where settle_dual_width does nothing
     KernelPlan pl;
-    TRY(resolve_plan(tb, closed_loop, &pl, sim));
+    TRY(resolve_plan(tb, call, &pl));
     if (tb->pm) TRY(pack_models(tb, pl));
     else if (tb->gains_dirty) TRY(pack_gains(tb));
     // (whatever the mode says NOW: a launch sequence enqueued after one prepare_solve — the captured graph of tiny_batch_mpc_run_async — gains a history with its
@@ -1169,9 +1240,9 @@ int prepare_solve(TinyBatch *tb, bool closed_loop, KernelPlan *plan, bool sim = 
     // reset_workspace() is folded into the launch by every fused kernel: the register-resident ones start from zero registers,
     // the streaming ones (MFMA, rowstream, wavestream) read zeros in their first iteration and zero-fill p, d, v, z of such an
     // instance in their epilogue
-    if (inputs_rebuilt) TRY(resolve_plan(tb, closed_loop, plan, sim));
+    if (inputs_rebuilt) TRY(resolve_plan(tb, call, plan));
     else *plan = pl; // rows_vary did not move: the provisional plan is the final one
-    return closed_loop ? 0 : ensure_tile_map(tb, *plan);
+    return call.run() ? 0 : ensure_tile_map(tb, *plan); // (a run forms no tiles through the map)
 }
 
 void fill_solve_params(const TinyBatch *tb, SolveParams &P)
@@ -1242,7 +1313,7 @@ int enqueue_dispatch_order(TinyBatch *tb, const KernelPlan &pl, int run_steps, b
 
 // the ONE place that launches a solve kernel.  P: the row-layout arguments (the two TILE-layout kernels take theirs from fill_solve_params)
 // S: the on-chip loop of a simulated run (16-lane kernel only)
-hipError_t launch_kernel(const TinyBatch *tb, const KernelPlan &pl, RowParams &P, const SimParams *S = nullptr)
+hipError_t launch_kernel(const TinyBatch *tb, const KernelPlan &pl, RowParams &P, const SimParams *S)
 {
     const int nx = tb->nx, nu = tb->nu, N = tb->N;
     if (S && pl.kernel != Kernel::Rowlane) return hipErrorInvalidValue;
@@ -1291,42 +1362,48 @@ hipError_t launch_kernel(const TinyBatch *tb, const KernelPlan &pl, RowParams &P
     return hipErrorInvalidValue;
 }
 
-// the stream operations of one solve: dispatch order or counter reset + kernel launch (capturable)
-int enqueue_solve(TinyBatch *tb, const KernelPlan &pl, bool record_events)
+// the stream operations of one solve launch: dispatch order or counter reset + kernel launch (capturable).  run: the launch is the on-chip loop of that run
+// (Loop::OnChip; NULL for a lone solve and for each solve of a replayed run): it differs in what the kernel is told and in its dispatch order, and is never timed
+int enqueue_solve(TinyBatch *tb, const KernelPlan &pl, bool record_events, const RunArgs *run)
 {
     const KernelTraits &t = traits(pl.kernel);
     RowParams P;
+    SimParams S;
     if (t.layout == LAYOUT_ROW)
     {
         fill_row_params(tb, P, pl.exact);
-        const int applied = enqueue_dispatch_order(tb, pl, 1, false, P);
+        if (run)
+        {
+            P.mpc_steps = run->steps; P.window_advance = run->window_advance; P.u0_traj = run->d_u0_traj;
+            P.iter_log = run->d_iter_log; P.status_log = run->d_status_log;
+            if (tb->plant_mode) { S.plant = tb->plant_rows; S.plant_stride = tb->plant_mode == 2 ? (unsigned)plant_row_floats(tb->nx, tb->nu) : 0u; }
+            S.w = run->d_w; S.x_traj = run->d_x_traj;
+        }
+        const int applied = enqueue_dispatch_order(tb, pl, run ? run->steps : 1, run && run->from_reset, P);
         if (applied < 0) return applied;
         tb->last_dispatch = applied;
-        tb->last_grouped = P.inst_map != nullptr;
     }
-    else
-    {
-        HIP_TRY(hipMemsetAsync(tb->n_unsolved, 0, 2 * sizeof(int), tb->stream)); // [0] unsolved count
-        tb->last_grouped = false;
-    }
+    else HIP_TRY(hipMemsetAsync(tb->n_unsolved, 0, 2 * sizeof(int), tb->stream)); // [0] unsolved count
+    tb->last_grouped = t.layout == LAYOUT_ROW && P.inst_map != nullptr; // (never in a run: the map forms the tiles of a lone solve only)
     if (record_events) HIP_TRY(hipEventRecord(tb->ev0, tb->stream)); // the events bracket the solve kernel itself
-    if (t.layout == LAYOUT_ROW && P.dual32 && !t.fp32_duals)
+    if (t.layout == LAYOUT_ROW && P.dual32 && !t.fp32_duals) // (an on-chip run never meets this: fp32 storage only)
         return fail(TINY_BATCH_EUNSUPPORTED, "fp16 storage with fp32 duals runs on the register-resident 16-lane and quad kernels only "
                                              "(batch-shared bounds, no optional terms, no forced row kernel)");
-    const hipError_t e = launch_kernel(tb, pl, P);
+    // (tile16 gets tb->tile_queue in a run like in a lone solve: its two-ended queue is off whenever mpc_steps > 1 — t16_tail_stride returns 0 — so the setting changes nothing there)
+    const hipError_t e = launch_kernel(tb, pl, P, run && pl.sim ? &S : nullptr);
     if (e != hipSuccess) return fail(TINY_BATCH_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
     if (record_events)
     {
         HIP_TRY(hipEventRecord(tb->ev1, tb->stream));
         tb->ev_valid = true;
     }
-    if (tb->max_iter > 0) tb->duals_zero_pending = tb->cold_pending = false; // consumed by the kernel's first iteration
-    if (tb->max_iter > 0) tb->iter_history = true;                            // iter[] now holds this launch's counts
+    // consumed by the kernel's first iteration; iter[] now holds this launch's counts (a run's: its last solve's)
+    if (tb->max_iter > 0) { tb->duals_zero_pending = tb->cold_pending = false; tb->iter_history = true; }
     return 0;
 }
 
 // d_w / d_x_traj: this step's [batch][nx] rows (NULL: no disturbance / not recorded).  With neither and no plant set: the launch it has always been
-int enqueue_plant_step(TinyBatch *tb, int window_advance, const float *d_w = nullptr, float *d_x_traj = nullptr)
+int enqueue_plant_step(TinyBatch *tb, int window_advance, const float *d_w, float *d_x_traj)
 {
     if (tb->xref_mode == 1 && window_advance) tb->tile_map_dirty = true; // the kernel slides xref_start[]
     // priority: the plant, then the per-instance model record, then the shared model (launch_plant_step picks the kernel by what is set here)
@@ -1921,8 +1998,8 @@ int tiny_batch_solve_async(TinyBatch *tb)
 {
     CHECK_TB(tb);
     KernelPlan pl;
-    TRY(prepare_solve(tb, false, &pl));
-    return enqueue_solve(tb, pl, tb->timing);
+    TRY(prepare_solve(tb, kLoneSolve, &pl));
+    return enqueue_solve(tb, pl, tb->timing, nullptr);
 }
 
 int tiny_batch_wait(TinyBatch *tb, int *n_unsolved)
@@ -1959,13 +2036,7 @@ int tiny_batch_group_solve(TinyBatch **tbs, int n, int *n_unsolved)
     for (int i = 0; i < n; i++)
     {
         TinyBatch *tb = tbs[i];
-        if (!tb->stream) // the null stream would serialise the group
-        {
-            TRY(set_device(tb));
-            HIP_TRY(hipStreamSynchronize(nullptr)); // work already queued on the null stream (uploads) comes first
-            if (!tb->own_stream) HIP_TRY(hipStreamCreateWithFlags(&tb->own_stream, hipStreamNonBlocking));
-            tb->stream = tb->own_stream;
-        }
+        TRY(leave_null_stream(tb)); // the null stream would serialise the group
         TRY(tiny_batch_solve_async(tb));
     }
     int total = 0;
@@ -2155,162 +2226,53 @@ int tiny_batch_get_u0_device(TinyBatch *tb, float *d_u0)
     return launch_unpack(tb, work_ptr(tb, TINY_ARR_U), d_u0, tb->layout, 1, tb->batch, 0, 1);
 }
 
-namespace
+namespace // closed loop: tiny_batch_mpc_step_* (solve + plant step, one MPC step per call) and tiny_batch_mpc_run_* (`steps` of them back to back)
 {
-// who: the public call, for its messages
+// what the step and the run calls ask alike.  who: the public call, what: "mpc_step" / "mpc_run", for the messages (no handle has nx > 64: tiny_batch_create)
+int check_loop_args(const TinyBatch *tb, const char *who, const char *what, int window_advance)
+{
+    if (window_advance < 0) return fail(TINY_BATCH_EINVAL, "%s: window_advance must be >= 0 (got %d): the window gather clamps at the last table row only", who, window_advance);
+    if (tb->nx > 64) return fail(TINY_BATCH_EUNSUPPORTED, "%s supports nx <= 64", what);
+    return 0;
+}
+
 int mpc_step_sim(TinyBatch *tb, const char *who, int window_advance, const float *d_w)
 {
-    if (tb->nx > 64) return fail(TINY_BATCH_EUNSUPPORTED, "mpc_step supports nx <= 64");
-    if (window_advance < 0) return fail(TINY_BATCH_EINVAL, "%s: window_advance must be >= 0 (got %d): the window gather clamps at the last table row only", who, window_advance);
-    // x.col(0) already holds x0 (set_x0 / previous plant step); reset duals, solve, then simulate forward.
-    tb->duals_zero_pending = true;
+    TRY(check_loop_args(tb, who, "mpc_step", window_advance));
+    tb->duals_zero_pending = true; // x.col(0) already holds x0 (set_x0 / previous plant step); reset duals, solve, then simulate forward
     TRY(tiny_batch_solve_async(tb));
-    return enqueue_plant_step(tb, window_advance, d_w);
-}
-} // namespace
-
-int tiny_batch_mpc_step_sim_async(TinyBatch *tb, int window_advance, const float *d_w)
-{
-    CHECK_TB(tb);
-    return mpc_step_sim(tb, "tiny_batch_mpc_step_sim_async", window_advance, d_w);
+    return enqueue_plant_step(tb, window_advance, d_w, nullptr);
 }
 
-int tiny_batch_mpc_step_async(TinyBatch *tb, int window_advance)
+// Loop::OnChip: ONE launch runs all the steps, the state never leaves registers / LDS between solves; the host adds what the last step leaves to it
+int run_on_chip(TinyBatch *tb, const KernelPlan &pl, const RunArgs &run)
 {
-    CHECK_TB(tb);
-    return mpc_step_sim(tb, "tiny_batch_mpc_step_async", window_advance, nullptr);
+    const int last = run.steps - 1;
+    TRY(enqueue_solve(tb, pl, false, &run));
+    if (run.d_u0_traj) TRY(launch_unpack(tb, work_ptr(tb, TINY_ARR_U), run.u0_at(tb, last), tb->layout, 1, tb->batch, 0, 1));
+    HIP_TRY(run.log_row(tb, last)); // the last row of the logs is the host's too: iter[] / status[] as the kernel's live-out left them
+    return enqueue_plant_step(tb, run.window_advance, run.w_at(tb, last), run.x_at(tb, last)); // ... and so is the last plant step: the same plant, its own rows
 }
 
-// `steps` closed-loop MPC steps back to back; d_u0_traj (device, [steps][B][nu], may be NULL) receives u.col(0) of every
-// step.  Two implementations with identical results:
-//  * on chip (the unrolled row kernel and the quad kernel, fp32 storage): ONE launch runs all the steps, the state never leaves registers/LDS
-//    between solves (admm_rowlane.hip, MPC = true); the host only adds the plant step of the last solve;
-//  * otherwise the launch sequence (counter reset, solve kernel, plant kernel) x steps is captured ONCE into a hipGraph and
-//    replayed, which removes the per-launch overhead that dominates small batches with short warm-started solves.
-namespace
+// Loop::Replay, and a run of one step: the launch sequence (dispatch order or counter reset, solve kernel, u.col(0), log rows, plant kernel) x steps is captured
+// ONCE into a hipGraph and replayed, which removes the per-launch overhead that dominates small batches with short warm-started solves
+int run_replayed(TinyBatch *tb, const KernelPlan &pl, const RunArgs &run)
 {
-int mpc_run_sim(TinyBatch *tb, const char *who, int steps, int window_advance, const float *d_w, float *d_u0_traj, float *d_x_traj, int *d_iter_log = nullptr,
-                int *d_status_log = nullptr);
-}
-
-// ... against the plant of tiny_batch_set_plant, with a disturbance d_w and the state trajectory d_x_traj (both DEVICE [steps][B][nx], may be NULL).  A run
-// is simulated when a plant is set or either pointer is: on the 16-lane kernel it takes the SIM instantiations of the on-chip loop (admm_rowsim.hip),
-// every other kernel replays solve + plant kernel per step with the rows of step k baked into the graph.
-int tiny_batch_mpc_run_sim_async(TinyBatch *tb, int steps, int window_advance, const float *d_w, float *d_u0_traj, float *d_x_traj)
-{
-    CHECK_TB(tb);
-    return mpc_run_sim(tb, "tiny_batch_mpc_run_sim_async", steps, window_advance, d_w, d_u0_traj, d_x_traj);
-}
-
-// ... and the per-step solver log: d_iter_log / d_status_log (DEVICE [steps][B] ints, either may be NULL) receive iter[] and status[] after the solve
-// of every step — what a step-by-step loop reads with tiny_batch_get_status after step k.  A log does not make a run simulated: kernel and results are those
-// of the same call without it.  The 16-lane and quad loops store rows 0 .. steps - 2 on chip, every replayed kernel copies per step — the matrix-core
-// kernel and the 16-lane kernel with per-instance models among them: with a log their run is replayed step by step
-int tiny_batch_mpc_run_log_async(TinyBatch *tb, int steps, int window_advance, const float *d_w, float *d_u0_traj, float *d_x_traj, int *d_iter_log, int *d_status_log)
-{
-    CHECK_TB(tb);
-    return mpc_run_sim(tb, "tiny_batch_mpc_run_log_async", steps, window_advance, d_w, d_u0_traj, d_x_traj, d_iter_log, d_status_log);
-}
-
-int tiny_batch_mpc_run_traj_async(TinyBatch *tb, int steps, int window_advance, float *d_u0_traj)
-{
-    CHECK_TB(tb);
-    return mpc_run_sim(tb, "tiny_batch_mpc_run_async", steps, window_advance, nullptr, d_u0_traj, nullptr);
-}
-
-namespace
-{
-// who: the public call, for its messages
-// d_iter_log / d_status_log: the per-step solver log (DEVICE [steps][B] ints, may be NULL): row k = iter[] / status[] after the solve of MPC step k.  They
-// do not make a run simulated and choose no kernel
-int mpc_run_sim(TinyBatch *tb, const char *who, int steps, int window_advance, const float *d_w, float *d_u0_traj, float *d_x_traj, int *d_iter_log, int *d_status_log)
-{
-    if (steps < 1) return fail(TINY_BATCH_EINVAL, "%s: steps must be >= 1", who);
-    if (window_advance < 0) return fail(TINY_BATCH_EINVAL, "%s: window_advance must be >= 0 (got %d): the window gather clamps at the last table row only", who, window_advance);
-    if (tb->nx > 64) return fail(TINY_BATCH_EUNSUPPORTED, "mpc_run supports nx <= 64");
-    if (tb->max_iter <= 0) return fail(TINY_BATCH_EINVAL, "%s needs max_iter > 0", who);
-    TRY(set_device(tb));
-    if (tb->xref_mode == 1 && window_advance) tb->tile_map_dirty = true; // every path below slides xref_start[] (the on-chip loop writes it back)
-    const bool from_reset = tb->cold_pending; // (flush_pending materialises the zeros and clears the flag: the run's first solve is the cold one all the same)
-    TRY(flush_pending(tb)); // every solve of the run starts from "duals reset, workspace warm"
-    tb->duals_zero_pending = true;
-    const bool sim = tb->plant_mode != 0 || d_w != nullptr || d_x_traj != nullptr; // the run is simulated
-    KernelPlan pl;
-    TRY(prepare_solve(tb, steps > 1, &pl, sim));
-    const size_t u0n = (size_t)tb->batch * tb->nu, x0n = (size_t)tb->batch * tb->nx;
-    // the rows of MPC step k
-    auto w_at = [&](int k) { return d_w ? d_w + (size_t)k * x0n : nullptr; };
-    auto xt_at = [&](int k) { return d_x_traj ? d_x_traj + (size_t)k * x0n : nullptr; };
-    // row k of the logs: iter[] / status[] as the solve before it left them (two device-to-device copies on the handle's stream: captured with the rest)
-    auto log_row = [&](int k) {
-        const size_t o = (size_t)k * tb->batch, bytes = (size_t)tb->batch * sizeof(int);
-        hipError_t e = hipSuccess;
-        if (d_iter_log) e = hipMemcpyAsync(d_iter_log + o, tb->iter, bytes, hipMemcpyDeviceToDevice, tb->stream);
-        if (e == hipSuccess && d_status_log) e = hipMemcpyAsync(d_status_log + o, tb->status, bytes, hipMemcpyDeviceToDevice, tb->stream);
-        return e;
-    };
-    // (the matrix-core kernel's loop and the 16-lane loops with per-instance models do not log: their largest instantiations sit at the register
-    //  allocator's cliff, and the store moved their pinned scratch whichever way it was written.  A run that asks for a log there replays the same
-    //  kernel step by step, with the same bits)
-    const bool logs = d_iter_log != nullptr || d_status_log != nullptr;
-    if (traits(pl.kernel).onchip_mpc && !tb->h16 && steps > 1 && bounds_all_shared(tb) && (!sim || pl.kernel == Kernel::Rowlane) &&
-        !(logs && (pl.kernel == Kernel::Tile16 || pl.pm)))
-    {
-        RowParams P;
-        fill_row_params(tb, P, pl.exact);
-        P.mpc_steps = steps; P.window_advance = window_advance; P.u0_traj = d_u0_traj;
-        P.iter_log = d_iter_log; P.status_log = d_status_log;
-        SimParams S;
-        if (tb->plant_mode) { S.plant = tb->plant_rows; S.plant_stride = tb->plant_mode == 2 ? (unsigned)plant_row_floats(tb->nx, tb->nu) : 0u; }
-        S.w = d_w; S.x_traj = d_x_traj;
-        const int applied = enqueue_dispatch_order(tb, pl, steps, from_reset, P);
-        if (applied < 0) return applied;
-        tb->last_dispatch = applied;
-        tb->last_grouped = false;
-        // (tile16 gets tb->tile_queue like a lone solve: its two-ended queue is off whenever mpc_steps > 1 — t16_tail_stride returns 0 — so the setting changes nothing here)
-        const hipError_t e = launch_kernel(tb, pl, P, sim ? &S : nullptr);
-        if (e != hipSuccess) return fail(TINY_BATCH_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
-        if (d_u0_traj) TRY(launch_unpack(tb, work_ptr(tb, TINY_ARR_U), d_u0_traj + (size_t)(steps - 1) * u0n, tb->layout, 1, tb->batch, 0, 1));
-        HIP_TRY(log_row(steps - 1)); // the last row of the logs is the host's too: iter[] / status[] as the kernel's live-out left them
-        TRY(enqueue_plant_step(tb, window_advance, w_at(steps - 1), xt_at(steps - 1))); // the last step's plant step is the host's: the same plant, its own rows
-        tb->duals_zero_pending = tb->cold_pending = false;
-        tb->iter_history = true; // iter[] = the counts of the run's last solve
-        tb->ev_valid = false;
-        return 0;
-    }
-    if (!tb->stream) // stream capture is not allowed on the null stream
-    {
-        HIP_TRY(hipStreamSynchronize(nullptr));
-        if (!tb->own_stream) HIP_TRY(hipStreamCreateWithFlags(&tb->own_stream, hipStreamNonBlocking));
-        tb->stream = tb->own_stream;
-    }
-    // the graph bakes in kernel arguments: rebuild it whenever anything they depend on may have changed
-    // (round 3: the signature is complete — rho, the shared / per-instance modes that set the strides, the bound flags and the
-    // dispatch order are in it — so setters that only change buffer CONTENTS no longer drop the graph: `set_xref; mpc_run(k)`
-    // in a loop replays one captured graph instead of re-capturing it every step)
-    char sig[768];
-    snprintf(sig, sizeof sig, "%d|%p|%p|%p|%p|%p|%p|%p|%p|%p|%d|%d|%d|%s|%d|%d|%g|%g|%d|%d|%p|%p|%p|%d|%p|%p|%p|%p|%d%d|%a|%d%d%d|%d%d|%d|%p|%p|%p|%d|%p|%p", tb->plant_mode, (void *)tb->plant_A,
-             (void *)tb->plant_B, (const void *)d_w, (void *)d_x_traj, (void *)tb->pm_src, (void *)tb->pm_row[0],
-             (void *)tb->pm_row[1], (void *)tb->pm_wave[0], (void *)tb->pm_wave[1], steps, window_advance, tb->variant, kernel_name(tb, pl).c_str(), tb->max_iter,
-             tb->check_termination, (double)tb->abs_pri_tol, (double)tb->abs_dua_tol, tb->xref_mode, tb->table_rows, (void *)tb->pair[0],
-             (void *)tb->arr[0], (void *)tb->r_bounds, (int)tb->h16, (void *)tb->stream, (void *)d_u0_traj, (void *)tb->r_xref,
-             (void *)tb->r_uref, (int)tb->en_uref, (int)tb->en_d2p, (double)tb->rho, (int)bounds_all_shared(tb),
-             (int)(tb->in_xref.set && tb->in_xref.shared), (int)(tb->in_uref.set && tb->in_uref.shared), tb->en_state_bound, tb->en_input_bound,
-             tb->dispatch_mode, (void *)tb->order_dev, (void *)tb->mats_exact, (void *)tb->xref_start, (int)tb->zero_ties,
-             (void *)d_iter_log, (void *)d_status_log);
+    TRY(leave_null_stream(tb)); // stream capture is not allowed on the null stream
+    const std::string sig = graph_signature(tb, pl, run);
     if (!tb->graph_exec || tb->graph_sig != sig)
     {
         if (tb->graph_exec) { (void)hipGraphExecDestroy(tb->graph_exec); tb->graph_exec = nullptr; }
         hipGraph_t graph = nullptr;
         HIP_TRY(hipStreamBeginCapture(tb->stream, hipStreamCaptureModeThreadLocal));
         int rc = 0;
-        for (int k = 0; k < steps && rc == 0; k++)
+        for (int k = 0; k < run.steps && rc == 0; k++)
         {
             tb->duals_zero_pending = true;
-            rc = enqueue_solve(tb, pl, false);
-            if (rc == 0 && d_u0_traj) rc = launch_unpack(tb, work_ptr(tb, TINY_ARR_U), d_u0_traj + (size_t)k * u0n, tb->layout, 1, tb->batch, 0, 1);
-            if (rc == 0 && log_row(k) != hipSuccess) rc = fail(TINY_BATCH_EHIP, "%s: the copy of a log row failed", who);
-            if (rc == 0) rc = enqueue_plant_step(tb, window_advance, w_at(k), xt_at(k));
+            rc = enqueue_solve(tb, pl, false, nullptr);
+            if (rc == 0 && run.d_u0_traj) rc = launch_unpack(tb, work_ptr(tb, TINY_ARR_U), run.u0_at(tb, k), tb->layout, 1, tb->batch, 0, 1);
+            if (rc == 0 && run.log_row(tb, k) != hipSuccess) rc = fail(TINY_BATCH_EHIP, "%s: the copy of a log row failed", run.who);
+            if (rc == 0) rc = enqueue_plant_step(tb, run.window_advance, run.w_at(tb, k), run.x_at(tb, k));
         }
         hipError_t ec = hipStreamEndCapture(tb->stream, &graph);
         if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
@@ -2322,16 +2284,85 @@ int mpc_run_sim(TinyBatch *tb, const char *who, int steps, int window_advance, c
         tb->graph_captures++;
     }
     HIP_TRY(hipGraphLaunch(tb->graph_exec, tb->stream));
-    tb->duals_zero_pending = tb->cold_pending = false;
-    tb->ev_valid = false;
+    tb->duals_zero_pending = tb->cold_pending = false; // (a replay enqueues no solve of its own to clear them)
+    return 0;
+}
+
+// the run calls, all of them: the argument checks, what may allocate or synchronise, then the loop the plan names.  The two loops give identical results
+int mpc_run_sim(TinyBatch *tb, RunArgs run)
+{
+    if (run.steps < 1) return fail(TINY_BATCH_EINVAL, "%s: steps must be >= 1", run.who);
+    TRY(check_loop_args(tb, run.who, "mpc_run", run.window_advance));
+    if (tb->max_iter <= 0) return fail(TINY_BATCH_EINVAL, "%s needs max_iter > 0", run.who);
+    TRY(set_device(tb));
+    if (tb->xref_mode == 1 && run.window_advance) tb->tile_map_dirty = true; // either loop slides xref_start[] (the on-chip one writes it back)
+    run.from_reset = tb->cold_pending; // (flush_pending materialises the zeros and clears the flag: the run's first solve is the cold one all the same)
+    TRY(flush_pending(tb)); // every solve of the run starts from "duals reset, workspace warm"
+    tb->duals_zero_pending = true;
+    const bool sim = tb->plant_mode != 0 || run.d_w != nullptr || run.d_x_traj != nullptr, logs = run.d_iter_log != nullptr || run.d_status_log != nullptr;
+    KernelPlan pl;
+    TRY(prepare_solve(tb, Call{run.steps > 1 ? Call::Run : Call::Solve, sim, logs}, &pl));
+    TRY(pl.loop == Loop::OnChip ? run_on_chip(tb, pl, run) : run_replayed(tb, pl, run));
+    tb->ev_valid = false; // no event brackets a run
+    return 0;
+}
+
+// host-array variant of tiny_batch_mpc_run_log_async (any of the five may be NULL): the device buffers live on the HANDLE's device for the call
+int mpc_run_log_host(TinyBatch *tb, const char *who, int steps, int window_advance, const float *w, float *u0_traj, float *x_traj, int *iter_log, int *status_log)
+{
+    if (!tb) return fail(TINY_BATCH_EINVAL, "%s: NULL TinyBatch handle", who);
+    if (steps < 1) return fail(TINY_BATCH_EINVAL, "%s: steps must be >= 1", who);
+    TRY(set_device(tb));
+    // device copies kept on the handle and re-allocated only when their size changes: on the replayed paths the captured graph bakes their addresses
+    // in (they are in its signature), and a loop of equal calls must replay one graph.  (The two logs are ints in float-sized words.)
+    const size_t nxf = (size_t)steps * tb->batch * tb->nx, nuf = (size_t)steps * tb->batch * tb->nu, nlf = (size_t)steps * tb->batch;
+    const void *host[5] = {w, u0_traj, x_traj, iter_log, status_log};
+    const size_t nf[5] = {nxf, nuf, nxf, nlf, nlf};
+    float *dev[5] = {};
+    for (int k = 0; k < 5; k++)
+        if (host[k])
+        {
+            if (tb->sim_stage[k] && tb->sim_stage_n[k] != nf[k]) HIP_TRY(hipStreamSynchronize(tb->stream)); // a run still using the old buffer may be in flight
+            TRY(sized_buffer(&tb->sim_stage[k], &tb->sim_stage_n[k], nf[k]));
+            dev[k] = tb->sim_stage[k];
+        }
+    if (w) HIP_TRY(hipMemcpy(dev[0], w, nxf * sizeof(float), hipMemcpyHostToDevice));
+    TRY(mpc_run_sim(tb, RunArgs{who, steps, window_advance, dev[0], dev[1], dev[2], (int *)dev[3], (int *)dev[4]}));
+    HIP_TRY(hipStreamSynchronize(tb->stream));
+    if (u0_traj) HIP_TRY(hipMemcpy(u0_traj, dev[1], nuf * sizeof(float), hipMemcpyDeviceToHost));
+    if (x_traj) HIP_TRY(hipMemcpy(x_traj, dev[2], nxf * sizeof(float), hipMemcpyDeviceToHost));
+    if (iter_log) HIP_TRY(hipMemcpy(iter_log, dev[3], nlf * sizeof(int), hipMemcpyDeviceToHost));
+    if (status_log) HIP_TRY(hipMemcpy(status_log, dev[4], nlf * sizeof(int), hipMemcpyDeviceToHost));
     return 0;
 }
 } // namespace
 
-int tiny_batch_mpc_run_async(TinyBatch *tb, int steps, int window_advance)
+int tiny_batch_mpc_step_sim_async(TinyBatch *tb, int window_advance, const float *d_w) { CHECK_TB(tb); return mpc_step_sim(tb, "tiny_batch_mpc_step_sim_async", window_advance, d_w); }
+int tiny_batch_mpc_step_async(TinyBatch *tb, int window_advance) { CHECK_TB(tb); return mpc_step_sim(tb, "tiny_batch_mpc_step_async", window_advance, nullptr); }
+
+// `steps` closed-loop MPC steps back to back against the plant of tiny_batch_set_plant (none set: the model's own dynamics): RunArgs has the arguments.  Whether
+// the steps run inside one launch or as a replayed launch sequence is the plan's to say (KernelPlan::loop): the results are the same
+int tiny_batch_mpc_run_sim_async(TinyBatch *tb, int steps, int window_advance, const float *d_w, float *d_u0_traj, float *d_x_traj)
 {
-    return tiny_batch_mpc_run_traj_async(tb, steps, window_advance, nullptr);
+    CHECK_TB(tb);
+    return mpc_run_sim(tb, RunArgs{"tiny_batch_mpc_run_sim_async", steps, window_advance, d_w, d_u0_traj, d_x_traj, nullptr, nullptr});
 }
+
+// ... and the per-step solver log: what a step-by-step loop reads with tiny_batch_get_status after step k.  A log does not make a run simulated: kernel and
+// results are those of the same call without it
+int tiny_batch_mpc_run_log_async(TinyBatch *tb, int steps, int window_advance, const float *d_w, float *d_u0_traj, float *d_x_traj, int *d_iter_log, int *d_status_log)
+{
+    CHECK_TB(tb);
+    return mpc_run_sim(tb, RunArgs{"tiny_batch_mpc_run_log_async", steps, window_advance, d_w, d_u0_traj, d_x_traj, d_iter_log, d_status_log});
+}
+
+int tiny_batch_mpc_run_traj_async(TinyBatch *tb, int steps, int window_advance, float *d_u0_traj)
+{
+    CHECK_TB(tb);
+    return mpc_run_sim(tb, RunArgs{"tiny_batch_mpc_run_async", steps, window_advance, nullptr, d_u0_traj, nullptr, nullptr, nullptr});
+}
+
+int tiny_batch_mpc_run_async(TinyBatch *tb, int steps, int window_advance) { return tiny_batch_mpc_run_traj_async(tb, steps, window_advance, nullptr); }
 
 // host-copy variant: the trajectory buffer is allocated on the HANDLE's device (whatever device is current for the calling
 // thread), the run is waited for and u.col(0) of every step lands in host memory
@@ -2354,44 +2385,10 @@ int tiny_batch_mpc_run_traj(TinyBatch *tb, int steps, int window_advance, float 
     return rc;
 }
 
-namespace
-{
-// host-array variant of tiny_batch_mpc_run_log_async (any of the five may be NULL): the device buffers live on the HANDLE's device for the call.
-// who: the public call, for its messages
-int mpc_run_log_host(TinyBatch *tb, const char *who, int steps, int window_advance, const float *w, float *u0_traj, float *x_traj, int *iter_log, int *status_log)
-{
-    if (!tb) return fail(TINY_BATCH_EINVAL, "%s: NULL TinyBatch handle", who);
-    if (steps < 1) return fail(TINY_BATCH_EINVAL, "%s: steps must be >= 1", who);
-    TRY(set_device(tb));
-    // device copies kept on the handle and re-allocated only when their size changes: on the replayed paths the captured graph bakes their addresses
-    // in (they are in its signature), and a loop of equal calls must replay one graph.  (The two logs are ints in float-sized words.)
-    const size_t nxf = (size_t)steps * tb->batch * tb->nx, nuf = (size_t)steps * tb->batch * tb->nu, nlf = (size_t)steps * tb->batch;
-    const void *host[5] = {w, u0_traj, x_traj, iter_log, status_log};
-    const size_t nf[5] = {nxf, nuf, nxf, nlf, nlf};
-    float *dev[5] = {};
-    for (int k = 0; k < 5; k++)
-        if (host[k])
-        {
-            if (tb->sim_stage[k] && tb->sim_stage_n[k] != nf[k]) HIP_TRY(hipStreamSynchronize(tb->stream)); // a run still using the old buffer may be in flight
-            TRY(sized_buffer(&tb->sim_stage[k], &tb->sim_stage_n[k], nf[k]));
-            dev[k] = tb->sim_stage[k];
-        }
-    if (w) HIP_TRY(hipMemcpy(dev[0], w, nxf * sizeof(float), hipMemcpyHostToDevice));
-    TRY(mpc_run_sim(tb, who, steps, window_advance, dev[0], dev[1], dev[2], (int *)dev[3], (int *)dev[4]));
-    HIP_TRY(hipStreamSynchronize(tb->stream));
-    if (u0_traj) HIP_TRY(hipMemcpy(u0_traj, dev[1], nuf * sizeof(float), hipMemcpyDeviceToHost));
-    if (x_traj) HIP_TRY(hipMemcpy(x_traj, dev[2], nxf * sizeof(float), hipMemcpyDeviceToHost));
-    if (iter_log) HIP_TRY(hipMemcpy(iter_log, dev[3], nlf * sizeof(int), hipMemcpyDeviceToHost));
-    if (status_log) HIP_TRY(hipMemcpy(status_log, dev[4], nlf * sizeof(int), hipMemcpyDeviceToHost));
-    return 0;
-}
-} // namespace
-
 int tiny_batch_mpc_run_log(TinyBatch *tb, int steps, int window_advance, const float *w, float *u0_traj, float *x_traj, int *iter_log, int *status_log)
 {
     return mpc_run_log_host(tb, "tiny_batch_mpc_run_log", steps, window_advance, w, u0_traj, x_traj, iter_log, status_log);
 }
-
 int tiny_batch_mpc_run_sim(TinyBatch *tb, int steps, int window_advance, const float *w, float *u0_traj, float *x_traj)
 {
     return mpc_run_log_host(tb, "tiny_batch_mpc_run_sim", steps, window_advance, w, u0_traj, x_traj, nullptr, nullptr);
@@ -2436,10 +2433,10 @@ const char *tiny_batch_kernel_name(TinyBatch *tb)
     {
         const std::string keep = g_err;
         KernelPlan pl;
-        (void)prepare_solve(tb, false, &pl); // (not ready yet: the name is then the one the present knowledge gives)
+        (void)prepare_solve(tb, kLoneSolve, &pl); // (not ready yet: the name is then the one the present knowledge gives)
         g_err = keep;
     }
-    return plan_name(tb, false);
+    return plan_name(tb, kLoneSolve);
 }
 
 int tiny_batch_debug_graph_captures(TinyBatch *tb)
@@ -2497,7 +2494,7 @@ int tiny_batch_arithmetic(TinyBatch *tb)
 {
     CHECK_TB(tb);
     KernelPlan pl;
-    TRY(resolve_plan(tb, false, &pl));
+    TRY(resolve_plan(tb, kLoneSolve, &pl));
     return pl.exact ? TINY_BATCH_ARITH_EXACT : TINY_BATCH_ARITH_FMA;
 }
 
@@ -2506,7 +2503,7 @@ int tiny_batch_arithmetic(TinyBatch *tb)
 const char *tiny_batch_closed_loop_kernel_name(TinyBatch *tb)
 {
     if (!tb) return "";
-    return plan_name(tb, true, tb->plant_mode != 0); // (a run that passes d_w or d_x_traj without a plant is simulated too: only the call knows)
+    return plan_name(tb, Call{Call::Run, tb->plant_mode != 0}); // (a run that passes d_w or d_x_traj without a plant is simulated too: only the call knows)
 }
 
 int tiny_batch_set_row_kernel(TinyBatch *tb, int family)
@@ -2579,7 +2576,7 @@ int tiny_batch_select_kernel(TinyBatch *tb, int variant)
     const int old = tb->variant;
     tb->variant = variant;
     KernelPlan pl;
-    if (int rc = resolve_plan(tb, false, &pl)) { tb->variant = old; return rc; }
+    if (int rc = resolve_plan(tb, kLoneSolve, &pl)) { tb->variant = old; return rc; }
     invalidate_graph(tb);
     TRY(set_device(tb));
     TRY(ensure_layout(tb, traits(pl.kernel).layout));

@@ -46,6 +46,14 @@ def test_selection_is_stated_once():
     assert src.count("launch_dispatch_order(") == 1 and src.count("launch_dispatch_order_history(") == 1
     for name in set(re.findall(r"launch_admm_\w+", src)) - {"launch_admm_step"}:
         assert src.count(name + "(") == 1, f"{name} is called from more than one place"
+    # ... and so is whether a closed-loop run stays on chip (KernelPlan::loop): the trait is read once, the kind of call travels as a Call, and one
+    # function (enqueue_solve) orders and launches a solve kernel
+    assert src.split("constexpr const KernelTraits &traits(", 1)[1].count("onchip_mpc") == 1, "onchip_mpc is read outside resolve_plan's plan_of"
+    for gone in ("bool sim = false", "bool closed_loop"):
+        assert gone not in src, gone
+    for name in ("launch_kernel(", "enqueue_dispatch_order("):
+        assert src.count(name) == 2, f"{name} its definition and ONE call"
+    assert len(re.findall(r"\bint mpc_run_sim\(", src)) == 1, "mpc_run_sim is declared once"
 
 
 @pytest.fixture(scope="module")
