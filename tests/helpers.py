@@ -400,3 +400,162 @@ def rounding_free_case(nx, nu, N, B, seed, terms=False):
     x0 = rng.integers(-4, 5, size=(B, nx)).astype(np.float32)
     xref = rng.integers(-2, 3, size=(B, N, nx)).astype(np.float32)
     return prob, settings, x0, xref, bounds_of(prob, np.float32), uref
+
+
+def _signed_band(rng, rows, cols, k=2):
+    """0 / +-1 with k entries per row, row r in columns r*k ... r*k + k - 1 (mod cols); k is raised to ceil(cols / rows), so that the rows together
+    cover every column, and capped at cols.  The placement is fixed, the signs are drawn."""
+    k = min(cols, max(k, -(-cols // rows)))
+    m = np.zeros((rows, cols))
+    m[np.arange(rows)[:, None], (np.arange(rows)[:, None] * k + np.arange(k)[None, :]) % cols] = rng.choice([-1.0, 1.0], size=(rows, k))
+    return m
+
+
+def dense_selection_model(nx, nu, N, seed):
+    """one model of rounding_free_dense_case: every matrix a _signed_band, an integer Q, rho = 1"""
+    rng = np.random.default_rng([seed, 0])
+    return dict(name=f"dense_selection_{nx}_{nu}", nx=nx, nu=nu, N=N, rho=1.0, Kinf=_signed_band(rng, nu, nx), Pinf=_signed_band(rng, nx, nx),
+                Quu_inv=_signed_band(rng, nu, nu), AmBKt=_signed_band(rng, nx, nx), Adyn=_signed_band(rng, nx, nx), Bdyn=_signed_band(rng, nx, nu),
+                Q=rng.integers(1, 4, size=nx).astype(np.float64), u_min=-16.0, u_max=16.0, x_min=-32.0, x_max=32.0)
+
+
+def integer_boxes(nx, nu, N, B, seed, per_instance, xlo=16, ulo=8):
+    """(x_min, x_max, u_min, u_max): integer bounds of magnitude xlo ... 2 xlo and ulo ... 2 ulo, drawn per (step, row) and each side on its own;
+    per_instance: a table per instance"""
+    lead = (B,) if per_instance else ()
+    box = lambda tag, sign, lo, shape: (sign * np.random.default_rng([seed, tag]).integers(lo, 2 * lo + 1, size=lead + shape)).astype(np.float32)
+    return box(4, -1, xlo, (N, nx)), box(5, 1, xlo, (N, nx)), box(6, -1, ulo, (N - 1, nu)), box(7, 1, ulo, (N - 1, nu))
+
+
+def nonzero_terminal_reference(xref, N, seed):
+    """xref (an array, or a (table, start) window) with every row that can be the LAST of a horizon of N redrawn from -2, -1, 1, 2: Pinf multiplies the
+    terminal reference row alone, and a zero there would hide an entry of Pinf from the only instance that reads it"""
+    table = np.array(xref[0] if isinstance(xref, tuple) else xref)
+    last = table[N - 1:] if isinstance(xref, tuple) else table[..., N - 1:, :]     # a window: any row from N - 1 on, by its start
+    last[...] = np.random.default_rng([seed, 8]).choice([-2.0, -1.0, 1.0, 2.0], size=last.shape)
+    return (table, xref[1]) if isinstance(xref, tuple) else table
+
+
+def rounding_free_dense_case(nx, nu, N, B, seed, bounds="shared", ref="inst", models=False):
+    """(prob, settings, x0, xref, bnds, uref) as rounding_free_case returns them (uref is None: the optional terms live in the row kernels, which
+    the fma oracle pins bit for bit), on the same premise — integers through matrices of 0 / +-1, rho = 1, tolerances 0, both bound flags on, so that no
+    fp32 operation rounds and an fma, a multiply-then-add, an MFMA accumulation and any summation order give the same VALUE — but with every term of
+    every product in play: each matrix is a _signed_band (at least two entries in every row that is two columns wide, no empty column).
+    The gains do not stabilise anything, so the values grow with the horizon and with the iterations: the caller keeps N and max_iter small and proves
+    the premise by comparing the fp32 with the fp64 exact oracle (tests/test_fma_oracle_host.py).
+    The boxes are integers, |u| bound 8 ... 16 and |x| bound 16 ... 32, drawn per (step, row) and each side on its own: the projections bind on a part of
+    the entries.  bounds = "inst": a table per instance.  ref = "inst": a reference per instance; "shared": one [N][nx]; "window": xref is a (table,
+    start) pair, an integer table of N + 8 rows and a start per instance.  The reference is drawn from -2 ... 2, its terminal row (every row of a
+    table that a start makes the terminal one) without the zero: nonzero_terminal_reference.  models: prob is a LIST of B models, instance b's drawn from seed + 1 + b.
+    Every array is drawn from a stream of its own, instance by instance: the first B' instances of a case of B are the case of B'."""
+    rng = lambda tag: np.random.default_rng([seed, tag])
+    prob = [dense_selection_model(nx, nu, N, seed + 1 + b) for b in range(B)] if models else dense_selection_model(nx, nu, N, seed)
+    settings = dict(abs_pri_tol=0.0, abs_dua_tol=0.0, check_termination=1, en_state_bound=1, en_input_bound=1)
+    x0 = rng(1).integers(-4, 5, size=(B, nx)).astype(np.float32)
+    if ref == "window":
+        xref = (rng(2).integers(-2, 3, size=(N + 8, nx)).astype(np.float32), rng(3).integers(0, 9, size=B).astype(np.int32))
+    else:
+        xref = rng(2).integers(-2, 3, size=(N, nx) if ref == "shared" else (B, N, nx)).astype(np.float32)
+    return prob, settings, x0, nonzero_terminal_reference(xref, N, seed), integer_boxes(nx, nu, N, B, seed, bounds == "inst"), None
+
+
+# ---- the cases of tests/test_fma_values_gpu.py; tests/test_fma_oracle_host.py proves what their inputs are worth, from this same list ------------------
+
+def _vc(kernel, dims, select, family, bounds, ref, Bs, max_iters=(1, 2), gen="dense"):
+    """kernel: the name the case must run on.  select / family: select_kernel / set_row_kernel.  gen: "dense" rounding_free_dense_case, "sparse"
+    rounding_free_case (where the dense values outgrow fp32 in a second iteration of N = 10); "..._pm": one model per instance."""
+    return dict(kernel=kernel, dims=dims, select=select, family=family, bounds=bounds, ref=ref, Bs=Bs, max_iters=max_iters, gen=gen)
+
+
+_ROWS2 = (("shared", "inst"), ("inst", "window"))
+_ROWS4 = _ROWS2 + (("shared", "window"), ("inst", "inst"))
+# four lanes per instance, N = 10 only: a wave holds sixteen instances (the quad kernel stages one shared bounds table)
+QUADLANE_VALUE_CASES = [_vc("quadlane<4,1,10,fast>", (4, 1, 10), 3, 4, "shared", "inst", (1, 17, 37), (1,)),
+                        _vc("quadlane<4,1,10,fast>", (4, 1, 10), 3, 4, "shared", "inst", (1, 17, 37), (1, 2), "sparse")]
+# one wavefront per instance; (16, 4) and (24, 4) outgrow fp32 in the second iteration of N = 5 (24, 4: in another order of the sums)
+WAVERES_VALUE_CASES = [_vc(f"waveres<{d[0]},{d[1]},fast>", d, 3, 7, b, r, (1, 3, 37), mi)
+                       for d, mi in (((32, 16, 5), (1, 2)), ((16, 8, 5), (1, 2)), ((20, 8, 5), (1, 2)), ((24, 4, 4), (1, 2)), ((16, 4, 4), (1, 2)),
+                                     ((16, 4, 5), (1,)), ((16, 4, 6), (1,)), ((24, 4, 5), (1,))) for b, r in _ROWS2]
+# sixteen instances per workgroup: one live column beside a full tile, and ragged
+TILE48_VALUE_CASES = [_vc(f"tile48<32,16,{N},fast>", (32, 16, N), 3, 8, b, r, (1, 17, 37)) for N in (4, 5) for b, r in _ROWS4]
+# the MFMA streaming kernel, named by its chunks of four rows: five classes with an instantiation of their own, four served by the smallest
+# instantiation that contains them (padding rows and columns); tiles of sixteen instances
+STREAM_VALUE_CASES = [_vc(k, d, 1, 0, b, r, (17, 37))
+                      for k, d in (("stream<3,1>", (12, 4, 5)), ("stream<1,1>", (4, 1, 6)), ("stream<2,1>", (8, 4, 5)), ("stream<8,4>", (32, 16, 5)),
+                                   ("stream<16,8>", (64, 32, 4)), ("stream<8,4>", (5, 5, 5)), ("stream<16,8>", (33, 17, 4)), ("stream<3,1>", (10, 3, 4)),
+                                   ("stream<2,1>", (6, 2, 4))) for b, r in _ROWS2]
+# every instance its own model
+# (most dense models of (12, 4) outgrow fp32 within one iteration of N = 10: the dense case of the 16-lane kernel is (8, 3, 7))
+MODELS_VALUE_CASES = [_vc("rowlane<8,3,7,fast,pm>", (8, 3, 7), 3, 1, "shared", "inst", (37,), (1,), "dense_pm"),
+                      _vc("rowlane<12,4,10,fast,pm>", (12, 4, 10), 3, 1, "inst", "inst", (37,), (1, 2), "sparse_pm"),
+                      _vc("waveres<32,16,fast,pm>", (32, 16, 5), 3, 7, "inst", "window", (37,), (1, 2), "dense_pm"),
+                      _vc("waveres<16,8,fast,pm>", (16, 8, 5), 3, 7, "shared", "inst", (37,), (1, 2), "dense_pm")]
+FMA_VALUE_CASES = QUADLANE_VALUE_CASES + WAVERES_VALUE_CASES + TILE48_VALUE_CASES + STREAM_VALUE_CASES + MODELS_VALUE_CASES
+# quadlane's closed loop on chip: two MPC steps of one iteration each
+QUADLANE_LOOP_CASE = dict(_vc("quadlane<4,1,10,fast>", (4, 1, 10), 3, 4, "shared", "inst", (1, 17, 37), (1,), "sparse"), steps=2)
+
+
+def value_case_id(c):
+    return "{}-{}-{}-{}".format(c["kernel"], "_".join(map(str, c["dims"])), c["gen"], c["bounds"] + "_" + c["ref"])
+
+
+_value_inputs = {}
+SPARSE_BOXES = (3, 2)   # through selection matrices the values stay small: boxes this narrow bind on a part of the entries
+
+
+def value_case_inputs(c, B=None):
+    """(prob or the list of B per-instance models, settings without max_iter, x0, xref, bnds) of a case at B instances: the first B of the case built
+    once at max(c["Bs"]) — every instance's inputs are its own, so what the host tests prove at the largest batch holds for the smaller ones."""
+    key = (c["gen"], c["dims"], c["bounds"], c["ref"], max(c["Bs"]))
+    if key not in _value_inputs:
+        nx, nu, N = c["dims"]
+        Bm, pm = max(c["Bs"]), c["gen"].endswith("_pm")
+        if c["gen"].startswith("dense"):
+            prob, settings, x0, xref, bnds, _ = rounding_free_dense_case(nx, nu, N, Bm, 0, bounds=c["bounds"], ref=c["ref"], models=pm)
+        else:   # the sparse generator draws a per-instance reference; its boxes (+-50, +-3: the states never reach theirs) are replaced
+            prob, settings, x0, xref, bnds, _ = rounding_free_case(nx, nu, N, Bm, 0)
+            assert c["ref"] == "inst"
+            xref = nonzero_terminal_reference(xref, N, 0)
+            # one term per row: a zero of x0 would hide the entry of Adyn or Kinf that multiplies it from the only instance that reads the model
+            x0 = np.where(x0 == 0, np.random.default_rng([0, 9]).choice([-1.0, 1.0], size=x0.shape), x0).astype(np.float32)
+            bnds = integer_boxes(nx, nu, N, Bm, 0, c["bounds"] == "inst", *SPARSE_BOXES)
+            if pm:
+                # models of seeds 300 ... 336: now and then a selection model outgrows fp32 in the second iteration of N = 10; of these 37 none does
+                # (largest magnitude 2.8e5, below 2^19), which tests/test_fma_oracle_host.py proves on the oracle for each of them
+                prob = [rounding_free_case(nx, nu, N, 1, 300 + b)[0] for b in range(Bm)]
+        _value_inputs[key] = (prob, settings, x0, xref, bnds)
+    prob, settings, x0, xref, bnds = _value_inputs[key]
+    B = B or max(c["Bs"])
+    cut = lambda a, shared_ndim: a if a.ndim == shared_ndim else a[:B]
+    xref = (xref[0], xref[1][:B]) if isinstance(xref, tuple) else cut(xref, 2)
+    return (prob[:B] if isinstance(prob, list) else prob), settings, x0[:B], xref, tuple(cut(b, 2) for b in bnds)
+
+
+def models_of(probs):
+    """the dict TinyBatchSolver.set_models takes, from one prob-style model per instance"""
+    mods = {k: np.array([p[k] for p in probs]) for k in PROB_KEYS}
+    mods["rho"] = np.array([p["rho"] for p in probs])
+    return mods
+
+
+def value_case_oracle(O, probs, dtype, settings, x0, xref, bnds, arith="exact"):
+    """(rc, state) of one cold solve of a value case on the CPU oracle; a list of models: every instance with its own.  fp64 is the proof that nothing
+    rounds, where the order of a sum is immaterial: every dimension is accepted."""
+    dt = np.float64 if dtype == np.float64 else np.float32
+    B, pm = len(x0), isinstance(probs, list)
+    p0 = probs[0] if pm else probs
+    nx, nu, N = p0["nx"], p0["nu"], p0["N"]
+    xr = np.asarray(ref_at(xref, 0, 0, N, B), dt)
+    bnds = [np.asarray(b, dt) for b in bnds]
+    st = O.new_state(B, nx, nu, N, dt)
+    st["x"][:, 0] = x0
+    if not pm:
+        return O.Oracle(probs, dtype, settings, arith=arith, allow_unpinned_dims=True).solve(st, *bnds, xr), st
+    rc = 0
+    for b, p in enumerate(probs):
+        sub = {k: np.ascontiguousarray(v[b:b + 1]) for k, v in st.items()}
+        rc += O.Oracle(p, dtype, settings, arith=arith, allow_unpinned_dims=True).solve(sub, *[a[b:b + 1] if a.ndim == 3 else a for a in bnds],
+                                                                                       np.ascontiguousarray(xr[b:b + 1] if xr.ndim == 3 else xr))
+        for k in st:
+            st[k][b] = sub[k][0]
+    return rc, st

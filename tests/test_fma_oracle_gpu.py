@@ -6,8 +6,10 @@ Fma arithmetic is a fully determined sequence of IEEE operations ("Fm
 on the CPU, so the plain-C restatement is a second statement of the same numbers.  Every case asserts the name of the kernel it runs on first, so that
 a routing change cannot quietly move it to another kernel.
 
-Out of scope: quadlane, waveres, tile48, stream and the padded MFMA kernel sum in orders of their own (they keep the yardstick bar of
-tests/test_parity_gpu.py), and the per-instance-model records.
+Out of scope here: quadlane, waveres, tile48, stream with the padded classes it serves, and the per-instance-model records sum in orders of their
+own, which a restatement in C does not follow.  tests/test_fma_values_gpu.py holds them to the EXACT oracle by value instead, on rounding-free
+inputs in which every term of every product is observable (proven in tests/test_fma_oracle_host.py); beyond those inputs they keep the yardstick
+bar of tests/test_parity_gpu.py, unchanged.
 """
 import numpy as np
 import pytest
@@ -65,9 +67,15 @@ def _warm_state(O, rng, B, nx, nu, N, R=lambda a: a, dual=lambda a: a):
     return st
 
 
-def _handle(T, prob, B, settings, select, family, bnds, ref, name, storage=None):
+def _handle(T, prob, B, settings, select, family, bnds, ref, name, storage=None, models=None):
+    """models: the dict set_models takes, one model per instance (prob then only gives the dimensions)"""
     sol = T.TinyBatchSolver(prob, B, settings={k: v for k, v in settings.items() if k not in ("en_uref", "en_coeff_d2p")})
-    sol.select_kernel(select); sol.set_row_kernel(family)
+    if models is not None:
+        sol.set_models(models)
+    if models is not None and family == 7:   # under models the row variants exist through the forced wave family only: the family first
+        sol.set_row_kernel(family); sol.select_kernel(select)
+    else:
+        sol.select_kernel(select); sol.set_row_kernel(family)
     if storage:
         sol.set_storage(*storage)
     sol.set_bounds(*bnds)
