@@ -51,6 +51,13 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 #ifndef TINY_T16_PADTAB
 #define TINY_T16_PADTAB 1 // the staged reference table carries N - 1 copies of its last row: no per-step clamp of the window's row (round 4)
 #endif
+#ifndef TINY_T16_HEADPAD
+#define TINY_T16_HEADPAD 1 // the exact cold-start instantiation reads the padded table without the per-step clamp too (it kept the clamp while the
+                           // unclamped form cost it two scratch accesses per iteration; with its sweeps under one EXEC region each it has none either way)
+#endif
+#ifndef TINY_T16_HEADWAIT
+#define TINY_T16_HEADWAIT 1 // HEAD: one counted LDS wait per sweep step, placed by hand, instead of the two hipcc places
+#endif
 #ifndef TINY_T16_XPOSE
 #define TINY_T16_XPOSE 1 // live-out rows transposed across the four lane groups in registers (v_permlane32_swap / v_permlane16_swap) instead of through LDS (round 4)
 #endif
@@ -248,7 +255,8 @@ struct TileMath
             F.acc = TINY_MFMA4(A3[2], p[2], acc);
         }
     }
-    __device__ __forceinline__ void riccati_finish(const InFlight &F, const f32x4 &lin, float (&pn)[3], float &dd) const
+    template <bool SPLIT = false>
+    __device__ __forceinline__ void riccati_finish(const InFlight &F, const f32x4 &lin, float (&pn)[3], float &dd, float *ddb = nullptr) const
     {
         if constexpr (EXACT)
         {
@@ -264,7 +272,13 @@ struct TileMath
             const f32x4 pn4 = wv - reduce4<PL::BWD_PK>(tk4);
             pn[0] = pn4[0]; pn[1] = pn4[1]; pn[2] = pn4[2];
             float tk[4];
-            gather4<3>(tk, pq); dd = reduce<PL::BWD_D>(tk);
+            gather4<3>(tk, pq);
+            if constexpr (SPLIT) // the last add of d_i is left to the caller (region_backward_update adds dd + ddb into the state register)
+            {
+                static_assert(!SPLIT || PL::BWD_D == PLAN_SEQ, "d_i is summed sequentially: ((t0 + t1) + t2) + t3");
+                dd = (tk[0] + tk[1]) + tk[2]; *ddb = tk[3];
+            }
+            else dd = reduce<PL::BWD_D>(tk);
         }
         else
         {
@@ -356,6 +370,54 @@ __device__ __forceinline__ void masked_backward_update(unsigned long long m, flo
                  : [m] "s"(m), [n0] "v"(pn[0]), [n1] "v"(pn[1]), [n2] "v"(pn[2]), [dd] "v"(dd)
                  : "scc");
 }
+
+// ---- the headline instantiation (HEAD in the kernel: exact, cold start, shared tables, one solve) runs each of its two sweeps under ONE
+// narrowed EXEC instead of sixty: a lone wave pays every instruction, scalar ones included, with an issue slot, and the sixty
+// s_and_saveexec / s_mov pairs of an iteration are 120 of them.  Nothing a converged column computes is used (its residual maxima, pN, iter and
+// status are guarded by `active`, its LDS accesses are not wanted, the matrix cores ignore EXEC and keep columns apart), and the four lanes of
+// an instance are active or inactive together.  What must hold is that every word of the state keeps its HOME register across the region: a
+// lane that is switched off keeps its frozen value only where the new value is written over the old one.  So the state is still written by asm
+// statements whose operands are tied ("+v" / "+a"), never by a plain assignment, which would be free to put the new value elsewhere.
+// The two statements name EXEC as clobbered, which makes the MACHINE scheduler treat them as boundaries (hipcc warns that EXEC is a reserved
+// register that "may not be preserved across the asm statement": changing it is the point, the warning is switched off for the two).
+// LIMITATION, not a guarantee: nothing tells the IR-level passes (GVN, LICM, sinking) or the register allocator about the narrowed EXEC.  They
+// remain free to move pure arithmetic or a readfirstlane across the statements, to copy a live value to another register inside a region, or
+// to rewrite an MFMA's gain operand there (which the MFMAs read from ALL lanes).  That the emitted code does none of it is CHECKED, not
+// implied: tests/test_tile16_headline_isa.py on the listing of every build (sweeps inside the pairs, home registers, gain operands) and the
+// bitwise tests of tests/test_tile16_headline_gpu.py.  A toolchain change that trips them means going back to masked_*_update.
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"
+__device__ __forceinline__ unsigned long long exec_narrow(unsigned long long m)
+{
+    unsigned long long sx;
+    asm volatile("s_and_saveexec_b64 %0, %1" : "=&s"(sx) : "s"(m) : "memory", "scc", "exec");
+    return sx;
+}
+__device__ __forceinline__ void exec_restore(unsigned long long sx) { asm volatile("s_mov_b64 exec, %0" : : "s"(sx) : "memory", "exec"); }
+#pragma clang diagnostic pop
+// masked_forward_update inside such a region; the slack slot of the step is addressed as the wave's base plus an immediate offset (<= 29 KB;
+// `off` is a constant once the sweep is unrolled, which the "i" constraint demands)
+__device__ __forceinline__ void region_forward_update(float (&a)[4], const f32x4 &tp, float (&bo)[4], const f32x4 &old, unsigned sn_addr, int off,
+                                                      const f32x4 &t)
+{
+    asm volatile("v_sub_f32 %[a0], %[p0], %[t0]\n\tv_sub_f32 %[a1], %[p1], %[t1]\n\tv_sub_f32 %[a2], %[p2], %[t2]\n\tv_sub_f32 %[a3], %[p3], %[t3]\n\t"
+                 "v_accvgpr_write_b32 %[b0], %[o0]\n\tv_accvgpr_write_b32 %[b1], %[o1]\n\tv_accvgpr_write_b32 %[b2], %[o2]\n\tv_accvgpr_write_b32 %[b3], %[o3]\n\t"
+                 "ds_write_b128 %[ad], %[tv] offset:%[off]"
+                 : [a0] "+v"(a[0]), [a1] "+v"(a[1]), [a2] "+v"(a[2]), [a3] "+v"(a[3]), [b0] "+a"(bo[0]), [b1] "+a"(bo[1]), [b2] "+a"(bo[2]),
+                   [b3] "+a"(bo[3])
+                 : [p0] "v"(tp[0]), [p1] "v"(tp[1]), [p2] "v"(tp[2]), [p3] "v"(tp[3]), [t0] "v"(t[0]), [t1] "v"(t[1]), [t2] "v"(t[2]), [t3] "v"(t[3]),
+                   [o0] "v"(old[0]), [o1] "v"(old[1]), [o2] "v"(old[2]), [o3] "v"(old[3]), [ad] "v"(sn_addr), [tv] "v"(t), [off] "i"(off)
+                 : "memory");
+}
+// masked_backward_update inside such a region; d_i = dda + ddb, the last add of its sum, lands in its state register
+__device__ __forceinline__ void region_backward_update(float (&pl)[3], float &dr, const float (&pn)[3], float dda, float ddb)
+{
+    asm volatile("v_accvgpr_write_b32 %[p0], %[n0]\n\tv_accvgpr_write_b32 %[p1], %[n1]\n\tv_accvgpr_write_b32 %[p2], %[n2]\n\tv_add_f32 %[d], %[da], %[db]"
+                 : [p0] "+a"(pl[0]), [p1] "+a"(pl[1]), [p2] "+a"(pl[2]), [d] "+v"(dr)
+                 : [n0] "v"(pn[0]), [n1] "v"(pn[1]), [n2] "v"(pn[2]), [da] "v"(dda), [db] "v"(ddb));
+}
+// p_{N-1} = pterm - prod (admm.cpp:83-84), for the lanes of the region
+__device__ __forceinline__ void region_sub(float &dst, float x, float y) { asm volatile("v_sub_f32 %0, %1, %2" : "+v"(dst) : "v"(x), "v"(y)); }
 
 // closed loop on chip: the lanes in `m` (instances that CONVERGED: the reference returned before v = vnew, admm.cpp:135-142) get their old
 // slack back from the backup, so that the next solve's first sweep finds v | z where every sweep expects the previous slack
@@ -500,6 +562,7 @@ __global__ __launch_bounds__(WAVE * TILE16_WAVES, 1) void admm_tile16_kernel(con
 {
     static_assert(!(MPC && (BR || XR)), "the closed loop on chip is instantiated for batch-shared bounds and a shared / windowed reference");
     constexpr int NX = 12, NU = 4;
+    constexpr bool HEAD = EXACT && COLD && !MPC && !BR && !XR; // the headline instantiation: its sweeps run under one narrowed EXEC each (exec_narrow)
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, g = lane >> 4, c = lane & 15;
     const int ntiles = (P.batch + 15) >> 4;
     const float rho = P.rho;
@@ -734,8 +797,9 @@ __global__ __launch_bounds__(WAVE * TILE16_WAVES, 1) void admm_tile16_kernel(con
         {
         int row;
         // (same-box A/B, 65 536 tracking instances: warm start 1.78 -> 1.71 ms, fma 0.874 -> 0.860, closed loop on chip 1.040 -> 1.030 / 0.540 -> 0.502; the
-        //  exact cold-start instantiation alone loses 0.8 % — two more scratch accesses per iteration at the allocator's cliff — and keeps the clamp)
-        if constexpr (TINY_T16_PADTAB && !(EXACT && COLD && !MPC && !BR && !XR)) row = (ws < tab_rows - 1 ? ws : tab_rows - 1) + i; // rows wc .. wc + N - 1 exist
+        //  exact cold-start instantiation alone lost 0.8 % then — two more scratch accesses per iteration at the allocator's cliff — and kept the clamp
+        //  until its sweeps ran under one EXEC region each: TINY_T16_HEADPAD)
+        if constexpr (TINY_T16_PADTAB && !(EXACT && COLD && !MPC && !BR && !XR && !TINY_T16_HEADPAD)) row = (ws < tab_rows - 1 ? ws : tab_rows - 1) + i; // rows wc .. wc + N - 1 exist
         else { row = ws + i; row = row < tab_rows ? row : tab_rows - 1; }
         const float4 t4 = tb[row * 4 + (gsel >= 0 ? gsel : g)];
         return f32x4{t4.x, t4.y, t4.z, t4.w};
@@ -891,13 +955,25 @@ __global__ __launch_bounds__(WAVE * TILE16_WAVES, 1) void admm_tile16_kernel(con
             for (int k = 0; k < DB - 1; k++) dma_b(k, 0.f, 0.f);
         }
         // The arithmetic of a sweep runs for all 16 columns (the MFMAs are wave-wide); only the state updates of a
-        // converged instance are masked, which freezes it exactly where the reference returns.
+        // converged instance are masked, which freezes it exactly where the reference returns.  (HEAD: the whole sweep runs for the
+        // columns still iterating only — exec_narrow below —, which freezes the others just the same.)
         // ---------------- forward sweep: forward_pass + update_slack + update_dual + residual maxima ----------------
         // Software pipelined by one step (round 3): step i issues its LDS reads (bounds, old slack) and its three product MFMAs,
         // then runs the slack / dual / residual arithmetic of step i - 1 while those are in flight, then sums the products.
+        unsigned long long exec_fw = 0ull;
+        if constexpr (HEAD) exec_fw = exec_narrow(amask); // the whole sweep for the instances still iterating only
         float s[3] = {x0[0], x0[1], x0[2]};
         float pri_x = 0.f, dua_x = 0.f, pri_u = 0.f, dua_u = 0.f;
         auto elementwise = [&](int i, const f32x4 &sv, const float4 &lo, const float4 &hi, const float4 &ol) {
+            // (HEAD: ONE counted wait for the three LDS reads of this step — bounds and old slack, issued a step ago, in front of the three reads of
+            //  the next step that are in flight now — where hipcc places two, lgkmcnt(4) and lgkmcnt(3), eight instructions apart; it sees the
+            //  statement and drops its own)
+            if constexpr (HEAD && TINY_T16_HEADWAIT)
+            {
+                if (i == N - 1) __builtin_amdgcn_s_waitcnt(0xC07F); // lgkmcnt(0): the last step, nothing behind it
+                else __builtin_amdgcn_s_waitcnt(0xC37F);            // lgkmcnt(3)
+                __builtin_amdgcn_sched_barrier(0);                   // (the statement alone is not held in place)
+            }
             const f32x4 old = {ol.x, ol.y, ol.z, ol.w};
             const f32x4 tp = sv + dual4(i);                                        // admm.cpp:47-48
             f32x4 t;
@@ -916,10 +992,16 @@ __global__ __launch_bounds__(WAVE * TILE16_WAVES, 1) void admm_tile16_kernel(con
 #pragma unroll
                 for (int v = 0; v < 3; v++)
                 {
+                    if constexpr (HEAD) region_sub(pN[v], pterm[v], rho * (t[v] - an[v])); // lin_cost's last operation, over the old value
+                    else
+                    {
                     const float pn_ = lin_cost<EXACT>(pterm[v], rho, t[v] - an[v]); // admm.cpp:83-84
                     pN[v] = active ? pn_ : pN[v];
+                    }
                 }
             }
+            if constexpr (HEAD) region_forward_update(a[i], tp, bo[i], old, sn_addr, i * (WAVE * 16), t);
+            else
             masked_forward_update(amask, a[i], tp, bo[i], old, sn_addr + i * (WAVE * 16), t); // a = tp - t (:69-70), slack, backup
         };
         f32x4 sv_p = {0.f, 0.f, 0.f, 0.f};
@@ -950,6 +1032,7 @@ __global__ __launch_bounds__(WAVE * TILE16_WAVES, 1) void admm_tile16_kernel(con
             s[0] = xn[0]; s[1] = xn[1]; s[2] = xn[2];
         }
         elementwise(N - 1, sv_p, lo_p, hi_p, ol_p);
+        if constexpr (HEAD) exec_restore(exec_fw);
         // ---------------- termination_condition (admm.cpp:91-109) ----------------
         pri_x = tile_inst_max(pri_x); dua_x = tile_inst_max(dua_x);
         pri_u = tile_inst_max(pri_u); dua_u = tile_inst_max(dua_u);
@@ -971,6 +1054,8 @@ __global__ __launch_bounds__(WAVE * TILE16_WAVES, 1) void admm_tile16_kernel(con
         {
             float p[3] = {pN[0], pN[1], pN[2]};
             const unsigned long long amask = __ballot(active);
+            unsigned long long exec_bw = 0ull;
+            if constexpr (HEAD) exec_bw = exec_narrow(amask);
             // the linear cost of step i - 1 depends on the state only, not on p: it is computed while the products of step i
             // are in flight
             auto load_lin = [&](int i, float4 &sl, f32x4 &xr) { // LDS reads of step i's linear cost: issued a step ahead, in front of the MFMAs
@@ -1009,16 +1094,28 @@ __global__ __launch_bounds__(WAVE * TILE16_WAVES, 1) void admm_tile16_kernel(con
                 if constexpr (EXACT) __builtin_amdgcn_sched_barrier(0);
 #endif
                 f32x4 lin_n = lin;
+                if constexpr (HEAD && TINY_T16_HEADWAIT) // one wait for the step's two LDS reads (slack, reference row) instead of lgkmcnt(1) and lgkmcnt(0)
+                    if (i > 0) { __builtin_amdgcn_s_waitcnt(0xC07F); __builtin_amdgcn_sched_barrier(0); }
                 if (i > 0) lin_n = make_lin(i - 1, sl_n, xr_n); // in the shadow of the four MFMAs, not behind the sums
 #if TINY_T16_SCHED
                 if constexpr (EXACT) __builtin_amdgcn_sched_barrier(0);
 #endif
                 float pn[3], dd;
+                if constexpr (HEAD)
+                {
+                    float ddb;
+                    M.template riccati_finish<true>(F, lin, pn, dd, &ddb);
+                    region_backward_update(pl[i], dr[i], pn, dd, ddb);
+                }
+                else
+                {
                 M.riccati_finish(F, lin, pn, dd);
                 masked_backward_update(amask, pl[i], dr[i], pn, dd);
+                }
                 p[0] = pn[0]; p[1] = pn[1]; p[2] = pn[2];
                 lin = lin_n;
             }
+            if constexpr (HEAD) exec_restore(exec_bw);
         }
     }
     if (!MPC || ms + 1 >= P.mpc_steps) break;
