@@ -49,12 +49,18 @@ constexpr int OPT_AHEAD = 4;
 // SIM = true (with MPC; admm_rowsim.hip): the plant step between two solves of the on-chip loop uses the plant's own rows S.plant (one table or one per
 // instance; NULL: the model's), adds the disturbance row S.w and records the state in S.x_traj (tinympc_internal.h: SimParams).  The rows are loaded
 // once per MPC step into transient registers (L2 resident): nothing is held across the iteration loop.
-template <int NX, int NU, int N, bool EXACT, bool H16, bool MPC, bool BPI, bool D32, bool OPT, bool PM, bool SIM = false>
-__device__ __forceinline__ void rowlane_body(const RowParams &P, const ModelParams &M, [[maybe_unused]] const SimParams &S = SimParams{})
+// PS = true (per-instance settings, tiny_batch_set_instance_settings; admm_rowlane_ps.hip): tolerances, max_iter and check_termination of a row come from
+// that instance's record SP.rec[inst], loaded once at entry into four registers.  The iteration loop keeps its wave-uniform bound — P.max_iter is then the
+// LARGEST budget of the batch — and a row whose own budget is used up only leaves `active`, behind the backward sweep of its last permitted iteration, as
+// a converged row does behind its check: the four rows of a wave end on different iterations, the 16 lanes of a row always together.
+template <int NX, int NU, int N, bool EXACT, bool H16, bool MPC, bool BPI, bool D32, bool OPT, bool PM, bool SIM = false, bool PS = false>
+__device__ __forceinline__ void rowlane_body(const RowParams &P, const ModelParams &M, [[maybe_unused]] const SimParams &S = SimParams{},
+                                             [[maybe_unused]] const SettingsParams &SP = SettingsParams{})
 {
     static_assert(!SIM || (MPC && !H16 && !BPI && !D32 && !OPT), "the simulated loop is instantiated where the on-chip loop is: fp32 storage, shared bounds");
     static_assert(!OPT || (!H16 && !MPC && !BPI && !D32), "the optional terms are instantiated for fp32 storage, shared bounds, one solve per launch");
     static_assert(!PM || (!H16 && !D32 && !OPT), "per-instance models are instantiated for fp32 storage without the optional terms");
+    static_assert(!PS || (!H16 && !D32 && !OPT && !PM && !SIM), "per-instance settings are instantiated for fp32 storage, the shared model, no optional terms, no plant");
     constexpr bool HD = H16 && !D32; // storage precision of the duals (gy)
     const int lane = threadIdx.x;
     const int r16 = lane & 15;
@@ -141,6 +147,10 @@ __device__ __forceinline__ void rowlane_body(const RowParams &P, const ModelPara
     float pterm = terminal_term<NX, NU, EXACT, H16>(mats, r16, xrN);
 
     SolveFrame F(P, inst, valid);
+    // this row's settings (PS): one 16-byte load per lane, the same record in the 16 lanes of a row.  (Every other instantiation goes on naming P where it
+    // reads a setting: one view object bound to either moved their code.)
+    [[maybe_unused]] InstSettings my{};
+    if constexpr (PS) my = SP.rec[inst_a];
     float pN = 0.f; // p_{N-1} of the last executed forward sweep (x rows)
     bool ran_bwd = false;
 
@@ -150,14 +160,14 @@ __device__ __forceinline__ void rowlane_body(const RowParams &P, const ModelPara
     // An ordinary solve is mpc_steps == 1.
     for (int ms = 0;; ++ms)
     {
-    bool active = valid && (P.max_iter > 0);
+    bool active = valid && ((PS ? my.max_iter : P.max_iter) > 0);
     F.reset();
-    for (int it = 0; it < P.max_iter; ++it)
+    for (int it = 0; it < P.max_iter; ++it) // (PS: the batch's largest budget — a wave-uniform bound; a row's own budget ends it through `active`)
     {
         if (!__any(active)) break;
         // the last permitted iteration must not overwrite d in registers: x,u of an instance that exhausts max_iter come
         // from the d its last forward sweep used (regenerated in the epilogue); the final d itself is kept in pd[]
-        const bool keep_d = (it == P.max_iter - 1);
+        const bool keep_d = (it == (PS ? my.max_iter : P.max_iter) - 1);
         if (active)
         {
             // ---------------- forward sweep: forward_pass + update_slack + update_dual + residual maxima ----------------
@@ -204,7 +214,8 @@ __device__ __forceinline__ void rowlane_body(const RowParams &P, const ModelPara
             // termination_condition (admm.cpp:91-109).  (The status is read back, not the value check() returns, and further down max_iter is
             // tested in front of no_iterations(), so that the lead flag is formed behind the test: either way the fma N = 50 instantiations, which
             // sit at 256 registers, spill one or two registers less — what their scratch is pinned at.)
-            F.check(P, it, pri, dua, is_x, is_u, rho);
+            if constexpr (PS) F.check(my, it, pri, dua, is_x, is_u, rho);
+            else F.check(P, it, pri, dua, is_x, is_u, rho);
             if (F.solved()) active = false;
             else
             {
@@ -244,6 +255,7 @@ __device__ __forceinline__ void rowlane_body(const RowParams &P, const ModelPara
                     pd[i] = is_u ? dd : pn;                // [p_i ; d_i] of this sweep (live-out only: stays in registers)
                     p = pn;
                 }
+                if constexpr (PS) active = !keep_d; // this row's budget is used up: it sits out the iterations its neighbours still run
             }
         }
     }
@@ -303,7 +315,11 @@ __device__ __forceinline__ void rowlane_body(const RowParams &P, const ModelPara
     }
     }
 
-    if (P.max_iter <= 0 && F.no_iterations(P, inst, valid && r16 == 0)) return;
+    if constexpr (PS)
+    {
+        if (my.max_iter <= 0 && F.no_iterations(my, P, inst, valid && r16 == 0)) return; // this row only: its neighbours in the wave go on to their live-out
+    }
+    else if (P.max_iter <= 0 && F.no_iterations(P, inst, valid && r16 == 0)) return;
 
     // ---------------- live-out: every work array written once ----------------
     if (valid)
@@ -358,7 +374,40 @@ __global__ __launch_bounds__(WAVE, (N > 32 && EXACT) ? 1 : 2) void admm_rowlane_
     rowlane_body<NX, NU, N, EXACT, false, MPC, BPI, false, false, true>(P, M);
 }
 
-#ifdef TINY_ROWSIM_UNIT
+#if defined(TINY_ROWLANE_PS_UNIT)
+// Per-instance settings: the PS instantiations of the body and their launcher, compiled as admm_rowlane_ps.hip (a translation unit of its own, so that the
+// kernels above keep their code).  fp32 storage; one solve with shared or per-instance bounds, or the on-chip closed loop (shared bounds), logs included.
+template <int NX, int NU, int N, bool EXACT, bool MPC, bool BPI>
+__global__ __launch_bounds__(WAVE, (N > 32 && EXACT) ? 1 : 2) void admm_rowlane_ps_kernel(const RowParams P, const SettingsParams SP)
+{
+    rowlane_body<NX, NU, N, EXACT, false, MPC, BPI, false, false, false, false, true>(P, ModelParams{}, SimParams{}, SP);
+}
+
+hipError_t launch_admm_rowlane_ps(int nx, int nu, int N, bool exact, const RowParams &P, const SettingsParams &SP, hipStream_t stream)
+{
+    const int nblocks = (P.batch + 3) / 4;
+    const bool mpc = P.mpc_steps > 1, bpi = P.bounds_inst_stride != 0;
+    if (!SP.rec || P.dual32 || (mpc && bpi) || P.uref != nullptr || P.en_d2p) return hipErrorInvalidValue;
+#define TINY_ROWLANE_PS_LAUNCH(NX, NU, NN, EX, MP, BP) \
+    hipLaunchKernelGGL((admm_rowlane_ps_kernel<NX, NU, NN, EX, MP, BP>), dim3(nblocks), dim3(WAVE), 0, stream, P, SP)
+#define TINY_ROWLANE_PS_FLAGS(NX, NU, NN, EX)                              \
+    do                                                                     \
+    {                                                                      \
+        if (mpc) TINY_ROWLANE_PS_LAUNCH(NX, NU, NN, EX, true, false);      \
+        else if (bpi) TINY_ROWLANE_PS_LAUNCH(NX, NU, NN, EX, false, true); \
+        else TINY_ROWLANE_PS_LAUNCH(NX, NU, NN, EX, false, false);         \
+    } while (0)
+#define TINY_ROWLANE_PS_DISPATCH(NX, NU, NN)                \
+    if (nx == NX && nu == NU && N == NN)                    \
+    {                                                       \
+        if (exact) TINY_ROWLANE_PS_FLAGS(NX, NU, NN, true); \
+        else TINY_ROWLANE_PS_FLAGS(NX, NU, NN, false);      \
+        return hipGetLastError();                           \
+    }
+    TINY_FOR_EACH_ROWLANE(TINY_ROWLANE_PS_DISPATCH)
+    return hipErrorInvalidValue;
+}
+#elif defined(TINY_ROWSIM_UNIT)
 // The simulated closed loop: the SIM instantiations of the body and their launcher, compiled as admm_rowsim.hip (a translation unit of its own, so that
 // the kernels above keep their code).  fp32 storage and shared bounds, exactly where MPC is instantiated.
 template <int NX, int NU, int N, bool EXACT>
@@ -460,6 +509,6 @@ hipError_t launch_admm_rowlane_pm(int nx, int nu, int N, bool exact, const RowPa
     TINY_FOR_EACH_ROWLANE(TINY_ROWLANE_PM_DISPATCH)
     return hipErrorInvalidValue;
 }
-#endif // TINY_ROWSIM_UNIT
+#endif // TINY_ROWLANE_PS_UNIT, TINY_ROWSIM_UNIT
 
 } // namespace tinympc

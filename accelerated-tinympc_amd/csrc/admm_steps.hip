@@ -30,12 +30,31 @@ __device__ __forceinline__ float cost_of(const RowParams &P, bool is_x, bool is_
     return -0.f;
 }
 
+// Both kernels of this file are compiled twice: here, with one set of settings for the launch (the settings view `my` of the frame is P), and as
+// admm_steps_ps.hip (TINY_STEPS_PS_UNIT) with per-instance settings: the kernels take a SettingsParams beside P, are named ..._ps_kernel, and `my` is the
+// row's own record SP.rec[inst], loaded once at entry.  The text of the bodies is one, so the two forms cannot drift apart; a kernel body behind a function
+// call instead moved this unit's code.
+#ifdef TINY_STEPS_PS_UNIT
+#define TINY_STEP_KERNEL admm_step_ps_kernel
+#define TINY_ROWSTREAM_KERNEL admm_rowstream_ps_kernel
+#define TINY_SETTINGS_ARG , const SettingsParams SP
+#define TINY_SETTINGS_VIEW const InstSettings my = SP.rec[valid ? inst : P.batch - 1]
+constexpr bool kPerInstanceSettings = true;
+#else
+#define TINY_STEP_KERNEL admm_step_kernel
+#define TINY_ROWSTREAM_KERNEL admm_rowstream_kernel
+#define TINY_SETTINGS_ARG
+#define TINY_SETTINGS_VIEW const RowParams &my = P
+constexpr bool kPerInstanceSettings = false;
+#endif
+
 template <int NX, int NU, bool EXACT, bool H16>
-__global__ __launch_bounds__(WAVE) void admm_step_kernel(const RowParams P, const int fn, int *__restrict__ conv_out)
+__global__ __launch_bounds__(WAVE) void TINY_STEP_KERNEL(const RowParams P TINY_SETTINGS_ARG, const int fn, int *__restrict__ conv_out)
 {
     const int lane = threadIdx.x, r16 = lane & 15;
     const int inst = blockIdx.x * 4 + (lane >> 4);
     const bool valid = inst < P.batch;
+    TINY_SETTINGS_VIEW;
     const bool is_x = r16 < NX, is_u = (r16 >= NX) && (r16 < NX + NU);
     const int N = P.N;
     const int rowbase = (inst * N) * 16 + r16;
@@ -93,7 +112,7 @@ __global__ __launch_bounds__(WAVE) void admm_step_kernel(const RowParams P, cons
     {
         bool conv = false;
         const int itn = valid ? P.iter[inst] : 1;
-        if (itn % P.check_termination == 0) // row-uniform
+        if (itn % my.check_termination == 0) // row-uniform
         {
             float pri = 0.f, dua = 0.f;
             for (int i = 0; i < N; i++)
@@ -104,7 +123,7 @@ __global__ __launch_bounds__(WAVE) void admm_step_kernel(const RowParams P, cons
             }
             RowResiduals res;
             res.measure(pri, dua, is_x, is_u, rho);
-            conv = res.below_tol(P);
+            conv = res.below_tol(my);
             if (valid && r16 == 0) res.store(P, inst);
         }
         if (valid && r16 == 0)
@@ -139,12 +158,15 @@ __global__ __launch_bounds__(WAVE) void admm_step_kernel(const RowParams P, cons
 // fallback for (nx, nu) classes whose N has no register-resident instantiation, and keeps exact mode bit-identical
 // to the reference there too.
 // ---------------------------------------------------------------------------------------------------------------------
+// Per-instance settings (see above): the loop bound P.max_iter is then the batch's largest budget, wave-uniform, and a row whose own budget is used up
+// leaves `active` behind its last backward sweep, as a converged row does behind its check (see admm_rowlane.hip)
 template <int NX, int NU, bool EXACT, bool H16>
-__global__ __launch_bounds__(WAVE) void admm_rowstream_kernel(const RowParams P)
+__global__ __launch_bounds__(WAVE) void TINY_ROWSTREAM_KERNEL(const RowParams P TINY_SETTINGS_ARG)
 {
     const int lane = threadIdx.x, r16 = lane & 15;
     const int inst = blockIdx.x * 4 + (lane >> 4);
     const bool valid = inst < P.batch;
+    TINY_SETTINGS_VIEW;
     const bool is_x = r16 < NX, is_u = (r16 >= NX) && (r16 < NX + NU);
     const int N = P.N;
     const int rowbase = (inst * N) * 16 + r16;
@@ -159,11 +181,11 @@ __global__ __launch_bounds__(WAVE) void admm_rowstream_kernel(const RowParams P)
     const float x0 = ldw<H16>(P.xu, rowbase);
     const float pterm = terminal_term<NX, NU, EXACT, H16>(P.mats, r16, xref.at(P, N - 1, r16));
     SolveFrame F(P, inst, valid);
-    bool active = valid && (P.max_iter > 0);
+    bool active = valid && (my.max_iter > 0);
     for (int it = 0; it < P.max_iter; ++it)
     {
         if (!__any(active)) break;
-        const bool last_iter = (it == P.max_iter - 1);
+        const bool last_iter = (it == my.max_iter - 1); // the iteration whose x, u an instance that uses up its budget keeps
         const bool zero_state = (it == 0) && (P.cold_start != 0);
         const bool zero_duals = (it == 0) && ((P.cold_start | P.duals_zero) != 0);
         if (active)
@@ -190,7 +212,7 @@ __global__ __launch_bounds__(WAVE) void admm_rowstream_kernel(const RowParams P)
             }
             const float pN = lin_cost<EXACT, H16>(pterm, rho, t1);
             stw<H16>(P.pd, rowbase + (N - 1) * 16, is_x ? pN : 0.f);
-            if (F.check(P, it, pri, dua, is_x, is_u, rho)) active = false;
+            if (F.check(my, it, pri, dua, is_x, is_u, rho)) active = false;
             else
             {
                 float p = pN;
@@ -207,10 +229,11 @@ __global__ __launch_bounds__(WAVE) void admm_rowstream_kernel(const RowParams P)
                     stw<H16>(P.vz, o, sni);
                     p = pn;
                 }
+                if constexpr (kPerInstanceSettings) active = !last_iter; // this row's budget is used up; its neighbours in the wave may go on
             }
         }
     }
-    if (F.no_iterations(P, inst, valid && r16 == 0)) return;
+    if (F.no_iterations(my, P, inst, valid && r16 == 0)) return; // (per-instance settings: this row only)
     {
         // live-out: q, r (admm.cpp:80-82) and, for converged instances, x,u regenerated from the frozen d
         const bool solved = F.solved();
@@ -239,6 +262,40 @@ __global__ __launch_bounds__(WAVE) void admm_rowstream_kernel(const RowParams P)
     }
 }
 
+#ifdef TINY_STEPS_PS_UNIT
+hipError_t launch_admm_rowstream_ps(int nx, int nu, bool exact, bool h16, const RowParams &P, const SettingsParams &SP, hipStream_t stream)
+{
+    const int nblocks = (P.batch + 3) / 4;
+    if (!SP.rec) return hipErrorInvalidValue;
+#define TINY_ROWSTREAM_PS_LAUNCH(NX, NU, EX, H) \
+    hipLaunchKernelGGL((admm_rowstream_ps_kernel<NX, NU, EX, H>), dim3(nblocks), dim3(WAVE), 0, stream, P, SP)
+#define TINY_ROWSTREAM_PS_DISPATCH(NX, NU)                                \
+    if (nx == NX && nu == NU)                                             \
+    {                                                                     \
+        TINY_FOR_EXACT_H16(exact, h16, TINY_ROWSTREAM_PS_LAUNCH, NX, NU); \
+        return hipGetLastError();                                         \
+    }
+    TINY_FOR_EACH_ROWDIMS(TINY_ROWSTREAM_PS_DISPATCH)
+    return hipErrorInvalidValue;
+}
+
+// termination_condition is the one step function that reads a setting the table of bounds does not carry
+hipError_t launch_admm_termination_ps(int nx, int nu, bool exact, bool h16, const RowParams &P, const SettingsParams &SP, int *conv_out, hipStream_t stream)
+{
+    const int nblocks = (P.batch + 3) / 4;
+    if (!SP.rec) return hipErrorInvalidValue;
+#define TINY_STEP_PS_LAUNCH(NX, NU, EX, H) \
+    hipLaunchKernelGGL((admm_step_ps_kernel<NX, NU, EX, H>), dim3(nblocks), dim3(WAVE), 0, stream, P, SP, (int)STEP_TERMINATION_CONDITION, conv_out)
+#define TINY_STEP_PS_DISPATCH(NX, NU)                               \
+    if (nx == NX && nu == NU)                                       \
+    {                                                               \
+        TINY_FOR_EXACT_H16(exact, h16, TINY_STEP_PS_LAUNCH, NX, NU); \
+        return hipGetLastError();                                   \
+    }
+    TINY_FOR_EACH_ROWDIMS(TINY_STEP_PS_DISPATCH)
+    return hipErrorInvalidValue;
+}
+#else
 hipError_t launch_admm_rowstream(int nx, int nu, bool exact, bool h16, const RowParams &P, hipStream_t stream)
 {
     const int nblocks = (P.batch + 3) / 4;
@@ -276,5 +333,7 @@ hipError_t launch_admm_step(int nx, int nu, bool exact, bool h16, int fn, const 
     TINY_FOR_EACH_ROWDIMS(TINY_ROWDIMS_DISPATCH)
     return hipErrorInvalidValue;
 }
+
+#endif // TINY_STEPS_PS_UNIT
 
 } // namespace tinympc

@@ -52,6 +52,9 @@ hipError_t launch_systems_to_models(const double *rho, const double *K, const do
                                     const double *Bm, const double *Q, float *dst, int batch, int nx, int nu, hipStream_t stream);
 hipError_t launch_bounds_table(const float *xmin, const float *xmax, const float *umin, const float *umax, int sh_x, int sh_u, float *dst, const Geo &g,
                                int nb, int en_state, int en_input, int h16, int *zero_ties, hipStream_t stream);
+// the same table with the two bound flags per instance (en_state[nb], en_input[nb]: tiny_batch_set_instance_settings); settings_helpers.hip
+hipError_t launch_bounds_table_ps(const float *xmin, const float *xmax, const float *umin, const float *umax, int sh_x, int sh_u, float *dst, const Geo &g,
+                                  int nb, const int *en_state, const int *en_input, int h16, int *zero_ties, hipStream_t stream);
 hipError_t launch_tile16_image(const float4 *src, float4 *dst, int nb, int N, int pieces, long long inst_stride_f4, hipStream_t stream);
 hipError_t launch_rows_vary(const float2 *bounds, const float *xref, int nb, int N, int nx, int nu, int *vary, hipStream_t stream);
 

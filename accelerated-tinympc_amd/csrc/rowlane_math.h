@@ -393,6 +393,10 @@ struct RowXref
     __device__ __forceinline__ void advance(const RowParams &P) { wstart += P.window_advance; }
 };
 
+// The settings view of the frame: the four TinySettings values a solve reads (types.hpp:39-47) — abs_pri_tol, abs_dua_tol, max_iter, check_termination — as
+// members of whatever the caller hands over.  Every kernel with one set of settings for the launch hands over its RowParams, read where the frame uses them
+// (a view type with accessor functions over P moved the code of the unrolled kernels); the ",ps" instantiations hand over the instance's record (tinympc_internal.h:
+// InstSettings), loaded once at their entry (tiny_batch_set_instance_settings).
 // The four residual fields of TinyWorkspace, res[4 * inst + 0..3] = primal state | primal input | dual state | dual input.
 struct RowResiduals
 {
@@ -410,9 +414,10 @@ struct RowResiduals
         set(pri_x, dua_x, pri_u, dua_u, rho);
     }
     // admm.cpp:100-103
-    __device__ __forceinline__ bool below_tol(const RowParams &P) const
+    template <class S>
+    __device__ __forceinline__ bool below_tol(const S &s) const
     {
-        return (ps < P.abs_pri_tol) && (pi < P.abs_pri_tol) && (ds < P.abs_dua_tol) && (di < P.abs_dua_tol);
+        return (ps < s.abs_pri_tol) && (pi < s.abs_pri_tol) && (ds < s.abs_dua_tol) && (di < s.abs_dua_tol);
     }
     __device__ __forceinline__ void load(const RowParams &P, int inst) { ps = P.res[4 * inst + 0]; pi = P.res[4 * inst + 1]; ds = P.res[4 * inst + 2]; di = P.res[4 * inst + 3]; }
     __device__ __forceinline__ void store(const RowParams &P, int inst) const { P.res[4 * inst + 0] = ps; P.res[4 * inst + 1] = pi; P.res[4 * inst + 2] = ds; P.res[4 * inst + 3] = di; }
@@ -431,33 +436,36 @@ struct SolveFrame
     // top of every solve of the on-chip closed loop (admm.cpp:114-115): the residual fields carry over, as in the workspace
     __device__ __forceinline__ void reset() { st = TINY_STATUS_UNSOLVED_; itn = 1; }
     // admm.cpp:120 and termination_condition (admm.cpp:91-109, 135-136) after the forward sweep of iteration `it`, from the
-    // residuals `now` the kernel measured there; true: converged
-    __device__ __forceinline__ bool judge(const RowParams &P, int it, const RowResiduals &now)
+    // residuals `now` the kernel measured there; true: converged.  `s`: the settings view (P: the batch's one set)
+    template <class S>
+    __device__ __forceinline__ bool judge(const S &s, int it, const RowResiduals &now)
     {
         itn = it + 1;
         bool conv = false;
-        if ((it + 1) % P.check_termination == 0)
+        if ((it + 1) % s.check_termination == 0)
         {
             res = now;
-            conv = res.below_tol(P);
+            conv = res.below_tol(s);
         }
         if (conv) st = TINY_STATUS_SOLVED_;
         return conv;
     }
     // the same for 16 lanes per instance, from the per-lane maxima
-    __device__ __forceinline__ bool check(const RowParams &P, int it, float pri, float dua, bool is_x, bool is_u, float rho)
+    template <class S>
+    __device__ __forceinline__ bool check(const S &s, int it, float pri, float dua, bool is_x, bool is_u, float rho)
     {
         RowResiduals now;
         now.measure(pri, dua, is_x, is_u, rho);
-        return judge(P, it, now);
+        return judge(s, it, now);
     }
     __device__ __forceinline__ bool solved() const { return st == TINY_STATUS_SOLVED_; }
     // step boundary of the on-chip closed loop: iter and status of the solve that just finished into row ms of the logs (one lane per instance calls)
     __device__ __forceinline__ void log(const RowParams &P, int ms, int inst) const { log_step(P, ms, inst, itn, st); }
     // max_iter <= 0: tiny_solve only sets status and iter (admm.cpp:114-117,151).  true: the kernel returns, nothing else is written
-    __device__ __forceinline__ bool no_iterations(const RowParams &P, int inst, bool lead) const
+    template <class S>
+    __device__ __forceinline__ bool no_iterations(const S &s, const RowParams &P, int inst, bool lead) const
     {
-        if (P.max_iter > 0) return false;
+        if (s.max_iter > 0) return false;
         if (lead)
         {
             P.status[inst] = TINY_STATUS_UNSOLVED_;
@@ -466,6 +474,7 @@ struct SolveFrame
         }
         return true;
     }
+    __device__ __forceinline__ bool no_iterations(const RowParams &P, int inst, bool lead) const { return no_iterations(P, P, inst, lead); }
     // live-out of the frame: residual fields, status, iter and the batch's count of unsolved instances
     __device__ __forceinline__ void store(const RowParams &P, int inst) const
     {

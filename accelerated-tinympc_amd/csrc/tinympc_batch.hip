@@ -213,6 +213,17 @@ struct TinyBatch
     float *plant_A = nullptr, *plant_B = nullptr, *plant_rows = nullptr;
     float *sim_stage[5] = {};      // tiny_batch_mpc_run_log's device copies of w, u0_traj, x_traj, iter_log, status_log: kept between calls (sized_buffer), so that their
     size_t sim_stage_n[5] = {};    // addresses, which the captured graph bakes in, hold from call to call
+    // per-instance settings (tiny_batch_set_instance_settings).  The caller's arrays as given (empty: NULL, the field follows tiny_batch_set_settings); the records
+    // the ps kernels read ([bpad4] InstSettings: admm_rowlane_ps.hip, admm_steps_ps.hip) and, where the bound flags differ between instances, the two flag
+    // arrays the bounds table is built from ([2][batch]); the largest and smallest budget; the flags' value where they are uniform over the batch
+    bool ps = false;
+    std::vector<float> ps_pri, ps_dua;
+    std::vector<int> ps_max_iter, ps_check, ps_en_state, ps_en_input;
+    InstSettings *ps_dev = nullptr;
+    int *ps_flags_dev = nullptr;
+    int ps_budget_max = 0, ps_budget_min = 0;
+    bool ps_flags_vary = false;
+    int ps_en_state_all = 0, ps_en_input_all = 0;
     bool h16 = false; // ROW-layout arrays, Xref and bounds stored as IEEE binary16 (tiny_batch_set_storage)
     bool dual32 = false; // with h16: the duals pair gy IS fp32 right now (the state of the array)
     bool dual32_pref = false;   // tiny_batch_set_storage(tb, 16): fp32 duals wherever the kernel a call resolves to implements them, 16-bit duals elsewhere
@@ -455,8 +466,17 @@ int dispatch_effective(const TinyBatch *tb)
     return tb->cold_pending ? 1 : (tb->iter_history ? 2 : 0);
 }
 
+// The settings as a solve of the whole batch sees them.  With per-instance settings (TinyBatch::ps): the largest budget bounds the launch's iteration loop
+// (RowParams::max_iter), the smallest decides whether some instance runs no iteration; the bound flags are the arrays' common value where they have one
+int budget_max(const TinyBatch *tb) { return tb->ps ? tb->ps_budget_max : tb->max_iter; }
+int budget_min(const TinyBatch *tb) { return tb->ps ? tb->ps_budget_min : tb->max_iter; }
+int state_bound_on(const TinyBatch *tb) { return tb->ps ? tb->ps_en_state_all : tb->en_state_bound; }
+int input_bound_on(const TinyBatch *tb) { return tb->ps ? tb->ps_en_input_all : tb->en_input_bound; }
+
+// one {lo, hi} table serves the batch: the bound inputs are shared, and so are the bound flags (per-instance settings can make them differ)
 bool bounds_all_shared(const TinyBatch *tb)
 {
+    if (tb->ps && tb->ps_flags_vary) return false;
     for (int k = 0; k < 4; k++)
         if (tb->in_bnd[k].set && !tb->in_bnd[k].shared) return false;
     return true;
@@ -635,10 +655,15 @@ int prepare_inputs(TinyBatch *tb, int layout)
             if (!tb->zero_ties_dev) TRY(dev_alloc_zero((float **)&tb->zero_ties_dev, 1));
             HIP_TRY(hipMemsetAsync(tb->zero_ties_dev, 0, sizeof(int), tb->stream));
             const InputArr *in = tb->in_bnd;
-            HIP_TRY(launch_bounds_table(in[0].set ? in[0].dev : nullptr, in[1].set ? in[1].dev : nullptr, in[2].set ? in[2].dev : nullptr,
-                                        in[3].set ? in[3].dev : nullptr, (in[0].set ? in[0].shared : in[1].shared) ? 1 : 0,
-                                        (in[2].set ? in[2].shared : in[3].shared) ? 1 : 0, tb->r_bounds, geo(tb), tb->batch, tb->en_state_bound,
-                                        tb->en_input_bound, tb->h16 ? 1 : 0, tb->zero_ties_dev, tb->stream));
+            const float *src[4];
+            for (int k = 0; k < 4; k++) src[k] = in[k].set ? in[k].dev : nullptr;
+            const int sh_x = (in[0].set ? in[0].shared : in[1].shared) ? 1 : 0, sh_u = (in[2].set ? in[2].shared : in[3].shared) ? 1 : 0;
+            if (tb->ps && tb->ps_flags_vary) // the flags per instance (settings_helpers.hip); zero_ties sees the folded table as below
+                HIP_TRY(launch_bounds_table_ps(src[0], src[1], src[2], src[3], sh_x, sh_u, tb->r_bounds, geo(tb), tb->batch, tb->ps_flags_dev,
+                                               tb->ps_flags_dev + tb->batch, tb->h16 ? 1 : 0, tb->zero_ties_dev, tb->stream));
+            else
+                HIP_TRY(launch_bounds_table(src[0], src[1], src[2], src[3], sh_x, sh_u, tb->r_bounds, geo(tb), tb->batch, state_bound_on(tb),
+                                            input_bound_on(tb), tb->h16 ? 1 : 0, tb->zero_ties_dev, tb->stream));
             int h = 0;
             HIP_TRY(hipMemcpyAsync(&h, tb->zero_ties_dev, sizeof h, hipMemcpyDeviceToHost, tb->stream));
             HIP_TRY(hipStreamSynchronize(tb->stream));
@@ -652,12 +677,12 @@ int prepare_inputs(TinyBatch *tb, int layout)
             for (int r = 0; r < RW; r++)
             {
                 float lo = -inf, hi = inf;
-                if (r < nx && tb->en_state_bound)
+                if (r < nx && state_bound_on(tb))
                 {
                     lo = tb->in_bnd[0].set ? tb->in_bnd[0].host[(size_t)i * nx + r] : 0.f;
                     hi = tb->in_bnd[1].set ? tb->in_bnd[1].host[(size_t)i * nx + r] : 0.f;
                 }
-                else if (r >= nx && r < nx + nu && i < N - 1 && tb->en_input_bound)
+                else if (r >= nx && r < nx + nu && i < N - 1 && input_bound_on(tb))
                 {
                     lo = tb->in_bnd[2].set ? tb->in_bnd[2].host[(size_t)i * nu + (r - nx)] : 0.f;
                     hi = tb->in_bnd[3].set ? tb->in_bnd[3].host[(size_t)i * nu + (r - nx)] : 0.f;
@@ -696,7 +721,7 @@ int prepare_inputs(TinyBatch *tb, int layout)
         // per-instance tables of the class the sixteen-instances-per-wave kernel serves: do they change along the horizon? (one pass, at set time)
         tb->rows_vary = 3u;
         const bool xper = tb->xref_mode != 1 && tb->in_xref.set && !tb->in_xref.shared;
-        if (tb->tile16_ok && !tb->h16 && tb->rw == 16 && (!bounds_all_shared(tb) || xper))
+        if (tb->tile16_ok && !tb->ps && !tb->h16 && tb->rw == 16 && (!bounds_all_shared(tb) || xper)) // (per-instance settings never reach tile16)
         {
             if (!tb->rows_vary_dev) TRY(dev_alloc_zero((float **)&tb->rows_vary_dev, 2));
             HIP_TRY(hipMemsetAsync(tb->rows_vary_dev, 0, 2 * sizeof(int), tb->stream));
@@ -808,6 +833,7 @@ struct KernelPlan
     Kernel kernel = Kernel::Rowlane;
     bool exact = true;   // arithmetic: the reference's summation order, or fma
     bool pm = false;     // per-instance models (the ",pm" instantiations of the 16-lane, the two wave and the run-time-dimension kernel)
+    bool ps = false;     // per-instance settings (the ",ps" instantiations of the 16-lane and the streaming row kernel: admm_rowlane_ps.hip, admm_steps_ps.hip)
     bool pi = false;     // tile16 with per-instance bounds / reference (admm_tile16_pi.hip)
     Tile16Pi pi_tables{}; // ... and which of its tables go through the rings
     Loop loop = Loop::None;
@@ -886,6 +912,35 @@ int plan_of(const TinyBatch *tb, const Call &call, int v, Kernel row, KernelPlan
 int resolve_plan(const TinyBatch *tb, const Call &call, KernelPlan *out)
 {
     int v = tb->variant;
+    if (tb->ps)
+    {
+        // per-instance settings: the two kernels with a ",ps" form — the unrolled 16-lane kernel where (nx, nu, N) is instantiated, under fp32 storage and
+        // without the optional terms (shared or per-instance bounds), the streaming row kernel for everything else with nx + nu <= 16, with the same bits.
+        // Nothing else is chosen: tile16 runs sixteen instances in lock step on one set of settings (a launch of its size goes to the 16-lane kernel), the
+        // cartpole class leaves the quad kernel for rowlane<4,1,N,..,ps>
+        if (tb->pm)
+            return fail(TINY_BATCH_EUNSUPPORTED, "per-instance settings (tiny_batch_set_instance_settings) are not implemented together with per-instance models "
+                                                 "(tiny_batch_clear_models() or tiny_batch_clear_instance_settings())");
+        if (!tb->rowmath_ok)
+            return fail(TINY_BATCH_EUNSUPPORTED, "per-instance settings are implemented by the 16-lane row kernels only (a compiled nx + nu <= 16): nx=%d nu=%d runs on a wave, "
+                                                 "tile48, generic or streaming MFMA kernel, which hold one set of settings per launch (tiny_batch_clear_instance_settings())", tb->nx, tb->nu);
+        if (v == VAR_STREAM || v == VAR_GENERIC)
+            return fail(TINY_BATCH_EUNSUPPORTED, "per-instance settings are implemented by the row variants only (tiny_batch_select_kernel 0, 2 or 3): variant %d holds one set "
+                                                 "of settings per launch", v);
+        const std::optional<Kernel> forced = tb->row_family_forced;
+        if (forced && forced != Kernel::Rowlane && forced != Kernel::Rowstream)
+            return fail(TINY_BATCH_EUNSUPPORTED, "the forced row kernel %s (tiny_batch_set_row_kernel) has no per-instance-settings form: only the 16-lane kernel (1), the "
+                                                 "streaming row kernel (3) or auto (0) serve tiny_batch_set_instance_settings", traits(*forced).name);
+        const bool unrolled = tb->row_dims_ok && !tb->h16 && !tb->en_uref && !tb->en_d2p && forced != Kernel::Rowstream;
+        out->kernel = unrolled ? Kernel::Rowlane : Kernel::Rowstream;
+        out->exact = v != VAR_ROW_FAST;
+        out->pm = out->pi = false;
+        out->ps = true;
+        out->sim = call.sim;
+        // the on-chip loop's ps instantiations: shared bounds, no plant, logs included; every other run replays the one-solve kernel
+        out->loop = !call.run() ? Loop::None : (unrolled && bounds_all_shared(tb) && !call.sim ? Loop::OnChip : Loop::Replay);
+        return 0;
+    }
     if (tb->pm)
     {
         // per-instance models: the unrolled 16-lane kernel where (nx, nu, N) is instantiated, the run-time-dimension kernel otherwise (both read a gain
@@ -960,7 +1015,7 @@ int resolve_plan(const TinyBatch *tb, const Call &call, KernelPlan *out)
     return plan_of(tb, call, v, row, out);
 }
 
-// the name tiny_batch_kernel_name() reports: "<family><nx,nu[,N],arithmetic[,h16 | ,h16d | ,pi | ,pm]>"; the streaming kernel is named by its chunk counts
+// the name tiny_batch_kernel_name() reports: "<family><nx,nu[,N],arithmetic[,h16 | ,h16d | ,pi | ,pm][,ps]>"; the streaming kernel is named by its chunk counts
 std::string kernel_name(const TinyBatch *tb, const KernelPlan &pl)
 {
     const KernelTraits &t = traits(pl.kernel);
@@ -974,7 +1029,7 @@ std::string kernel_name(const TinyBatch *tb, const KernelPlan &pl)
     if (t.name_has_N) n += snprintf(nm + n, sizeof nm - n, ",%d", tb->N);
     const bool d32 = tb->dual32_forced ? tb->dual32 : (tb->dual32_pref && t.fp32_duals);
     const char *suffix = pl.pm ? ",pm" : pl.pi ? ",pi" : (t.name_has_storage && tb->h16) ? (d32 ? ",h16d" : ",h16") : "";
-    snprintf(nm + n, sizeof nm - n, ",%s%s>", pl.exact ? "exact" : "fast", suffix);
+    snprintf(nm + n, sizeof nm - n, ",%s%s%s>", pl.exact ? "exact" : "fast", suffix, pl.ps ? ",ps" : "");
     return nm;
 }
 
@@ -1034,15 +1089,15 @@ void invalidate_graph(TinyBatch *tb)
 std::string graph_signature(const TinyBatch *tb, const KernelPlan &pl, const RunArgs &run)
 {
     char sig[768];
-    snprintf(sig, sizeof sig, "%d|%p|%p|%p|%p|%p|%p|%p|%p|%p|%d|%d|%d|%s|%d|%d|%g|%g|%d|%d|%p|%p|%p|%d|%p|%p|%p|%p|%d%d|%a|%d%d%d|%d%d|%d|%p|%p|%p|%d|%p|%p", tb->plant_mode, (void *)tb->plant_A,
+    snprintf(sig, sizeof sig, "%d|%p|%p|%p|%p|%p|%p|%p|%p|%p|%d|%d|%d|%s|%d|%d|%g|%g|%d|%d|%p|%p|%p|%d|%p|%p|%p|%p|%d%d|%a|%d%d%d|%d%d|%d|%p|%p|%p|%d|%p|%p|%p|%d", tb->plant_mode, (void *)tb->plant_A,
              (void *)tb->plant_B, (const void *)run.d_w, (void *)run.d_x_traj, (void *)tb->pm_src, (void *)tb->pm_row[0],
              (void *)tb->pm_row[1], (void *)tb->pm_wave[0], (void *)tb->pm_wave[1], run.steps, run.window_advance, tb->variant, kernel_name(tb, pl).c_str(), tb->max_iter,
              tb->check_termination, (double)tb->abs_pri_tol, (double)tb->abs_dua_tol, tb->xref_mode, tb->table_rows, (void *)tb->pair[0],
              (void *)tb->arr[0], (void *)tb->r_bounds, (int)tb->h16, (void *)tb->stream, (void *)run.d_u0_traj, (void *)tb->r_xref,
              (void *)tb->r_uref, (int)tb->en_uref, (int)tb->en_d2p, (double)tb->rho, (int)bounds_all_shared(tb),
-             (int)(tb->in_xref.set && tb->in_xref.shared), (int)(tb->in_uref.set && tb->in_uref.shared), tb->en_state_bound, tb->en_input_bound,
+             (int)(tb->in_xref.set && tb->in_xref.shared), (int)(tb->in_uref.set && tb->in_uref.shared), state_bound_on(tb), input_bound_on(tb),
              tb->dispatch_mode, (void *)tb->order_dev, (void *)tb->mats_exact, (void *)tb->xref_start, (int)tb->zero_ties,
-             (void *)run.d_iter_log, (void *)run.d_status_log);
+             (void *)run.d_iter_log, (void *)run.d_status_log, (void *)tb->ps_dev, budget_max(tb));
     return sig;
 }
 
@@ -1073,7 +1128,7 @@ void fill_row_params(TinyBatch *tb, RowParams &P, bool exact)
 {
     P.nx = tb->nx; P.nu = tb->nu; P.N = tb->N; P.batch = tb->batch;
     P.rho = tb->rho; P.abs_pri_tol = tb->abs_pri_tol; P.abs_dua_tol = tb->abs_dua_tol;
-    P.max_iter = tb->max_iter; P.check_termination = tb->check_termination;
+    P.max_iter = budget_max(tb); P.check_termination = tb->check_termination; // (per-instance settings: the loop bound of the launch; the kernel reads the rest per instance)
     P.duals_zero = tb->duals_zero_pending ? 1 : 0;
     P.cold_start = tb->cold_pending ? 1 : 0;
     P.xref_mode = tb->xref_mode;
@@ -1127,7 +1182,10 @@ int run_step(TinyBatch *tb, int fn, int *converged_host, int *n_true)
     RowParams P;
     fill_row_params(tb, P, tb->variant != VAR_ROW_FAST);
     HIP_TRY(hipMemsetAsync(tb->n_unsolved, 0, 2 * sizeof(int), tb->stream)); // [0] unsolved count, [1] tile queue of admm_tile16.hip
-    hipError_t e = launch_admm_step(tb->nx, tb->nu, tb->variant != VAR_ROW_FAST, tb->h16, fn, P, tb->conv_dev, tb->stream);
+    // (per-instance settings: termination_condition reads the instance's record; update_slack sees the bound flags through the table; the rest read no setting)
+    hipError_t e = tb->ps && fn == STEP_TERMINATION_CONDITION
+                       ? launch_admm_termination_ps(tb->nx, tb->nu, tb->variant != VAR_ROW_FAST, tb->h16, P, SettingsParams{tb->ps_dev}, tb->conv_dev, tb->stream)
+                       : launch_admm_step(tb->nx, tb->nu, tb->variant != VAR_ROW_FAST, tb->h16, fn, P, tb->conv_dev, tb->stream);
     if (e != hipSuccess) return fail(TINY_BATCH_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
     if (fn == STEP_TERMINATION_CONDITION)
     {
@@ -1235,7 +1293,7 @@ int prepare_solve(TinyBatch *tb, const Call &call, KernelPlan *plan)
     TRY(settle_dual_width(tb, traits(pl.kernel).fp32_duals));
     TRY(prepare_inputs(tb, layout));
     TRY(flush_x0_zero(tb)); // every solve reads x.col(0)
-    if (tb->max_iter <= 0) TRY(flush_pending(tb));
+    if (budget_min(tb) <= 0) TRY(flush_pending(tb)); // an instance that runs no iteration must read back as the reset left it
     // A cold start that converges in its first iteration (x0 at the origin) runs no backward sweep, which is what writes p, d, v, z.
     // reset_workspace() is folded into the launch by every fused kernel: the register-resident ones start from zero registers,
     // the streaming ones (MFMA, rowstream, wavestream) read zeros in their first iteration and zero-fill p, d, v, z of such an
@@ -1287,12 +1345,13 @@ int enqueue_dispatch_order(TinyBatch *tb, const KernelPlan &pl, int run_steps, b
     // a run's tiles / groups go longest first by the counts of the solve before it (the last step of the previous run): a tile's total over the steps
     // of a run spreads 150 ... 700 iterations around a mean of 280 (65 536 tracking instances, 20 steps) and four tiles per wave slot in index order end
     // 33 % above even slots; ordered by the previous step's counts 15 % (tests/fuzz/sim_history_dispatch.py)
-    const bool history = eligible && dispatch_effective(tb) == 2 && (run || tb->max_iter > 1);
+    const bool history = eligible && dispatch_effective(tb) == 2 && (run || budget_max(tb) > 1);
     // a run that starts from a reset workspace goes by the predictor of its first, cold solve (which is also its longest: 22 iterations against 11): steps 0 - 19
     // of the tracking loop, makespan 1 522 iterations in index order, 1 299 by the predictor (by the true first-step counts 1 291; 16-lane kernel 2 336 -> 2 175)
     const bool want_predicted = run ? (tb->dispatch_mode == 1 || (tb->dispatch_mode == -1 && from_reset)) : dispatch_effective(tb) == 1;
     // (per-instance models: the predictor sweep reads the shared fma gains, which are unset or stale there — such a launch keeps index order)
-    const bool predicted = eligible && want_predicted && !history && !pl.pm && !tb->dual32 && tb->max_iter > 1;
+    // (per-instance settings: the predictor assumes one tolerance and one budget for the batch — index order)
+    const bool predicted = eligible && want_predicted && !history && !pl.pm && !pl.ps && !tb->dual32 && tb->max_iter > 1;
     if (traits(pl.kernel).order_unit_solve == 16) P.order = nullptr; // a caller's order lists groups of four instances, not tiles of sixteen
     // tile16 from a reset workspace: tiles formed from instances of one window start; the predictor's keys are then those tiles' keys
     P.inst_map = (!run && tb->tile_map && tile_grouping_wanted(tb, pl)) ? tb->tile_map : nullptr;
@@ -1316,7 +1375,8 @@ int enqueue_dispatch_order(TinyBatch *tb, const KernelPlan &pl, int run_steps, b
 hipError_t launch_kernel(const TinyBatch *tb, const KernelPlan &pl, RowParams &P, const SimParams *S)
 {
     const int nx = tb->nx, nu = tb->nu, N = tb->N;
-    if (S && pl.kernel != Kernel::Rowlane) return hipErrorInvalidValue;
+    if (S && (pl.kernel != Kernel::Rowlane || pl.ps)) return hipErrorInvalidValue;
+    if (pl.ps && pl.kernel != Kernel::Rowlane && pl.kernel != Kernel::Rowstream) return hipErrorInvalidValue; // a missing ps kernel is an error, never another kernel
     switch (pl.kernel)
     {
     case Kernel::Rowlane:
@@ -1325,9 +1385,12 @@ hipError_t launch_kernel(const TinyBatch *tb, const KernelPlan &pl, RowParams &P
             const ModelParams M = pl.pm ? model_params(tb, pl) : ModelParams{};
             return launch_admm_rowsim(nx, nu, N, pl.exact, P, pl.pm ? &M : nullptr, *S, tb->stream);
         }
+        if (pl.ps) return launch_admm_rowlane_ps(nx, nu, N, pl.exact, P, SettingsParams{tb->ps_dev}, tb->stream);
         return pl.pm ? launch_admm_rowlane_pm(nx, nu, N, pl.exact, P, model_params(tb, pl), tb->stream) : launch_admm_rowlane(nx, nu, N, pl.exact, tb->h16, P, tb->stream);
     case Kernel::Rowloop: return launch_admm_rowloop(nx, nu, pl.exact, tb->h16, P, tb->stream);
-    case Kernel::Rowstream: return launch_admm_rowstream(nx, nu, pl.exact, tb->h16, P, tb->stream);
+    case Kernel::Rowstream:
+        if (pl.ps) return launch_admm_rowstream_ps(nx, nu, pl.exact, tb->h16, P, SettingsParams{tb->ps_dev}, tb->stream);
+        return launch_admm_rowstream(nx, nu, pl.exact, tb->h16, P, tb->stream);
     case Kernel::Wavestream: return pl.pm ? launch_admm_wavestream_pm(nx, nu, P, model_params(tb, pl), tb->stream) : launch_admm_wavestream(nx, nu, P, tb->stream);
     case Kernel::Quadlane: return launch_admm_quadlane(N, pl.exact, tb->h16, P, tb->stream);
     case Kernel::Waveres: return pl.pm ? launch_admm_waveres_pm(nx, nu, pl.exact, P, model_params(tb, pl), tb->stream) : launch_admm_waveres(nx, nu, pl.exact, P, tb->stream);
@@ -1398,7 +1461,7 @@ int enqueue_solve(TinyBatch *tb, const KernelPlan &pl, bool record_events, const
         tb->ev_valid = true;
     }
     // consumed by the kernel's first iteration; iter[] now holds this launch's counts (a run's: its last solve's)
-    if (tb->max_iter > 0) { tb->duals_zero_pending = tb->cold_pending = false; tb->iter_history = true; }
+    if (budget_max(tb) > 0) { tb->duals_zero_pending = tb->cold_pending = false; tb->iter_history = true; }
     return 0;
 }
 
@@ -1427,6 +1490,43 @@ int enqueue_plant_step(TinyBatch *tb, int window_advance, const float *d_w, floa
     a.g = geo(tb);
     a.h16 = h16_of(tb, tb->layout);
     HIP_TRY(launch_plant_step(a, tb->stream));
+    return 0;
+}
+
+// Per-instance settings: the device records and flag arrays from the caller's arrays and, for a field given as NULL, the batch's value; the budgets' range and
+// the flags' uniformity for the host's decisions.  Called by tiny_batch_set_instance_settings and, while they are in force, by tiny_batch_set_settings
+int rebuild_instance_settings(TinyBatch *tb)
+{
+    TRY(set_device(tb));
+    invalidate_graph(tb);
+    HIP_TRY(hipStreamSynchronize(tb->stream)); // a launch still reading the old records may be in flight
+    const int B = tb->batch;
+    std::vector<InstSettings> rec((size_t)tb->bpad4, InstSettings{0.f, 0.f, 0, 1}); // (the padding rows of the last wave run nothing)
+    std::vector<int> flags(2 * (size_t)B);
+    for (int b = 0; b < B; b++)
+    {
+        rec[b].abs_pri_tol = tb->ps_pri.empty() ? tb->abs_pri_tol : tb->ps_pri[b];
+        rec[b].abs_dua_tol = tb->ps_dua.empty() ? tb->abs_dua_tol : tb->ps_dua[b];
+        rec[b].max_iter = tb->ps_max_iter.empty() ? tb->max_iter : tb->ps_max_iter[b];
+        rec[b].check_termination = tb->ps_check.empty() ? tb->check_termination : tb->ps_check[b];
+        flags[b] = (tb->ps_en_state.empty() ? tb->en_state_bound : tb->ps_en_state[b]) ? 1 : 0;
+        flags[(size_t)B + b] = (tb->ps_en_input.empty() ? tb->en_input_bound : tb->ps_en_input[b]) ? 1 : 0;
+    }
+    tb->ps_budget_max = tb->ps_budget_min = rec[0].max_iter;
+    tb->ps_flags_vary = false;
+    for (int b = 1; b < B; b++)
+    {
+        tb->ps_budget_max = std::max(tb->ps_budget_max, rec[b].max_iter);
+        tb->ps_budget_min = std::min(tb->ps_budget_min, rec[b].max_iter);
+        if (flags[b] != flags[0] || flags[(size_t)B + b] != flags[B]) tb->ps_flags_vary = true;
+    }
+    tb->ps_en_state_all = flags[0]; tb->ps_en_input_all = flags[B]; // read only while the flags are uniform
+    if (!tb->ps_dev) HIP_TRY(guarded_malloc((void **)&tb->ps_dev, rec.size() * sizeof(InstSettings)));
+    HIP_TRY(hipMemcpy(tb->ps_dev, rec.data(), rec.size() * sizeof(InstSettings), hipMemcpyHostToDevice));
+    if (!tb->ps_flags_dev) HIP_TRY(guarded_malloc((void **)&tb->ps_flags_dev, flags.size() * sizeof(int)));
+    HIP_TRY(hipMemcpy(tb->ps_flags_dev, flags.data(), flags.size() * sizeof(int), hipMemcpyHostToDevice));
+    tb->ps = true;
+    tb->derived_dirty[LAYOUT_ROW] = true; // the bound flags are folded into the {lo, hi} table
     return 0;
 }
 
@@ -1537,6 +1637,7 @@ void tiny_batch_destroy(TinyBatch *tb)
     (void)guarded_free(tb->pm_src); (void)guarded_free(tb->pm_rho); (void)guarded_free(tb->pm_row[0]); (void)guarded_free(tb->pm_row[1]);
     (void)guarded_free(tb->pm_wave[0]); (void)guarded_free(tb->pm_wave[1]);
     (void)guarded_free(tb->plant_A); (void)guarded_free(tb->plant_B); (void)guarded_free(tb->plant_rows);
+    (void)guarded_free(tb->ps_dev); (void)guarded_free(tb->ps_flags_dev);
     for (float *p : tb->sim_stage) (void)guarded_free(p);
     (void)guarded_free(tb->dA); (void)guarded_free(tb->dB); (void)guarded_free(tb->x0buf); (void)guarded_free(tb->staging); (void)guarded_free(tb->conv_dev);
     if (tb->graph_exec) (void)hipGraphExecDestroy(tb->graph_exec);
@@ -1913,7 +2014,46 @@ int tiny_batch_set_settings(TinyBatch *tb, float abs_pri_tol, float abs_dua_tol,
     tb->max_iter = max_iter; tb->check_termination = check_termination;
     tb->en_state_bound = en_state_bound; tb->en_input_bound = en_input_bound;
     tb->have_settings = true; // tolerances, max_iter, check_termination and the bound flags are in the graph signature
+    return tb->ps ? rebuild_instance_settings(tb) : 0; // (the fields a per-instance call left NULL follow the batch's values)
+}
+
+int tiny_batch_set_instance_settings(TinyBatch *tb, const float *abs_pri_tol, const float *abs_dua_tol, const int *max_iter, const int *check_termination,
+                                     const int *en_state_bound, const int *en_input_bound)
+{
+    CHECK_TB(tb);
+    if (!tb->have_settings) return fail(TINY_BATCH_ENOTREADY, "tiny_batch_set_instance_settings: tiny_batch_set_settings must be called first (a NULL field keeps its value)");
+    if (check_termination)
+        for (int b = 0; b < tb->batch; b++)
+            if (check_termination[b] < 1)
+                return fail(TINY_BATCH_EINVAL, "check_termination[%d] = %d: must be >= 1 (the reference computes iter %% check_termination, admm.cpp:93)", b, check_termination[b]);
+    const size_t B = (size_t)tb->batch;
+    auto take = [B](auto &dst, const auto *src) { if (src) dst.assign(src, src + B); else dst.clear(); };
+    take(tb->ps_pri, abs_pri_tol); take(tb->ps_dua, abs_dua_tol);
+    take(tb->ps_max_iter, max_iter); take(tb->ps_check, check_termination);
+    take(tb->ps_en_state, en_state_bound); take(tb->ps_en_input, en_input_bound);
+    return rebuild_instance_settings(tb);
+}
+
+int tiny_batch_clear_instance_settings(TinyBatch *tb)
+{
+    CHECK_TB(tb);
+    if (!tb->ps) return 0;
+    TRY(set_device(tb));
+    invalidate_graph(tb);
+    HIP_TRY(hipStreamSynchronize(tb->stream)); // a launch still reading the records may be in flight
+    (void)guarded_free(tb->ps_dev); tb->ps_dev = nullptr;
+    (void)guarded_free(tb->ps_flags_dev); tb->ps_flags_dev = nullptr;
+    for (std::vector<float> *v : {&tb->ps_pri, &tb->ps_dua}) v->clear();
+    for (std::vector<int> *v : {&tb->ps_max_iter, &tb->ps_check, &tb->ps_en_state, &tb->ps_en_input}) v->clear();
+    tb->ps = tb->ps_flags_vary = false;
+    tb->derived_dirty[LAYOUT_ROW] = true; // the bounds table is the batch flags' again
     return 0;
+}
+
+int tiny_batch_settings_per_instance(TinyBatch *tb)
+{
+    CHECK_TB(tb);
+    return tb->ps ? 1 : 0;
 }
 
 int tiny_batch_set_x0(TinyBatch *tb, const float *x0)
@@ -2293,7 +2433,7 @@ int mpc_run_sim(TinyBatch *tb, RunArgs run)
 {
     if (run.steps < 1) return fail(TINY_BATCH_EINVAL, "%s: steps must be >= 1", run.who);
     TRY(check_loop_args(tb, run.who, "mpc_run", run.window_advance));
-    if (tb->max_iter <= 0) return fail(TINY_BATCH_EINVAL, "%s needs max_iter > 0", run.who);
+    if (budget_min(tb) <= 0) return fail(TINY_BATCH_EINVAL, tb->ps ? "%s needs max_iter > 0 for every instance" : "%s needs max_iter > 0", run.who);
     TRY(set_device(tb));
     if (tb->xref_mode == 1 && run.window_advance) tb->tile_map_dirty = true; // either loop slides xref_start[] (the on-chip one writes it back)
     run.from_reset = tb->cold_pending; // (flush_pending materialises the zeros and clears the flag: the run's first solve is the cold one all the same)

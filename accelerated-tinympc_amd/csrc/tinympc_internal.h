@@ -191,6 +191,19 @@ struct SimParams
     const float *w = nullptr;
     float *x_traj = nullptr;
 };
+// Per-instance settings (tiny_batch_set_instance_settings): a kernel argument of its own of the ",ps" instantiations (admm_rowlane_ps.hip, admm_steps_ps.hip),
+// beside RowParams, whose layout stays as it is.  One 16-byte record per instance, [batch padded to 4], loaded once per instance at kernel entry: the four
+// TinySettings members a solve reads (types.hpp:39-47).  The two bound flags never reach a kernel: the host folds them into the {lo, hi} table.  RowParams'
+// own four values are not read by a ps kernel, except P.max_iter, which carries the batch's LARGEST budget: the wave-uniform bound of the iteration loop.
+struct InstSettings // (the members' names are RowParams': either is a settings view of the solve frame, rowlane_math.h)
+{
+    float abs_pri_tol, abs_dua_tol;
+    int max_iter, check_termination;
+};
+struct SettingsParams
+{
+    const InstSettings *rec = nullptr;
+};
 __host__ __device__ inline int plant_row_floats(int nx, int nu) { return (nx + nu) * 16; }
 // floats of one instance's record in the two forms
 __host__ __device__ inline int pm_row_floats(int nx, int nu) { return (3 * nx + 2 * nu + 1) * 16; }
@@ -230,6 +243,12 @@ hipError_t launch_admm_rowlane_pm(int nx, int nu, int N, bool exact, const RowPa
 // the on-chip closed loop (P.mpc_steps > 1) against a separate plant, with a disturbance and the state trajectory (admm_rowsim.hip: the SIM instantiations
 // of the same body): fp32 storage, shared bounds; M = NULL: the batch-shared model, else per-instance models
 hipError_t launch_admm_rowsim(int nx, int nu, int N, bool exact, const RowParams &P, const ModelParams *M, const SimParams &S, hipStream_t stream);
+// the same body with per-instance settings (admm_rowlane_ps.hip): fp32 storage, no optional terms, the batch-shared model; one solve with shared or
+// per-instance bounds, or the on-chip closed loop (P.mpc_steps > 1) with shared bounds.  P.max_iter = the largest budget of the batch
+hipError_t launch_admm_rowlane_ps(int nx, int nu, int N, bool exact, const RowParams &P, const SettingsParams &SP, hipStream_t stream);
+// ... and the streaming row kernel and the termination_condition step with them (admm_steps_ps.hip): every (nx, nu) of TINY_FOR_EACH_ROWDIMS, any N
+hipError_t launch_admm_rowstream_ps(int nx, int nu, bool exact, bool h16, const RowParams &P, const SettingsParams &SP, hipStream_t stream);
+hipError_t launch_admm_termination_ps(int nx, int nu, bool exact, bool h16, const RowParams &P, const SettingsParams &SP, int *conv_out, hipStream_t stream);
 bool rowdims_supported(int nx, int nu);
 hipError_t launch_admm_rowstream(int nx, int nu, bool exact, bool h16, const RowParams &P, hipStream_t stream);
 hipError_t launch_admm_step(int nx, int nu, bool exact, bool h16, int fn, const RowParams &P, int *conv_out, hipStream_t stream);

@@ -86,6 +86,7 @@ def load_library(build_if_missing: bool = False) -> C.CDLL:
         "tiny_riccati": [C.c_int, C.c_int, D, D, D, D, C.c_double, D, D, D, D, D, I],
         "tiny_batch_set_models": [P, F, F, F, F, F, F, F, F], "tiny_batch_set_models_device": [P, P, P, P, P, P, P, P, P],
         "tiny_batch_clear_models": [P], "tiny_batch_models_per_instance": [P],
+        "tiny_batch_set_instance_settings": [P, F, F, I, I, I, I], "tiny_batch_clear_instance_settings": [P], "tiny_batch_settings_per_instance": [P],
         "tiny_batch_riccati_device": [C.c_int, C.c_int, C.c_int, P, P, P, P, P, P, P, P, P, P, P, P],
         "tiny_batch_set_systems": [P, D, D, D, D, D, I],
         "tiny_batch_set_plant": [P, F, F, C.c_int], "tiny_batch_clear_plant": [P], "tiny_batch_plant_mode": [P],
@@ -358,6 +359,24 @@ class TinyBatchSolver:
                              en_input_bound=en_input_bound)
         self._check(self.lib.tiny_batch_set_settings(self._h, abs_pri_tol, abs_dua_tol, max_iter, check_termination,
                                                      en_state_bound, en_input_bound))
+
+    # -- per-instance settings (tiny_batch_set_instance_settings) ----------------------------------
+    def set_instance_settings(self, abs_pri_tol=None, abs_dua_tol=None, max_iter=None, check_termination=None, en_state_bound=None, en_input_bound=None):
+        """Every instance its own TinySettings: each argument is an array [B], a scalar (broadcast over the batch) or None (the field keeps the value of
+        set_settings).  Served by rowlane<...,ps> / rowstream<...,ps> (nx + nu <= 16); replaces any earlier per-instance settings."""
+        def arr(v, dt):
+            return None if v is None else np.ascontiguousarray(np.broadcast_to(np.asarray(v, dt), (self.B,)))
+        f = [arr(v, np.float32) for v in (abs_pri_tol, abs_dua_tol)]
+        i = [arr(v, np.int32) for v in (max_iter, check_termination, en_state_bound, en_input_bound)]
+        self._check(self.lib.tiny_batch_set_instance_settings(self._h, *[None if a is None else _fp(a) for a in f],
+                                                              *[None if a is None else a.ctypes.data_as(C.POINTER(C.c_int)) for a in i]))
+
+    def clear_instance_settings(self):
+        """Back to the batch's one set of set_settings."""
+        self._check(self.lib.tiny_batch_clear_instance_settings(self._h))
+
+    def settings_per_instance(self) -> bool:
+        return bool(self._check(self.lib.tiny_batch_settings_per_instance(self._h)))
 
     # -- wrapper twins (tiny_wrapper.hpp:14-23) ------------------------------------------------
     def set_x0(self, x0):

@@ -408,6 +408,27 @@ extern "C"
     int tiny_batch_clear_models(TinyBatch *tb);
     /* 1 while per-instance models are in force, 0 otherwise */
     int tiny_batch_models_per_instance(TinyBatch *tb);
+
+    /* ---- per-instance settings: every instance its own TinySettings -----------------------------------------------------
+     * TinySettings (types.hpp:39-47) per instance.  Every pointer is a host array [batch] or NULL; NULL = that field stays the batch's value from
+     * tiny_batch_set_settings (which must have been called; a later tiny_batch_set_settings moves the NULL fields with it).  The call replaces any earlier
+     * per-instance settings, drops a captured closed-loop graph and rebuilds the bounds table.  check_termination[b] < 1: TINY_BATCH_EINVAL, the message names
+     * the first such index (the batch setter's rule, admm.cpp:93); tolerances are compared with `<` as in the reference (admm.cpp:100-103), any float goes.
+     * From then on every solve entry point — tiny_batch_solve[_async], tiny_batch_mpc_step*, tiny_batch_mpc_run*, tiny_batch_termination_condition, and
+     * tiny_batch_update_slack through the bound flags — treats instance b bit for bit as tiny_solve treats a solver with instance b's TinySettings.
+     * max_iter[b] <= 0: status 11, iter 1, counted unsolved, nothing else of that instance is written; tiny_batch_mpc_run* then returns TINY_BATCH_EINVAL.
+     * tiny_batch_solve returns 1 if any instance used up its own budget.  Bound flags that differ between instances make the {lo, hi} table per instance.
+     * Kernels: "rowlane<nx,nu,N,arith,ps>" where (nx, nu, N) has an unrolled instantiation (fp32 storage, no optional terms; shared or per-instance
+     * bounds; the on-chip closed loop with shared bounds and no plant), "rowstream<nx,nu,arith[,h16],ps>" for every other compiled nx + nu <= 16.
+     * TINY_BATCH_EUNSUPPORTED with a message: nx + nu > 16, per-instance models, a forced row kernel without a ps form (rowloop, quadlane, tile16),
+     * the streaming MFMA and run-time-dimension variants.  The longest-first predictor assumes batch-wide settings: a cold start keeps index order. */
+    int tiny_batch_set_instance_settings(TinyBatch *tb, const float *abs_pri_tol, const float *abs_dua_tol, const int *max_iter,
+                                         const int *check_termination, const int *en_state_bound, const int *en_input_bound);
+    /* back to the batch's one set of tiny_batch_set_settings: kernels, kernel names and results are what they were */
+    int tiny_batch_clear_instance_settings(TinyBatch *tb);
+    /* 1 while per-instance settings are in force, 0 otherwise */
+    int tiny_batch_settings_per_instance(TinyBatch *tb);
+
     /* tiny_riccati for `count` independent systems on the device, fp64, bitwise equal per system.  Per system: A [nx*nx], B [nx*nu] column-major,
      * Q [nx], R [nu], rho; outputs as tiny_riccati, [count][...] each; coeff_d2p may be NULL.  iters[i] = tiny_riccati's *iters, or -1 where
      * tiny_riccati would return TINY_BATCH_EINVAL (singular); such a system's outputs are not written.  Device pointers; runs on hip_stream
