@@ -17,7 +17,7 @@ CSRC = PKG / "csrc"
 LIB = PKG / "lib" / "libtinympc_hip.so"
 WRAPPER_LIB = PKG / "lib" / "libtinympc_wrapper.so"  # same-name twin of the reference's generated wrapper library
 WRAPPER64_LIB = PKG / "lib" / "libtinympc_wrapper64.so"  # the native names (tiny_solve, forward_pass, ...) for tinytype = double
-SOURCES = ["tinympc_batch.hip", "batch_helpers.hip", "tinympc_batch64.hip", "batch64_helpers.hip", "admm_f64_thread.hip", "admm_f64_rows.hip", "admm_f64_rowsim.hip", "admm_f64_plant.hip", "admm_f64_rows_pm.hip", "admm_f64_rowsim_pm.hip", "admm_f64_thread_pm.hip", "admm_stream.hip", "admm_generic.hip", "admm_rowlane.hip", "admm_rowsim.hip", "admm_rowlane_ps.hip", "admm_rowloop.hip", "admm_quadlane.hip", "admm_tile16.hip", "admm_tile16_pi.hip", "admm_wave.hip", "admm_wave_pm.hip", "admm_waveres.hip", "admm_waveres_pm.hip", "admm_tile48.hip", "admm_steps.hip", "admm_steps_ps.hip", "settings_helpers.hip", "dispatch_order.hip", "riccati.cpp", "riccati_batch.hip"]
+SOURCES = ["tinympc_batch.hip", "batch_helpers.hip", "tinympc_batch64.hip", "batch64_helpers.hip", "admm_f64_thread.hip", "admm_f64_rows.hip", "admm_f64_rowsim.hip", "admm_f64_plant.hip", "admm_f64_rows_pm.hip", "admm_f64_rowsim_pm.hip", "admm_f64_thread_pm.hip", "admm_f64_rows_ps.hip", "admm_f64_rowloop_ps.hip", "admm_f64_thread_ps.hip", "admm_stream.hip", "admm_generic.hip", "admm_rowlane.hip", "admm_rowsim.hip", "admm_rowlane_ps.hip", "admm_rowloop.hip", "admm_quadlane.hip", "admm_tile16.hip", "admm_tile16_pi.hip", "admm_wave.hip", "admm_wave_pm.hip", "admm_waveres.hip", "admm_waveres_pm.hip", "admm_tile48.hip", "admm_steps.hip", "admm_steps_ps.hip", "settings_helpers.hip", "dispatch_order.hip", "riccati.cpp", "riccati_batch.hip"]
 WRAPPER_SRCS = [CSRC / "wrapper_compat.cpp", CSRC / "admm_compat.cpp"]
 HEADERS = [CSRC / "tinympc_internal.h", CSRC / "batch_helpers.h", CSRC / "eigen_orders.h", CSRC / "rowlane_math.h", CSRC / "tile_math.h", CSRC / "wave_math.h", CSRC / "dpp_ops_gen.h", CSRC / "f64_internal.h", CSRC / "f64_math.h", PKG.parent / "include" / "tinympc_batch.h", PKG.parent / "include" / "tinympc_batch64.h"]
 # -ffp-contract=off : exact arithmetic must not fuse a*b+c; the fast paths call fma explicitly
@@ -39,6 +39,7 @@ EXTRA_FLAGS = {"admm_tile16.hip": _T16_FLAGS, "admm_tile16_pi.hip": _T16_FLAGS,
 INCLUDED_SOURCES = {"admm_tile16_pi.hip": ["admm_tile16.hip"], "admm_rowsim.hip": ["admm_rowlane.hip"], "admm_rowlane_ps.hip": ["admm_rowlane.hip"],
                     "admm_steps_ps.hip": ["admm_steps.hip"], "admm_f64_rowsim.hip": ["admm_f64_rows.hip"],
                     "admm_f64_rows_pm.hip": ["admm_f64_rows.hip"], "admm_f64_rowsim_pm.hip": ["admm_f64_rows.hip"], "admm_f64_thread_pm.hip": ["admm_f64_thread.hip"],
+                    "admm_f64_rows_ps.hip": ["admm_f64_rows.hip"], "admm_f64_rowloop_ps.hip": ["admm_f64_rows.hip"], "admm_f64_thread_ps.hip": ["admm_f64_thread.hip"],
                     "admm_wave_pm.hip": ["admm_wave.hip"], "admm_waveres_pm.hip": ["admm_waveres.hip"]}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-slp-vectorize", "-fno-gpu-rdc"]
 
@@ -173,6 +174,10 @@ def kernel_isa_sha(kernel_name: str) -> str | None:
         src = "admm_f64_rowsim_pm.hip" if kernel_name.endswith((",mpc,pm>", ",sim,pm>")) else "admm_f64_rows_pm.hip"
     if src == "admm_f64_thread.hip" and kernel_name.endswith(",pm>"):
         src = "admm_f64_thread_pm.hip"
+    if src == "admm_f64_rows.hip" and kernel_name.endswith(",ps>"):  # and the fp64 per-instance-settings families: the on-chip closed loop, one solve
+        src = "admm_f64_rowloop_ps.hip" if kernel_name.endswith(",mpc,ps>") else "admm_f64_rows_ps.hip"
+    if src == "admm_f64_thread.hip" and kernel_name.endswith(",ps>"):
+        src = "admm_f64_thread_ps.hip"
     if src in ("admm_wave.hip", "admm_waveres.hip") and kernel_name.endswith(",pm>"):  # and the two wave kernels' per-instance-model instantiations
         src = src.replace(".hip", "_pm.hip")
     try:

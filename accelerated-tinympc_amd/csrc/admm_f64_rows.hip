@@ -1,7 +1,8 @@
-// admm_f64_rows.hip — the sixteen-lanes-per-instance kernel of the fp64 library, admm_f64_rows_kernel, with its launchers.  Compiled four times: as
+// admm_f64_rows.hip — the sixteen-lanes-per-instance kernel of the fp64 library, admm_f64_rows_kernel, with its launchers.  Compiled six times: as
 // itself (the one-solve and the MPC instantiations, launch_f64_rows), under TINY_F64SIM_UNIT as admm_f64_rowsim.hip (the SIM instantiations,
-// launch_rows64_sim) and, under TINY_F64PM_UNIT = 1 / 2, as admm_f64_rows_pm.hip / admm_f64_rowsim_pm.hip (per-instance models: one solve,
-// launch_f64_rows_pm / the closed loop, launch_rows64_loop_pm), so that the families build side by side.
+// launch_rows64_sim), under TINY_F64PM_UNIT = 1 / 2 as admm_f64_rows_pm.hip / admm_f64_rowsim_pm.hip (per-instance models: one solve,
+// launch_f64_rows_pm / the closed loop, launch_rows64_loop_pm) and, under TINY_F64PS_UNIT = 1 / 2, as admm_f64_rows_ps.hip / admm_f64_rowloop_ps.hip
+// (per-instance settings: one solve, launch_f64_rows_ps / the on-chip closed loop, launch_rows64_loop_ps), so that the families build side by side.
 #include "f64_math.h"
 
 namespace
@@ -22,6 +23,13 @@ __device__ __forceinline__ Models64 models_args(const Models64 &m) { return m; }
 __device__ __forceinline__ Models64 models_args(const Mpc64 &, const Sim64 &, const Models64 &m) { return m; }
 template <class... T>
 __device__ __forceinline__ Models64 models_args(const T &...) { return Models64{}; }
+// per-instance settings: a Settings64 as the last trailing argument, alone (one solve) or behind the Mpc64 (the on-chip closed loop)
+__device__ __forceinline__ Mpc64 loop_args(const Settings64 &) { return Mpc64{}; }
+__device__ __forceinline__ Mpc64 loop_args(const Mpc64 &l, const Settings64 &) { return l; }
+__device__ __forceinline__ Settings64 settings_args(const Settings64 &s) { return s; }
+__device__ __forceinline__ Settings64 settings_args(const Mpc64 &, const Settings64 &s) { return s; }
+template <class... T>
+__device__ __forceinline__ Settings64 settings_args(const T &...) { return Settings64{}; }
 
 // This lane's gain rows from its instance's record (Models64::rec), element for element what pack_row_gains lays out for the shared table: the x rows
 // read row r of Adyn, AmBKt, Bdyn, column r of Kinf and Pinf and Q(r), the u rows row m of Kinf, Quu_inv and column m of Bdyn; the other lanes zeros.
@@ -96,7 +104,12 @@ __global__ __launch_bounds__(WAVE64, (N <= 12 ? 2 : 1)) void admm_f64_rows_kerne
     // PM (the ",pm" instantiations, admm_f64_rows_pm.hip and admm_f64_rowsim_pm.hip): a Models64 as the last trailing argument.  The gain rows and rho
     // of a row are its instance's, read from the instance's record; `gains` is not read.  The closed loop with per-instance models is the SIM one
     constexpr bool PM = (false || ... || std::is_same<LOOP, Models64>::value);
-    constexpr int NLOOP = (int)sizeof...(LOOP) - (PM ? 1 : 0);
+    // SET (the ",ps" instantiations, admm_f64_rows_ps.hip and admm_f64_rowloop_ps.hip): a Settings64 as the last trailing argument.  The tolerances, the
+    // budget, check_termination and the two bound flags of a row are its instance's, read from the instance's record; of P's settings only max_iter is
+    // read, the batch's LARGEST budget: it bounds the iteration loop, which stays wave-uniform
+    constexpr bool SET = (false || ... || std::is_same<LOOP, Settings64>::value);
+    static_assert(!(PM && SET), "per-instance settings together with per-instance models are refused by the host");
+    constexpr int NLOOP = (int)sizeof...(LOOP) - (PM ? 1 : 0) - (SET ? 1 : 0);
     constexpr bool SIM = NLOOP == 2;
     static_assert(NLOOP == (MPC ? (SIM ? 2 : 1) : 0), "the closed-loop instantiations take one further argument, an Mpc64, the simulated ones a Sim64 behind it; the one-solve kernels none");
     static_assert(!SIM || MPC, "the simulated loop is the on-chip loop's");
@@ -104,6 +117,7 @@ __global__ __launch_bounds__(WAVE64, (N <= 12 ? 2 : 1)) void admm_f64_rows_kerne
     [[maybe_unused]] const Mpc64 L = loop_args(loop...);
     [[maybe_unused]] const Sim64 S = sim_args(loop...);
     [[maybe_unused]] const Models64 MO = models_args(loop...);
+    [[maybe_unused]] const Settings64 ST = settings_args(loop...);
     static_assert(!MPC || !(RT && N > 32), "the on-chip loop takes the workspace's d from the registers of [p ; d]");
     static_assert(NX + NU <= 16 && !(NX >= 8 && NU >= 8), "16-lane mapping; both dims >= 8 would take Eigen's GEMV kernel");
     static_assert(!RT || N > 20, "the runtime-horizon variant indexes the slack by the horizon: it keeps it in LDS");
@@ -120,6 +134,15 @@ __global__ __launch_bounds__(WAVE64, (N <= 12 ? 2 : 1)) void admm_f64_rows_kerne
     if constexpr (PM) rho_of_row = MO.rho[b];
     else rho_of_row = P.rho;
     const double rho = rho_of_row;
+    // This row's record, read again wherever it is needed (here, and once per iteration) through a lane index the compiler cannot see through, as the
+    // bounds' offset below: held instead, its eight words would be live across an iteration loop that already sits at 256 registers
+    [[maybe_unused]] auto my_settings = [&]() -> InstSettings64 {
+        int ia = inst;
+        asm volatile("" : "+v"(ia));
+        ia = valid ? ia : P.batch - 1;
+        return ST.rec[ia];
+    };
+    [[maybe_unused]] bool budget = true; // SET: this row's max_iter > 0.  A row without one runs along inactive and writes status and iter only
     // element (step, this lane's row) of the pair [x-type array ; u-type array]; u-type arrays have N - 1 steps
     auto ld = [&](int idx, int idu, int i) -> double {
         if (is_x) return P.arr[idx][((size_t)i * NX + row) * bp + b];
@@ -128,10 +151,19 @@ __global__ __launch_bounds__(WAVE64, (N <= 12 ? 2 : 1)) void admm_f64_rows_kerne
     };
     auto st = [&](int idx, int idu, int i, double v) {
         if (!valid) return;
+        if constexpr (SET) { if (!budget) return; }
         if (is_x) P.arr[idx][((size_t)i * NX + row) * bp + b] = v;
         else if (is_u && i < n - 1) P.arr[idu][((size_t)i * NU + row) * bp + b] = v;
     };
-    const bool en_b = is_x ? (P.en_state_bound != 0) : (is_u && P.en_input_bound != 0);
+    bool en_b_of_row;
+    if constexpr (SET)
+    {
+        const InstSettings64 my = my_settings();
+        en_b_of_row = is_x ? (my.en_state_bound != 0) : (is_u && my.en_input_bound != 0);
+        budget = my.max_iter > 0;
+    }
+    else en_b_of_row = is_x ? (P.en_state_bound != 0) : (is_u && P.en_input_bound != 0);
+    const bool en_b = en_b_of_row;
     // this lane's bounds of step i sit at pl0[i * bstep], ph0[i * bstep] (u rows have N - 1 steps; the other lanes read x row 0, unused)
     const size_t bstr = is_u ? (size_t)P.ub_stride : (size_t)P.xb_stride;
     const size_t boff = (size_t)row * bstr + (bstr > 1 ? b : 0);
@@ -218,6 +250,7 @@ __global__ __launch_bounds__(WAVE64, (N <= 12 ? 2 : 1)) void admm_f64_rows_kerne
     }
     int status = ST_UNSOLVED, itn = 1; // admm.cpp:114-115
     bool active = valid;
+    if constexpr (SET) active = valid && budget; // (a run on chip never meets a zero budget: the host sends it through the launch sequence)
     double pN = 0.0;
 
     [[maybe_unused]] int ms = 0; // the MPC step of the on-chip closed loop
@@ -231,7 +264,13 @@ next_solve: // (a label, not a loop around the solve: the one-solve instantiatio
         itn = active ? it + 1 : itn; // admm.cpp:120
         // the last permitted backward sweep must not overwrite d in c: x, u of an instance that exhausts max_iter come from
         // the d its last forward sweep used (regenerated below); the final d itself goes to pd
-        const bool keep_d = (it == P.max_iter - 1);
+        // (SET: the row's own last iteration, so that a row whose budget ends before the wave's regenerates x, u from the right d)
+        [[maybe_unused]] InstSettings64 my{};
+        if constexpr (SET) my = my_settings();
+        bool keep_d_of_row;
+        if constexpr (SET) keep_d_of_row = (it == my.max_iter - 1);
+        else keep_d_of_row = (it == P.max_iter - 1);
+        const bool keep_d = keep_d_of_row;
         // ---- forward_pass + update_slack + update_dual + residual maxima (admm.cpp:27-71, 95-98) ----
         double s = x0, pri = 0.0, dua = 0.0, t1 = 0.0;
         double lo[F64_AHEAD], hi[F64_AHEAD];
@@ -284,7 +323,14 @@ next_solve: // (a label, not a loop around the solve: the one-solve instantiatio
         const double pri_x = row_max(is_x ? pri : 0.0), dua_x = row_max(is_x ? dua : 0.0);
         const double pri_u = row_max(is_u ? pri : 0.0), dua_u = row_max(is_u ? dua : 0.0);
         bool conv = false;
-        if ((it + 1) % P.check_termination == 0) // admm.cpp:91-109 (wave-uniform condition)
+        if constexpr (SET)
+        {
+            // row-uniform, no longer wave-uniform: selects, not a divergent region (as every other update of a row's state)
+            const bool due = active && ((it + 1) % my.check_termination == 0);
+            r_ps = due ? pri_x : r_ps; r_ds = due ? dua_x * rho : r_ds; r_pi = due ? pri_u : r_pi; r_di = due ? dua_u * rho : r_di;
+            conv = due && (r_ps < my.abs_pri_tol) && (r_pi < my.abs_pri_tol) && (r_ds < my.abs_dua_tol) && (r_di < my.abs_dua_tol);
+        }
+        else if ((it + 1) % P.check_termination == 0) // admm.cpp:91-109 (wave-uniform condition)
         {
             r_ps = active ? pri_x : r_ps; r_ds = active ? dua_x * rho : r_ds; r_pi = active ? pri_u : r_pi; r_di = active ? dua_u * rho : r_di;
             conv = active && (r_ps < P.abs_pri_tol) && (r_pi < P.abs_pri_tol) && (r_ds < P.abs_dua_tol) && (r_di < P.abs_dua_tol);
@@ -319,6 +365,8 @@ next_solve: // (a label, not a loop around the solve: the one-solve instantiatio
             C_(i) = (active && is_u && !keep_d) ? dd : C_(i);
             p = pn;
         }
+        // a row whose own budget is used up leaves behind the backward sweep of its last permitted iteration; its state is frozen by the selects on `active`
+        if constexpr (SET) active = active && (it + 1 < my.max_iter);
     }
     if constexpr (MPC)
     if (ms + 1 < L.mpc_steps)
@@ -449,7 +497,10 @@ next_solve: // (a label, not a loop around the solve: the one-solve instantiatio
         }
         if (valid && r16 == 0)
         {
-            P.res[0 * bp + inst] = r_ps; P.res[1 * bp + inst] = r_pi; P.res[2 * bp + inst] = r_ds; P.res[3 * bp + inst] = r_di;
+            if (!SET || budget)
+            {
+                P.res[0 * bp + inst] = r_ps; P.res[1 * bp + inst] = r_pi; P.res[2 * bp + inst] = r_ds; P.res[3 * bp + inst] = r_di;
+            }
             P.status[inst] = status;
             P.iter[inst] = itn;
             if (!solved) atomicAdd(P.n_unsolved, 1);
@@ -535,6 +586,51 @@ hipError_t launch_rows64_sim(int nx, int nu, int N, const Params64 &P, const dou
         return hipGetLastError();                                                                                                                  \
     }
     TINY_FOR_EACH_F64ROWS_RT(TINY_F64ROWS_RT_SIM_LAUNCH)
+    return hipErrorInvalidValue;
+}
+#elif defined(TINY_F64PS_UNIT) && TINY_F64PS_UNIT == 1
+// per-instance settings, one solve: an instantiation wherever launch_f64_rows has one
+hipError_t launch_f64_rows_ps(int nx, int nu, int N, const Params64 &P, const double *gains, const Settings64 &S)
+{
+    const int nrow_blocks = (P.batch + 3) / 4;
+#define TINY_F64ROWS_PS_LAUNCH(NX, NU, NN)                                                                                                         \
+    if (nx == NX && nu == NU && N == NN)                                                                                                           \
+    {                                                                                                                                              \
+        hipLaunchKernelGGL((admm_f64_rows_kernel<NX, NU, NN, false, false, Settings64>), dim3(nrow_blocks), dim3(WAVE64), 0, 0, P, gains, S);      \
+        return hipGetLastError();                                                                                                                  \
+    }
+    TINY_FOR_EACH_F64ROWS(TINY_F64ROWS_PS_LAUNCH)
+#define TINY_F64ROWS_RT_PS_LAUNCH(NX, NU)                                                                                                          \
+    if (nx == NX && nu == NU && N >= 2 && N <= F64ROWS_RT_MAX_N)                                                                                   \
+    {                                                                                                                                              \
+        if (N <= 32) hipLaunchKernelGGL((admm_f64_rows_kernel<NX, NU, 32, true, false, Settings64>), dim3(nrow_blocks), dim3(WAVE64), 0, 0, P, gains, S); \
+        else hipLaunchKernelGGL((admm_f64_rows_kernel<NX, NU, 64, true, false, Settings64>), dim3(nrow_blocks), dim3(WAVE64), 0, 0, P, gains, S);  \
+        return hipGetLastError();                                                                                                                  \
+    }
+    TINY_FOR_EACH_F64ROWS_RT(TINY_F64ROWS_RT_PS_LAUNCH)
+    return hipErrorInvalidValue;
+}
+#elif defined(TINY_F64PS_UNIT)
+// per-instance settings, the on-chip closed loop with the nominal plant step: wherever launch_f64_rows has an MPC instantiation.  The caller sends no
+// run here in which some instance has no budget
+hipError_t launch_rows64_loop_ps(int nx, int nu, int N, const Params64 &P, const double *gains, const Mpc64 &L, const Settings64 &S)
+{
+    if (L.mpc_steps < 1 || P.max_iter < 1) return hipErrorInvalidValue;
+    const int nrow_blocks = (P.batch + 3) / 4;
+#define TINY_F64ROWS_PS_LOOP_LAUNCH(NX, NU, NN)                                                                                                    \
+    if (nx == NX && nu == NU && N == NN)                                                                                                           \
+    {                                                                                                                                              \
+        hipLaunchKernelGGL((admm_f64_rows_kernel<NX, NU, NN, false, true, Mpc64, Settings64>), dim3(nrow_blocks), dim3(WAVE64), 0, 0, P, gains, L, S); \
+        return hipGetLastError();                                                                                                                  \
+    }
+    TINY_FOR_EACH_F64ROWS(TINY_F64ROWS_PS_LOOP_LAUNCH)
+#define TINY_F64ROWS_RT_PS_LOOP_LAUNCH(NX, NU)                                                                                                     \
+    if (nx == NX && nu == NU && N >= 2 && N <= 32)                                                                                                 \
+    {                                                                                                                                              \
+        hipLaunchKernelGGL((admm_f64_rows_kernel<NX, NU, 32, true, true, Mpc64, Settings64>), dim3(nrow_blocks), dim3(WAVE64), 0, 0, P, gains, L, S); \
+        return hipGetLastError();                                                                                                                  \
+    }
+    TINY_FOR_EACH_F64ROWS_RT(TINY_F64ROWS_RT_PS_LOOP_LAUNCH)
     return hipErrorInvalidValue;
 }
 #else

@@ -1,6 +1,7 @@
 // admm_f64_thread.hip — the thread-per-instance kernels of the fp64 library: admm_f64_kernel (all ADMM iterations in one launch) and
 // admm_f64_step_kernel (the six functions tiny_solve() is made of, one launch each), with their launchers.  Under TINY_F64PM_UNIT
-// (admm_f64_thread_pm.hip) the unit holds the per-instance-model instantiations of admm_f64_kernel and their launcher instead.
+// (admm_f64_thread_pm.hip) the unit holds the per-instance-model instantiations of admm_f64_kernel and their launcher instead, under TINY_F64PS_UNIT
+// (admm_f64_thread_ps.hip) the per-instance-settings ones.
 //
 // One thread per instance, state in HBM.  Every per-instance array is stored instance-minor — element (step, row) of
 // instance b at ((step * dim + row) * Bpad + b) — so that the 64 instances of a wavefront read and write 512 contiguous
@@ -13,6 +14,8 @@ namespace
 using namespace tinympc64;
 
 __device__ __forceinline__ Models64 models_of(const Models64 &m) { return m; }
+__device__ __forceinline__ Settings64 settings_of(const Settings64 &s) { return s; }
+#define SETTING_(field) (SET ? my.field : P.field)
 
 // PM (one trailing argument, a Models64: the ",pm" instantiations of admm_f64_thread_pm.hip): a thread reads its own instance's record and rho from
 // device memory instead of the block's LDS copy of the one shared model; a thread past the batch addresses the last instance's and stores nothing.
@@ -20,8 +23,11 @@ template <int NX, int NU, class... PMA>
 __global__ __launch_bounds__(WAVE64) void admm_f64_kernel(const Params64 P, const PMA... pma)
 {
     static_assert(!(NX >= 8 && NU >= 8), "both dims >= 8: Eigen switches to its GEMV kernel, not restated here");
-    constexpr bool PM = sizeof...(PMA) == 1;
-    static_assert(sizeof...(PMA) <= 1, "at most one trailing argument, the Models64");
+    constexpr bool PM = (false || ... || std::is_same<PMA, Models64>::value);
+    // SET (one trailing argument, a Settings64: the ",ps" instantiations of admm_f64_thread_ps.hip): a thread reads its own instance's tolerances, budget,
+    // check_termination and bound flags from the instance's record; P.max_iter is the batch's largest budget and bounds the loop
+    constexpr bool SET = (false || ... || std::is_same<PMA, Settings64>::value);
+    static_assert(sizeof...(PMA) == (PM ? 1 : 0) + (SET ? 1 : 0) && !(PM && SET), "at most one trailing argument, a Models64 or a Settings64");
     constexpr int NMAT = NU * NX + NX * NX + NU * NU + NX * NX + NX * NX + NX * NU + NX;
     __shared__ double mats[PM ? 1 : NMAT];
     const double *mats_of_thread = mats;
@@ -60,6 +66,10 @@ __global__ __launch_bounds__(WAVE64) void admm_f64_kernel(const Params64 P, cons
         }
         return;
     }
+    // the settings of this thread, SETTING_(field): the batch's, read where they always were, or (SET) its instance's; a thread past the batch reads the
+    // last instance's record
+    [[maybe_unused]] InstSettings64 my{};
+    if constexpr (SET) my = settings_of(pma...).rec[valid ? b : P.batch - 1];
     double x0[NX];
 #pragma unroll
     for (int j = 0; j < NX; j++) x0[j] = valid ? at(TINY_ARR_X, 0, j, NX) : 0.0;
@@ -70,6 +80,7 @@ __global__ __launch_bounds__(WAVE64) void admm_f64_kernel(const Params64 P, cons
     }
     int st = ST_UNSOLVED, itn = 1; // admm.cpp:114-115
     bool active = valid;
+    if constexpr (SET) active = valid && my.max_iter > 0; // a thread without a budget stays with its wave, inactive: status and iter are all it writes
     for (int it = 0; it < P.max_iter; ++it)
     {
         if (!__any(active)) break;
@@ -95,7 +106,7 @@ __global__ __launch_bounds__(WAVE64) void admm_f64_kernel(const Params64 P, cons
                     {
                         const double y = at(TINY_ARR_Y, i, j, NU);
                         double zn = u[j] + y;                                                                             // :47
-                        if (P.en_input_bound)                                                                             // :51-54
+                        if (SETTING_(en_input_bound))                                                                   // :51-54
                         {
                             const double lo = in(P.umin, P.ub_stride, i, j, NU), hi = in(P.umax, P.ub_stride, i, j, NU);
                             zn = (lo < zn) ? zn : lo;
@@ -116,7 +127,7 @@ __global__ __launch_bounds__(WAVE64) void admm_f64_kernel(const Params64 P, cons
                 {
                     const double g = at(TINY_ARR_G, i, j, NX);
                     double vn = x[j] + g;                                                                                 // :48
-                    if (P.en_state_bound)                                                                                 // :57-60
+                    if (SETTING_(en_state_bound))                                                                       // :57-60
                     {
                         const double lo = in(P.xmin, P.xb_stride, i, j, NX), hi = in(P.xmax, P.xb_stride, i, j, NX);
                         vn = (lo < vn) ? vn : lo;
@@ -158,10 +169,10 @@ __global__ __launch_bounds__(WAVE64) void admm_f64_kernel(const Params64 P, cons
             }
             // ---- termination_condition (:91-109) ----
             bool conv = false;
-            if ((it + 1) % P.check_termination == 0)
+            if ((it + 1) % SETTING_(check_termination) == 0)
             {
                 r_ps = pri_x; r_ds = dua_x * rho; r_pi = pri_u; r_di = dua_u * rho;
-                conv = (r_ps < P.abs_pri_tol) && (r_pi < P.abs_pri_tol) && (r_ds < P.abs_dua_tol) && (r_di < P.abs_dua_tol);
+                conv = (r_ps < SETTING_(abs_pri_tol)) && (r_pi < SETTING_(abs_pri_tol)) && (r_ds < SETTING_(abs_dua_tol)) && (r_di < SETTING_(abs_dua_tol));
             }
             if (conv)
             {
@@ -216,12 +227,16 @@ __global__ __launch_bounds__(WAVE64) void admm_f64_kernel(const Params64 P, cons
                         pn[j] = pi[j];
                     }
                 }
+                if constexpr (SET) active = it + 1 < my.max_iter; // its own budget is used up: the thread leaves behind its last backward pass
             }
         }
     }
     if (valid)
     {
-        P.res[0 * bp + b] = r_ps; P.res[1 * bp + b] = r_pi; P.res[2 * bp + b] = r_ds; P.res[3 * bp + b] = r_di;
+        if (!SET || my.max_iter > 0)
+        {
+            P.res[0 * bp + b] = r_ps; P.res[1 * bp + b] = r_pi; P.res[2 * bp + b] = r_ds; P.res[3 * bp + b] = r_di;
+        }
         P.status[b] = st;
         P.iter[b] = itn;
         if (st != ST_SOLVED) atomicAdd(P.n_unsolved, 1);
@@ -404,7 +419,19 @@ __global__ __launch_bounds__(WAVE64) void admm_f64_step_kernel(const Params64 P,
 
 namespace tinympc64
 {
-#ifdef TINY_F64PM_UNIT
+#if defined(TINY_F64PS_UNIT)
+hipError_t launch_f64_thread_ps(int nx, int nu, const Params64 &P, const Settings64 &S)
+{
+#define TINY_F64_PS_LAUNCH(NX, NU)                                                                                  \
+    if (nx == NX && nu == NU)                                                                                       \
+    {                                                                                                               \
+        hipLaunchKernelGGL((admm_f64_kernel<NX, NU, Settings64>), dim3(P.bpad / WAVE64), dim3(WAVE64), 0, 0, P, S); \
+        return hipGetLastError();                                                                                   \
+    }
+    TINY_FOR_EACH_F64DIMS(TINY_F64_PS_LAUNCH)
+    return hipErrorInvalidValue;
+}
+#elif defined(TINY_F64PM_UNIT)
 hipError_t launch_f64_thread_pm(int nx, int nu, const Params64 &P, const Models64 &M)
 {
 #define TINY_F64_PM_LAUNCH(NX, NU)                                                                                  \

@@ -49,6 +49,19 @@ struct Models64
     size_t stride;     // doubles from one instance's record to the next
     const double *rho; // [batch]
 };
+// per-instance settings (tiny_batch64_set_instance_settings): one record per instance, TinySettings (types.hpp:39-47) without the unused fields, and the
+// further argument of the ",ps" instantiations, the last of a kernel's trailing arguments.  The host rebuilds the records on every
+// set_instance_settings / set_settings; Params64::max_iter of a ps launch carries the batch's largest budget, its other settings are not read
+struct InstSettings64
+{
+    double abs_pri_tol, abs_dua_tol;
+    int max_iter, check_termination, en_state_bound, en_input_bound;
+};
+static_assert(sizeof(InstSettings64) == 32, "one record is two 16-byte loads");
+struct Settings64
+{
+    const InstSettings64 *rec; // [batch]
+};
 // arguments of plant64_sim_kernel: the plant step of one MPC step on the workspace's x.col(0) / u.col(0)
 struct PlantSim64
 {
@@ -108,6 +121,13 @@ hipError_t launch_rows64_loop_pm(int nx, int nu, int N, const Params64 &P, const
 hipError_t launch_f64_thread_pm(int nx, int nu, const Params64 &P, const Models64 &M);
 hipError_t launch_models64_gather(const double *rho, const double *Kinf, const double *Pinf, const double *Quu_inv, const double *AmBKt, const double *Adyn,
                                   const double *Bdyn, const double *Q, double *rec, double *rho_out, int batch, int nx, int nu, int q_plus_rho);
+// admm_f64_rows_ps.hip / admm_f64_rowloop_ps.hip / admm_f64_thread_ps.hip: the same kernels with per-instance settings.  One solve on the sixteen lanes
+// wherever launch_f64_rows has an instantiation; the on-chip closed loop (mpc.mpc_steps >= 1 solves, the nominal plant step; every budget >= 1) wherever
+// launch_f64_rows has one; one solve with a thread per instance; F64_UPDATE_SLACK and F64_TERMINATION_CONDITION, the two step functions that read a setting
+hipError_t launch_f64_rows_ps(int nx, int nu, int N, const Params64 &P, const double *gains, const Settings64 &S);
+hipError_t launch_rows64_loop_ps(int nx, int nu, int N, const Params64 &P, const double *gains, const Mpc64 &mpc, const Settings64 &S);
+hipError_t launch_f64_thread_ps(int nx, int nu, const Params64 &P, const Settings64 &S);
+hipError_t launch_f64_step_ps(int fn, int nx, int nu, const Params64 &P, int *conv, const Settings64 &S);
 // admm_f64_plant.hip: x.col(0) <- Adyn * x.col(0) + Bdyn * u.col(0) on the workspace; the same recording u.col(0) in u0_row and sliding the window
 // starts (either may be NULL); the same against a separate plant, with a disturbance and the state trajectory
 hipError_t launch_plant64(int nx, int nu, double *X, const double *U, const double *mats, int batch, int bpad);

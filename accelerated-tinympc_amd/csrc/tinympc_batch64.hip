@@ -2,7 +2,8 @@
 // src/tinympc/glob_opts.hpp:3): the handle, the device workspace, the choice of kernel and the C-ABI of include/tinympc_batch64.h.
 //
 // Host code only.  Every kernel lives in a translation unit of its own (admm_f64_thread.hip, admm_f64_rows.hip, admm_f64_rowsim.hip,
-// admm_f64_plant.hip; admm_f64_rows_pm.hip, admm_f64_rowsim_pm.hip, admm_f64_thread_pm.hip: per-instance models; batch64_helpers.hip: the three
+// admm_f64_plant.hip; admm_f64_rows_pm.hip, admm_f64_rowsim_pm.hip, admm_f64_thread_pm.hip: per-instance models; admm_f64_rows_ps.hip,
+// admm_f64_rowloop_ps.hip, admm_f64_thread_ps.hip: per-instance settings; batch64_helpers.hip: the three
 // that move arrays between the host's layout and the workspace's) and is reached through the typed launchers of f64_internal.h, so nothing in this
 // file — not the order of its functions, not a name in it — has a bearing on device code.
 //
@@ -102,6 +103,13 @@ struct TinyBatch64
     // is set they replace mats, row_gains and rho in every launch
     bool pm = false;
     double *pm_rec = nullptr, *pm_rho = nullptr;
+    // per-instance settings (tiny_batch64_set_instance_settings): the caller's arrays as given (an empty vector: the field was NULL and follows the
+    // batch's value), the records built from them and from the batch's settings ([batch], rebuilt by every setter), the largest and the smallest budget
+    bool ps = false;
+    std::vector<double> ps_tol[2];
+    std::vector<int> ps_int[4]; // max_iter, check_termination, en_state_bound, en_input_bound
+    InstSettings64 *ps_rec = nullptr;
+    int ps_max_iter = 0, ps_min_iter = 0;
     std::vector<double> hm; // host copy of the packed matrices
     bool have_cache = false, have_dyn = false, have_settings = false, mats_dirty = true;
     double rho = 0, abs_pri_tol = 0, abs_dua_tol = 0;
@@ -186,6 +194,27 @@ int gather_window64(TinyBatch64 *tb)
 }
 size_t rec_len(const TinyBatch64 *tb) { return mat_off(tb, 6) + tb->nx; }
 
+// the per-instance settings records from the caller's arrays and, for the fields given as NULL, the batch's settings as they stand now
+int rebuild_settings64(TinyBatch64 *tb)
+{
+    const size_t B = tb->batch;
+    std::vector<InstSettings64> rec(B);
+    const int batch_int[4] = {tb->max_iter, tb->check_termination, tb->en_state_bound, tb->en_input_bound};
+    for (size_t b = 0; b < B; b++)
+    {
+        int v[4];
+        for (int k = 0; k < 4; k++) v[k] = tb->ps_int[k].empty() ? batch_int[k] : tb->ps_int[k][b];
+        rec[b] = InstSettings64{tb->ps_tol[0].empty() ? tb->abs_pri_tol : tb->ps_tol[0][b], tb->ps_tol[1].empty() ? tb->abs_dua_tol : tb->ps_tol[1][b], v[0], v[1], v[2], v[3]};
+        tb->ps_max_iter = b && tb->ps_max_iter > v[0] ? tb->ps_max_iter : v[0];
+        tb->ps_min_iter = b && tb->ps_min_iter < v[0] ? tb->ps_min_iter : v[0];
+    }
+    HIP64(hipSetDevice(tb->device));
+    HIP64(hipDeviceSynchronize()); // a launch still reading the records may be in flight
+    if (!tb->ps_rec) HIP64(hipMalloc((void **)&tb->ps_rec, B * sizeof(InstSettings64)));
+    HIP64(hipMemcpy(tb->ps_rec, rec.data(), B * sizeof(InstSettings64), hipMemcpyHostToDevice));
+    return 0;
+}
+
 // ---- what a call launches: resolved ONCE per call by resolve_plan64() and read by everything that names, prepares or launches (DESIGN.md 5.6 has the
 // table).  No other function looks at kernel_choice, the lists of instantiated classes, the capacities, max_iter or TINYMPC_F64_LOOP.
 enum class Family64 { Thread, Rows };         // one thread per instance (state in HBM, any N); sixteen lanes per instance (state in registers)
@@ -196,6 +225,7 @@ struct Plan64
     Family64 family = Family64::Thread;
     Body64 body = Body64::Unrolled;
     bool pm = false; // per-instance models: the ",pm" instantiations
+    bool ps = false; // per-instance settings: the ",ps" instantiations (never with pm)
     Loop64 loop = Loop64::None;
     bool sim = false; // the plant step is the simulated one: a plant is set, the call passes w or asks for x_traj — or pm: the simulated kernels are the
                       // ones that take a matrix pair per instance, here the instance's own model.  Any other call enqueues what it always has
@@ -207,10 +237,13 @@ struct Call64
     bool log = false;                      // ... asks for the per-step solver log (tiny_batch64_mpc_run_log)
 };
 
-// Reads the handle and changes nothing.  The one refusal a resolution can meet is the step functions' under models: tiny_batch64_select_kernel refuses
-// the sixteen lanes where the class has none, so a stored choice can always be served.
+// Reads the handle and changes nothing.  The two refusals a resolution can meet are the step functions' under models and per-instance settings together
+// with models: tiny_batch64_select_kernel refuses the sixteen lanes where the class has none, so a stored choice can always be served.
 int resolve_plan64(const TinyBatch64 *tb, const Call64 &call, Plan64 *out)
 {
+    if (tb->pm && tb->ps)
+        return fail64(TINY_BATCH_EUNSUPPORTED, "per-instance settings together with per-instance models: no kernel reads both records "
+                                               "(tiny_batch64_clear_instance_settings() or tiny_batch64_clear_models())");
     if (call.kind == Call64::StepFn && tb->pm)
         return fail64(TINY_BATCH_EUNSUPPORTED, "the six single-function step kernels read one shared model: not available with per-instance models (tiny_batch64_clear_models())");
     Plan64 p;
@@ -221,6 +254,7 @@ int resolve_plan64(const TinyBatch64 *tb, const Call64 &call, Plan64 *out)
         p.body = rows_unrolled(tb->nx, tb->nu, tb->N) ? Body64::Unrolled : tb->N <= 32 ? Body64::Cap32 : Body64::Cap64;
     }
     p.pm = tb->pm;
+    p.ps = tb->ps;
     p.sim = tb->plant_mode != 0 || call.w || call.x_traj || tb->pm;
     if (call.kind == Call64::Run)
     {
@@ -230,7 +264,10 @@ int resolve_plan64(const TinyBatch64 *tb, const Call64 &call, Plan64 *out)
         const char *force = getenv("TINYMPC_F64_LOOP");
         // A run that asks for the per-step solver log is a launch sequence as well: the on-chip loops do not log (their instruction streams are pinned,
         // tests/test_isa_sim64.py), the sequence copies iter[] / status[] behind each solve of the same solve kernel, with the same bits.
-        const bool on_chip = p.family == Family64::Rows && p.body != Body64::Cap64 && tb->max_iter >= 1 && !(force && !strcmp(force, "sequence")) && !call.log;
+        // With per-instance settings the budget that counts is the smallest (an instance without one writes status and iter only: the sequence's solve
+        // kernel does that), and the on-chip loop is the nominal one: a plant, w or x_traj make the run a sequence.
+        const bool budget = (tb->ps ? tb->ps_min_iter : tb->max_iter) >= 1, ps_nominal = !tb->ps || !(tb->plant_mode || call.w || call.x_traj);
+        const bool on_chip = p.family == Family64::Rows && p.body != Body64::Cap64 && budget && ps_nominal && !(force && !strcmp(force, "sequence")) && !call.log;
         p.loop = on_chip ? Loop64::OnChip : Loop64::Sequence;
     }
     *out = p;
@@ -245,7 +282,7 @@ const char *name_of(const TinyBatch64 *tb, const Plan64 &p, char (&nm)[64])
     if (p.family == Family64::Rows && p.body == Body64::Unrolled) snprintf(body, sizeof body, ",%d", tb->N);
     else if (p.family == Family64::Rows) snprintf(body, sizeof body, ",n<=%d", p.body == Body64::Cap32 ? 32 : 64);
     const char *const loop = p.loop != Loop64::OnChip ? "" : tb->plant_mode ? ",sim" : ",mpc";
-    snprintf(nm, sizeof nm, "%s<%d,%d%s%s%s>", p.family == Family64::Rows ? "rows64" : "thread64", tb->nx, tb->nu, body, loop, p.pm ? ",pm" : "");
+    snprintf(nm, sizeof nm, "%s<%d,%d%s%s%s>", p.family == Family64::Rows ? "rows64" : "thread64", tb->nx, tb->nu, body, loop, p.pm ? ",pm" : p.ps ? ",ps" : "");
     return nm;
 }
 
@@ -268,7 +305,7 @@ int prepare64(TinyBatch64 *tb, const Call64 &call, Plan64 &plan, Params64 &P)
     }
     P.nx = tb->nx; P.nu = tb->nu; P.N = tb->N; P.batch = tb->batch; P.bpad = tb->bpad;
     P.rho = tb->rho; P.abs_pri_tol = tb->abs_pri_tol; P.abs_dua_tol = tb->abs_dua_tol;
-    P.max_iter = tb->max_iter; P.check_termination = tb->check_termination;
+    P.max_iter = plan.ps ? tb->ps_max_iter : tb->max_iter; P.check_termination = tb->check_termination;
     P.en_state_bound = tb->en_state_bound; P.en_input_bound = tb->en_input_bound;
     for (int id = 0; id < TINY_ARR_COUNT; id++) P.arr[id] = tb->arr[id];
     P.xref = tb->in[0]; P.xmin = tb->in[1]; P.xmax = tb->in[2]; P.umin = tb->in[3]; P.umax = tb->in[4];
@@ -289,7 +326,9 @@ int run_step64(TinyBatch64 *tb, int fn, int *conv_dev)
     Plan64 plan;
     Params64 P;
     TRY64(prepare64(tb, Call64{Call64::StepFn}, plan, P));
-    HIP64(launch_f64_step(fn, tb->nx, tb->nu, P, conv_dev));
+    // update_slack and termination_condition are the two that read a setting: with per-instance settings their ",ps" forms; the other four keep their kernels
+    if (plan.ps && (fn == F64_UPDATE_SLACK || fn == F64_TERMINATION_CONDITION)) HIP64(launch_f64_step_ps(fn, tb->nx, tb->nu, P, conv_dev, Settings64{tb->ps_rec}));
+    else HIP64(launch_f64_step(fn, tb->nx, tb->nu, P, conv_dev));
     HIP64(hipDeviceSynchronize());
     return 0;
 }
@@ -313,6 +352,13 @@ int launch_solve64(TinyBatch64 *tb, const Plan64 &plan, const Params64 &P, const
     {
         if (rows) HIP64(launch_f64_rows_pm(nx, nu, N, P, M));
         else HIP64(launch_f64_thread_pm(nx, nu, P, M));
+    }
+    else if (plan.ps)
+    {
+        const Settings64 ST{tb->ps_rec};
+        if (plan.loop == Loop64::OnChip) HIP64(launch_rows64_loop_ps(nx, nu, N, P, tb->row_gains, *L, ST));
+        else if (rows) HIP64(launch_f64_rows_ps(nx, nu, N, P, tb->row_gains, ST));
+        else HIP64(launch_f64_thread_ps(nx, nu, P, ST));
     }
     else if (rows) HIP64(launch_f64_rows(nx, nu, N, P, tb->row_gains, plan.loop == Loop64::OnChip ? L : nullptr));
     else HIP64(launch_f64_thread(nx, nu, P));
@@ -419,7 +465,7 @@ void tiny_batch64_destroy(TinyBatch64 *tb)
     (void)hipFree(tb->table); (void)hipFree(tb->xwin); (void)hipFree(tb->u0_traj); (void)hipFree(tb->xref_start);
     (void)hipFree(tb->log_iter); (void)hipFree(tb->log_status);
     (void)hipFree(tb->plant_A); (void)hipFree(tb->plant_B); (void)hipFree(tb->plant_rows); (void)hipFree(tb->sim_w); (void)hipFree(tb->sim_x);
-    (void)hipFree(tb->pm_rec); (void)hipFree(tb->pm_rho);
+    (void)hipFree(tb->pm_rec); (void)hipFree(tb->pm_rho); (void)hipFree(tb->ps_rec);
     delete tb;
 }
 
@@ -455,7 +501,47 @@ int tiny_batch64_set_settings(TinyBatch64 *tb, double abs_pri_tol, double abs_du
     tb->abs_pri_tol = abs_pri_tol; tb->abs_dua_tol = abs_dua_tol; tb->max_iter = max_iter; tb->check_termination = check_termination;
     tb->en_state_bound = en_state_bound; tb->en_input_bound = en_input_bound;
     tb->have_settings = true;
+    if (tb->ps) TRY64(rebuild_settings64(tb)); // the fields given as NULL move with the batch's
     return 0;
+}
+
+// ---- per-instance settings ---------------------------------------------------------------------------------------------------
+int tiny_batch64_set_instance_settings(TinyBatch64 *tb, const double *abs_pri_tol, const double *abs_dua_tol, const int *max_iter, const int *check_termination,
+                                       const int *en_state_bound, const int *en_input_bound)
+{
+    CHECK64(tb, "NULL handle");
+    if (!tb->have_settings) return fail64(TINY_BATCH_ENOTREADY, "tiny_batch64_set_settings must be called first: a NULL field keeps the batch's value");
+    const size_t B = tb->batch;
+    if (check_termination)
+        for (size_t b = 0; b < B; b++)
+            CHECK64(check_termination[b] >= 1, "check_termination[%zu] = %d: must be >= 1 (the reference computes iter %% check_termination, admm.cpp:93)", b,
+                    check_termination[b]);
+    const double *const tol[2] = {abs_pri_tol, abs_dua_tol};
+    const int *const ints[4] = {max_iter, check_termination, en_state_bound, en_input_bound};
+    for (int k = 0; k < 2; k++) tb->ps_tol[k].assign(tol[k], tol[k] ? tol[k] + B : tol[k]);
+    for (int k = 0; k < 4; k++) tb->ps_int[k].assign(ints[k], ints[k] ? ints[k] + B : ints[k]);
+    TRY64(rebuild_settings64(tb));
+    tb->ps = true;
+    return 0;
+}
+
+int tiny_batch64_clear_instance_settings(TinyBatch64 *tb)
+{
+    CHECK64(tb, "NULL handle");
+    if (!tb->ps) return 0;
+    HIP64(hipSetDevice(tb->device));
+    HIP64(hipDeviceSynchronize()); // a launch still reading the records may be in flight
+    (void)hipFree(tb->ps_rec); tb->ps_rec = nullptr;
+    for (auto &v : tb->ps_tol) v.clear();
+    for (auto &v : tb->ps_int) v.clear();
+    tb->ps = false;
+    return 0;
+}
+
+int tiny_batch64_settings_per_instance(TinyBatch64 *tb)
+{
+    CHECK64(tb, "NULL handle");
+    return tb->ps ? 1 : 0;
 }
 
 int tiny_batch64_set_x0(TinyBatch64 *tb, const double *x0)
@@ -511,8 +597,9 @@ int tiny_batch64_solve(TinyBatch64 *tb)
 static int mpc_step64(TinyBatch64 *tb, const double *w)
 {
     CHECK64(tb, "NULL handle");
-    TRY64(tiny_batch64_reset_dual_variables(tb)); // quadrotor_hovering.cpp:100-101
     Plan64 plan;
+    TRY64(resolve_plan64(tb, Call64{Call64::Solve, w != nullptr}, &plan)); // a refused combination touches nothing
+    TRY64(tiny_batch64_reset_dual_variables(tb)); // quadrotor_hovering.cpp:100-101
     const int rc = solve64(tb, Call64{Call64::Solve, w != nullptr}, plan); // :104
     if (rc < 0) return rc;
     if (w)
@@ -798,7 +885,7 @@ static const char *plan_name64(TinyBatch64 *tb, Call64::Kind kind, char (&nm)[64
 {
     if (!tb) return "";
     Plan64 plan;
-    (void)resolve_plan64(tb, Call64{kind}, &plan); // (neither a solve's nor a run's resolution refuses anything)
+    if (resolve_plan64(tb, Call64{kind}, &plan) < 0) return "unsupported"; // per-instance settings with models: tiny_batch64_last_error() says so
     return name_of(tb, plan, nm);
 }
 const char *tiny_batch64_kernel_name(TinyBatch64 *tb)

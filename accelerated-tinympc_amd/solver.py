@@ -119,6 +119,7 @@ def load_library(build_if_missing: bool = False) -> C.CDLL:
         "tiny_batch64_set_models": [P, D, D, D, D, D, D, D, D], "tiny_batch64_set_models_device": [P, P, P, P, P, P, P, P, P],
         "tiny_batch64_clear_models": [P], "tiny_batch64_models_per_instance": [P],
         "tiny_batch64_set_systems": [P, D, D, D, D, D, I],
+        "tiny_batch64_set_instance_settings": [P, D, D, I, I, I, I], "tiny_batch64_clear_instance_settings": [P], "tiny_batch64_settings_per_instance": [P],
     }
     for name, args in sig64.items():
         fn = getattr(lib, name)
@@ -695,6 +696,24 @@ class TinyBatchSolver64:
         self.settings = dict(abs_pri_tol=abs_pri_tol, abs_dua_tol=abs_dua_tol, max_iter=max_iter, check_termination=check_termination,
                              en_state_bound=en_state_bound, en_input_bound=en_input_bound)
         self._check(self.lib.tiny_batch64_set_settings(self._h, abs_pri_tol, abs_dua_tol, max_iter, check_termination, en_state_bound, en_input_bound))
+
+    # -- per-instance settings (tiny_batch64_set_instance_settings) --------------------------------
+    def set_instance_settings(self, abs_pri_tol=None, abs_dua_tol=None, max_iter=None, check_termination=None, en_state_bound=None, en_input_bound=None):
+        """Every instance its own TinySettings: each argument is an array [B], a scalar (broadcast over the batch) or None (the field keeps the value of
+        set_settings); the tolerances are float64.  Served by rows64<...,ps> / thread64<...,ps>; replaces any earlier per-instance settings."""
+        def arr(v, dt):
+            return None if v is None else np.ascontiguousarray(np.broadcast_to(np.asarray(v, dt), (self.B,)))
+        f = [arr(v, np.float64) for v in (abs_pri_tol, abs_dua_tol)]
+        i = [arr(v, np.int32) for v in (max_iter, check_termination, en_state_bound, en_input_bound)]
+        self._check(self.lib.tiny_batch64_set_instance_settings(self._h, *[None if a is None else self._dp(a) for a in f],
+                                                                *[None if a is None else a.ctypes.data_as(C.POINTER(C.c_int)) for a in i]))
+
+    def clear_instance_settings(self):
+        """Back to the batch's one set of set_settings."""
+        self._check(self.lib.tiny_batch64_clear_instance_settings(self._h))
+
+    def settings_per_instance(self) -> bool:
+        return bool(self._check(self.lib.tiny_batch64_settings_per_instance(self._h)))
 
     def set_x0(self, x0):
         a = np.ascontiguousarray(x0, np.float64); assert a.shape == (self.B, self.nx), a.shape

@@ -148,6 +148,30 @@ extern "C"
      * itself.  iters ([B], may be NULL) as tiny_batch_riccati_device.  Any failed system: TINY_BATCH_EINVAL and the handle's models are unchanged. */
     int tiny_batch64_set_systems(TinyBatch64 *tb, const double *A, const double *B, const double *Q, const double *R, const double *rho, int *iters);
 
+    /* Per-instance settings (the float library's tiny_batch_set_instance_settings family, in double): TinySettings (types.hpp:39-47) per instance.  Every
+     * pointer is a host array [batch] or NULL; NULL = that field stays the batch's value from tiny_batch64_set_settings (which must have been called:
+     * TINY_BATCH_ENOTREADY otherwise; a later tiny_batch64_set_settings moves the NULL fields with it).  The call replaces any earlier per-instance
+     * settings.  check_termination[b] < 1: TINY_BATCH_EINVAL, the message names the first such index (admm.cpp:93); the tolerances are doubles, compared
+     * with `<` as in the reference (admm.cpp:100-103).  From then on every solve entry point — tiny_batch64_solve, tiny_batch64_mpc_step[_sim],
+     * tiny_batch64_mpc_run[_traj|_sim|_log], tiny_batch64_termination_condition, and tiny_batch64_update_slack through the bound flags — treats instance b
+     * bit for bit as the reference's fp64 tiny_solve treats a solver whose TinySettings are instance b's.  max_iter[b] <= 0: status 11, iter 1, counted
+     * unsolved, nothing else of that instance is written.  tiny_batch64_solve returns 1 if any instance did not converge within its own budget.
+     * Kernels: ",ps" last inside the brackets — "rows64<12,4,10,ps>", "rows64<12,2,n<=32,ps>", "rows64<4,2,n<=64,ps>" wherever the sixteen lanes serve the
+     * solve, "thread64<16,4,ps>" elsewhere, with shared or per-instance bounds and any reference.  A run is ONE launch ("rows64<12,4,10,mpc,ps>") where it
+     * is one without per-instance settings AND every budget is >= 1, no plant is set, the call passes neither w nor x_traj and asks for no log; every
+     * other run is the launch sequence of the ",ps" solve kernel and the plant kernel per step, with the same bits.  Unlike the float library, which
+     * refuses it, a run in which some instance has no budget is served, by the sequence (as this library has always served a batch-wide max_iter <= 0):
+     * that instance's status is 11 at every step and the plant steps on with the u.col(0) its workspace holds.  tiny_batch64_closed_loop_kernel_name,
+     * which knows the handle alone, says ",mpc,ps" whenever no plant is set and every budget is >= 1, also for a call that passes w or x_traj and
+     * therefore runs as a sequence.  Refused with TINY_BATCH_EUNSUPPORTED and a message, at the next solve, step function or run and with nothing
+     * launched: per-instance settings together with per-instance models, in either order of the two setters (the two names then read "unsupported"). */
+    int tiny_batch64_set_instance_settings(TinyBatch64 *tb, const double *abs_pri_tol, const double *abs_dua_tol, const int *max_iter,
+                                           const int *check_termination, const int *en_state_bound, const int *en_input_bound);
+    /* back to the batch's one set of tiny_batch64_set_settings: kernels, kernel names and results are what they were */
+    int tiny_batch64_clear_instance_settings(TinyBatch64 *tb);
+    /* 1 while per-instance settings are in force, 0 otherwise */
+    int tiny_batch64_settings_per_instance(TinyBatch64 *tb);
+
     /* Implementation: 0 = automatic (the second where (nx, nu, N) has an instantiation, else the first), 1 = one thread per
      * instance with the state in HBM (any N), 2 = sixteen lanes per instance with the state in registers for the whole solve
      * (instantiated (nx, nu, N): (12,4,10) as shipped, (12,4,20), (12,4,30), (4,1,10), (8,4,9)).  Identical results. */
