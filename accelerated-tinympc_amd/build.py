@@ -10,38 +10,89 @@ from __future__ import annotations
 import os
 import subprocess
 import sys
+from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
+from typing import NamedTuple
 
 PKG = Path(__file__).resolve().parent
 CSRC = PKG / "csrc"
 LIB = PKG / "lib" / "libtinympc_hip.so"
 WRAPPER_LIB = PKG / "lib" / "libtinympc_wrapper.so"  # same-name twin of the reference's generated wrapper library
 WRAPPER64_LIB = PKG / "lib" / "libtinympc_wrapper64.so"  # the native names (tiny_solve, forward_pass, ...) for tinytype = double
-SOURCES = ["tinympc_batch.hip", "batch_helpers.hip", "tinympc_batch64.hip", "batch64_helpers.hip", "admm_f64_thread.hip", "admm_f64_rows.hip", "admm_f64_rowsim.hip", "admm_f64_plant.hip", "admm_f64_rows_pm.hip", "admm_f64_rowsim_pm.hip", "admm_f64_thread_pm.hip", "admm_f64_rows_ps.hip", "admm_f64_rowloop_ps.hip", "admm_f64_thread_ps.hip", "admm_stream.hip", "admm_generic.hip", "admm_rowlane.hip", "admm_rowsim.hip", "admm_rowlane_ps.hip", "admm_rowloop.hip", "admm_quadlane.hip", "admm_tile16.hip", "admm_tile16_pi.hip", "admm_wave.hip", "admm_wave_pm.hip", "admm_waveres.hip", "admm_waveres_pm.hip", "admm_tile48.hip", "admm_steps.hip", "admm_steps_ps.hip", "settings_helpers.hip", "dispatch_order.hip", "riccati.cpp", "riccati_batch.hip"]
 WRAPPER_SRCS = [CSRC / "wrapper_compat.cpp", CSRC / "admm_compat.cpp"]
 HEADERS = [CSRC / "tinympc_internal.h", CSRC / "batch_helpers.h", CSRC / "eigen_orders.h", CSRC / "rowlane_math.h", CSRC / "tile_math.h", CSRC / "wave_math.h", CSRC / "dpp_ops_gen.h", CSRC / "f64_internal.h", CSRC / "f64_math.h", PKG.parent / "include" / "tinympc_batch.h", PKG.parent / "include" / "tinympc_batch64.h"]
 # -ffp-contract=off : exact arithmetic must not fuse a*b+c; the fast paths call fma explicitly
 # -fno-slp-vectorize: hipcc otherwise pairs scalar fp32 adds into v_pk_add_f32 (+ v_mov to build the pairs), which on
 #                     gfx950 is slower than two plain v_add_f32 (measured, tools/micro/*.hip)
-# per-file extras.  admm_tile16.hip: the max-ILP scheduling strategy (one wave per SIMD: nothing else hides a latency; measured
+FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-slp-vectorize", "-fno-gpu-rdc"]
+
+
+class Unit(NamedTuple):
+    """One translation unit of libtinympc_hip.so.  Everything build() and the tools know about a unit is its row of UNITS."""
+    source: str
+    parent: str | None = None      # the kernel source it #includes (a variant unit: the parent's text compiled again): rebuilt with it
+    flags: tuple = ()              # extra hipcc flags
+    flags_env: str | None = None   # environment variable whose words are appended to flags (A/B runs of the tools)
+    family: str | None = None      # the kernel-name prefix it serves (tiny_batch_kernel_name(), up to the '<')
+    tails: tuple = ()              # name endings that route to this unit; the family's unit without tails is its default
+
+
+# per-unit flags.  admm_tile16.hip: the max-ILP scheduling strategy (one wave per SIMD: nothing else hides a latency; measured
 # 1.88 -> 1.79 ms, the other kernels do not react to it); MFMA results go to VGPRs (the sums that consume the exact products are VALU instructions,
 # which cannot read the accumulator half of the register file: left to its heuristics hipcc parks the products there and
 # copies every one of them back, 110 v_accvgpr_read per horizon step)
-_T16_FLAGS = ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-mllvm", "-amdgpu-sched-strategy=max-ilp"] + os.environ.get("TINYMPC_T16_FLAGS", "").split()
-EXTRA_FLAGS = {"admm_tile16.hip": _T16_FLAGS, "admm_tile16_pi.hip": _T16_FLAGS,
-               "admm_rowlane.hip": os.environ.get("TINYMPC_ROWLANE_FLAGS", "").split(),
-               "admm_rowsim.hip": os.environ.get("TINYMPC_ROWLANE_FLAGS", "").split(),
-               "admm_rowlane_ps.hip": os.environ.get("TINYMPC_ROWLANE_FLAGS", "").split(),
-               "admm_waveres.hip": os.environ.get("TINYMPC_WAVERES_FLAGS", "").split(),
-               "admm_waveres_pm.hip": os.environ.get("TINYMPC_WAVERES_FLAGS", "").split(),
-               "admm_tile48.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"] + os.environ.get("TINYMPC_T48_FLAGS", "").split()}
-# translation units that #include another kernel source: rebuilt with it
-INCLUDED_SOURCES = {"admm_tile16_pi.hip": ["admm_tile16.hip"], "admm_rowsim.hip": ["admm_rowlane.hip"], "admm_rowlane_ps.hip": ["admm_rowlane.hip"],
-                    "admm_steps_ps.hip": ["admm_steps.hip"], "admm_f64_rowsim.hip": ["admm_f64_rows.hip"],
-                    "admm_f64_rows_pm.hip": ["admm_f64_rows.hip"], "admm_f64_rowsim_pm.hip": ["admm_f64_rows.hip"], "admm_f64_thread_pm.hip": ["admm_f64_thread.hip"],
-                    "admm_f64_rows_ps.hip": ["admm_f64_rows.hip"], "admm_f64_rowloop_ps.hip": ["admm_f64_rows.hip"], "admm_f64_thread_ps.hip": ["admm_f64_thread.hip"],
-                    "admm_wave_pm.hip": ["admm_wave.hip"], "admm_waveres_pm.hip": ["admm_waveres.hip"]}
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-slp-vectorize", "-fno-gpu-rdc"]
+_MFMA_VGPR = ("-mllvm", "-amdgpu-mfma-vgpr-form=1")
+_T16_FLAGS = _MFMA_VGPR + ("-mllvm", "-amdgpu-sched-strategy=max-ilp")
+# in link order
+UNITS = (
+    Unit("tinympc_batch.hip"),
+    Unit("batch_helpers.hip"),
+    Unit("tinympc_batch64.hip"),
+    Unit("batch64_helpers.hip"),
+    Unit("admm_f64_thread.hip", family="thread64"),
+    Unit("admm_f64_rows.hip", family="rows64"),
+    Unit("admm_f64_rowsim.hip", "admm_f64_rows.hip", family="rows64", tails=(",sim>",)),
+    Unit("admm_f64_plant.hip"),
+    Unit("admm_f64_rows_pm.hip", "admm_f64_rows.hip", family="rows64", tails=(",pm>",)),
+    Unit("admm_f64_rowsim_pm.hip", "admm_f64_rows.hip", family="rows64", tails=(",mpc,pm>", ",sim,pm>")),
+    Unit("admm_f64_thread_pm.hip", "admm_f64_thread.hip", family="thread64", tails=(",pm>",)),
+    Unit("admm_f64_rows_ps.hip", "admm_f64_rows.hip", family="rows64", tails=(",ps>",)),
+    Unit("admm_f64_rowloop_ps.hip", "admm_f64_rows.hip", family="rows64", tails=(",mpc,ps>",)),
+    Unit("admm_f64_thread_ps.hip", "admm_f64_thread.hip", family="thread64", tails=(",ps>",)),
+    Unit("admm_stream.hip", family="stream"),
+    Unit("admm_generic.hip", family="generic"),
+    Unit("admm_rowlane.hip", family="rowlane", flags_env="TINYMPC_ROWLANE_FLAGS"),
+    Unit("admm_rowsim.hip", "admm_rowlane.hip", flags_env="TINYMPC_ROWLANE_FLAGS"),  # (the simulated loop reports its MPC twin's name)
+    Unit("admm_rowlane_ps.hip", "admm_rowlane.hip", family="rowlane", tails=(",ps>",), flags_env="TINYMPC_ROWLANE_FLAGS"),
+    Unit("admm_rowloop.hip", family="rowloop"),
+    Unit("admm_quadlane.hip", family="quadlane"),
+    Unit("admm_tile16.hip", flags=_T16_FLAGS, flags_env="TINYMPC_T16_FLAGS", family="tile16"),
+    Unit("admm_tile16_pi.hip", "admm_tile16.hip", flags=_T16_FLAGS, flags_env="TINYMPC_T16_FLAGS", family="tile16", tails=(",pi>",)),
+    Unit("admm_wave.hip", family="wavestream"),
+    Unit("admm_wave_pm.hip", "admm_wave.hip", family="wavestream", tails=(",pm>",)),
+    Unit("admm_waveres.hip", flags_env="TINYMPC_WAVERES_FLAGS", family="waveres"),
+    Unit("admm_waveres_pm.hip", "admm_waveres.hip", flags_env="TINYMPC_WAVERES_FLAGS", family="waveres", tails=(",pm>",)),
+    Unit("admm_tile48.hip", flags=_MFMA_VGPR, flags_env="TINYMPC_T48_FLAGS", family="tile48"),
+    Unit("admm_steps.hip", family="rowstream"),
+    Unit("admm_steps_ps.hip", "admm_steps.hip", family="rowstream", tails=(",ps>",)),
+    Unit("settings_helpers.hip"),
+    Unit("dispatch_order.hip"),
+    Unit("riccati.cpp"),
+    Unit("riccati_batch.hip"),
+)
+# the views of the table that build(), bench.py, the tests and the tools read
+SOURCES = [u.source for u in UNITS]
+INCLUDED_SOURCES = {u.source: [u.parent] for u in UNITS if u.parent}
+EXTRA_FLAGS = {u.source: [*u.flags, *os.environ.get(u.flags_env or "", "").split()] for u in UNITS if u.flags or u.flags_env}
+KERNEL_SOURCES = {u.family: u.source for u in UNITS if u.family and not u.tails}  # family -> its default unit
+
+
+def unit_of(kernel_name: str) -> str | None:
+    """The translation unit that holds the device code behind a kernel name such as 'tile16<12,4,30,exact,pi>': of the family's units the one
+    with the longest matching tail, else the family's default unit; None for an unknown family."""
+    family = kernel_name.split("<", 1)[0]
+    tails = [(t, u.source) for u in UNITS if u.family == family for t in u.tails if kernel_name.endswith(t)]
+    return max(tails, key=lambda t: len(t[0]))[1] if tails else KERNEL_SOURCES.get(family)
 
 
 def _objs():
@@ -63,7 +114,7 @@ def build(force: bool = False, verbose: bool = False) -> Path:
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     LIB.parent.mkdir(parents=True, exist_ok=True)
     hdr_t = max(h.stat().st_mtime for h in HEADERS + [Path(__file__)] if h.exists())
-    procs = []
+    stale = []
     for src, obj in _objs():
         src_t = max([src.stat().st_mtime] + [(CSRC / i).stat().st_mtime for i in INCLUDED_SOURCES.get(src.name, [])])
         if not force and obj.exists() and obj.stat().st_mtime > max(src_t, hdr_t):
@@ -71,10 +122,12 @@ def build(force: bool = False, verbose: bool = False) -> Path:
         cmd = [hipcc, *FLAGS, *EXTRA_FLAGS.get(src.name, []), "-c", str(src), "-o", str(obj)]
         if verbose:
             print(" ".join(cmd))
-        procs.append((src, subprocess.Popen(cmd)))
-    for src, p in procs:
-        if p.wait() != 0:
-            raise RuntimeError(f"hipcc failed on {src}")
+        stale.append((src, cmd))
+    # started in table order, at most MAX_JOBS (and never more than 16) at a time
+    with ThreadPoolExecutor(min(int(os.environ.get("MAX_JOBS", "16")), 16)) as pool:
+        for (src, _), rc in zip(stale, pool.map(lambda c: subprocess.run(c[1]).returncode, stale)):
+            if rc != 0:
+                raise RuntimeError(f"hipcc failed on {src}")
     cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", str(LIB)] + [str(o) for _, o in _objs()]
     if verbose:
         print(" ".join(cmd))
@@ -107,12 +160,6 @@ def device_asm(source: str) -> Path:
         cmd = [hipcc, *[f for f in FLAGS if f != "-fPIC"], *EXTRA_FLAGS.get(source, []), "-S", "--cuda-device-only", str(src), "-o", str(out)]
         subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
     return out
-
-
-# kernel family (the name tiny_batch_kernel_name() reports, up to the '<') -> the translation unit that holds its device code
-KERNEL_SOURCES = {"rowlane": "admm_rowlane.hip", "rowloop": "admm_rowloop.hip", "rowstream": "admm_steps.hip", "quadlane": "admm_quadlane.hip",
-                  "tile16": "admm_tile16.hip", "tile48": "admm_tile48.hip", "waveres": "admm_waveres.hip", "wavestream": "admm_wave.hip",
-                  "stream": "admm_stream.hip", "generic": "admm_generic.hip", "rows64": "admm_f64_rows.hip", "thread64": "admm_f64_thread.hip"}
 
 
 def _elf_sections(b: bytes, base: int = 0) -> dict:
@@ -163,23 +210,7 @@ def device_isa_sha(source: str) -> str:
 
 def kernel_isa_sha(kernel_name: str) -> str | None:
     """device_isa_sha of the translation unit behind a kernel name such as 'tile16<12,4,30,exact>'; None for an unknown family or a missing object."""
-    src = KERNEL_SOURCES.get(kernel_name.split("<", 1)[0])
-    if src == "admm_tile16.hip" and kernel_name.endswith(",pi>"):
-        src = "admm_tile16_pi.hip"  # the per-instance instantiations are a translation unit of their own
-    if src in ("admm_rowlane.hip", "admm_steps.hip") and kernel_name.endswith(",ps>"):  # per-instance settings: admm_rowlane_ps.hip, admm_steps_ps.hip
-        src = src.replace(".hip", "_ps.hip")
-    if src == "admm_f64_rows.hip" and kernel_name.endswith(",sim>"):
-        src = "admm_f64_rowsim.hip"  # as are the fp64 simulated closed loop's
-    if src == "admm_f64_rows.hip" and kernel_name.endswith(",pm>"):  # and the fp64 per-instance-model families: the closed loop, one solve
-        src = "admm_f64_rowsim_pm.hip" if kernel_name.endswith((",mpc,pm>", ",sim,pm>")) else "admm_f64_rows_pm.hip"
-    if src == "admm_f64_thread.hip" and kernel_name.endswith(",pm>"):
-        src = "admm_f64_thread_pm.hip"
-    if src == "admm_f64_rows.hip" and kernel_name.endswith(",ps>"):  # and the fp64 per-instance-settings families: the on-chip closed loop, one solve
-        src = "admm_f64_rowloop_ps.hip" if kernel_name.endswith(",mpc,ps>") else "admm_f64_rows_ps.hip"
-    if src == "admm_f64_thread.hip" and kernel_name.endswith(",ps>"):
-        src = "admm_f64_thread_ps.hip"
-    if src in ("admm_wave.hip", "admm_waveres.hip") and kernel_name.endswith(",pm>"):  # and the two wave kernels' per-instance-model instantiations
-        src = src.replace(".hip", "_pm.hip")
+    src = unit_of(kernel_name)
     try:
         return device_isa_sha(src) if src else None
     except (OSError, AssertionError, KeyError):

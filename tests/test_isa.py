@@ -17,81 +17,9 @@ import re
 import pytest
 
 import accelerated_tinympc_amd as T
+from isa_tools import hazards, is_dpp, iteration_loop, kernels_of, regs, scratch_sizes
 
 DPP_SOURCES = ["admm_rowlane.hip", "admm_rowloop.hip", "admm_quadlane.hip", "admm_steps.hip", "dispatch_order.hip"]
-VALU_EXEC_WRITERS = ("v_cmpx",)
-
-
-def kernels_of(listing: str):
-    """{mangled name: [instruction lines]} for every kernel (function body up to its .amdhsa_kernel / end marker)."""
-    out, cur, name = {}, None, None
-    for line in listing.split("\n"):
-        m = re.match(r"^(_Z\w+):\s*(;.*)?$", line)
-        if m:
-            name, cur = m.group(1), []
-            out[name] = cur
-            continue
-        if cur is None:
-            continue
-        if line.startswith(".Lfunc_end") or line.lstrip().startswith(".amdhsa_kernel") or line.lstrip().startswith(".section"):
-            cur = None
-            continue
-        t = line.strip()
-        if not t or t[0] in ";." and not re.match(r"^\.LBB\d+_\d+:", t):
-            continue
-        cur.append(t.split(";")[0].strip())
-    return out
-
-
-def regs(op: str):
-    """VGPR numbers named by one operand: v7 -> {7}, v[4:7] -> {4,5,6,7}; anything else -> {}."""
-    op = op.strip().rstrip(",")
-    op = re.sub(r"^[-|]+|[|]+$", "", op)
-    m = re.match(r"^v(\d+)$", op)
-    if m:
-        return {int(m.group(1))}
-    m = re.match(r"^v\[(\d+):(\d+)\]$", op)
-    if m:
-        return set(range(int(m.group(1)), int(m.group(2)) + 1))
-    return set()
-
-
-def is_dpp(ins: str):
-    return "_dpp" in ins.split()[0] or re.search(r"\b(row_newbcast|row_shr|row_shl|row_ror|row_bcast|quad_perm|row_mirror|row_half_mirror|wave_shr|wave_ror|row_share|row_xmask):?", ins) is not None
-
-
-def hazards(lines):
-    """[(index, text, reason)] of DPP instructions with a VALU write of their DPP source less than 2 wait states ahead, or a VALU
-    write of EXEC less than 5 wait states ahead.  Labels end the look-back (another path may join there)."""
-    bad = []
-    for i, ins in enumerate(lines):
-        if ins.endswith(":") or not ins.startswith("v_") or not is_dpp(ins):
-            continue
-        ops = [o for o in re.split(r",\s*", ins.split(None, 1)[1])] if len(ins.split(None, 1)) > 1 else []
-        if len(ops) < 2:
-            continue
-        src = regs(ops[1].split()[0])  # src0 is the operand that goes through the DPP network
-        ws, j = 0, i - 1
-        while j >= 0 and ws < 5:
-            p = lines[j]
-            if p.endswith(":"):
-                break
-            op = p.split()[0]
-            if op == "s_nop":
-                ws += int(p.split()[1]) + 1
-                j -= 1
-                continue
-            if op.startswith("v_") and not op.startswith(("v_cmp_", "v_readlane", "v_readfirstlane")):
-                if op.startswith(VALU_EXEC_WRITERS):
-                    bad.append((i, ins, f"VALU write of EXEC {ws} wait states ahead: {p}"))
-                elif ws < 2:
-                    pops = p.split(None, 1)[1] if len(p.split(None, 1)) > 1 else ""
-                    dst = regs(re.split(r",\s*", pops)[0]) if pops else set()
-                    if dst & src:
-                        bad.append((i, ins, f"VALU write of the DPP source {ws} wait states ahead: {p}"))
-            ws += 1
-            j -= 1
-    return bad
 
 
 @pytest.fixture(scope="module")
@@ -169,18 +97,6 @@ SCRATCH_PINS = {
 }
 
 
-def scratch_sizes(listing: str):
-    out, name = {}, None
-    for line in listing.split("\n"):
-        m = re.match(r"^(_Z\w+):", line)
-        if m:
-            name = m.group(1)
-        m = re.match(r"^; ScratchSize: (\d+)", line)
-        if m and name:
-            out[name] = int(m.group(1))
-    return out
-
-
 def test_scratch_sizes_of_the_headline_kernels_are_pinned(listings):
     for (src, key), pin in SCRATCH_PINS.items():
         sizes = {k: v for k, v in scratch_sizes(listings[src]).items() if key in k}
@@ -224,20 +140,6 @@ def test_packed_adds_only_where_they_are_deliberate(listings):
     t16 = kernels_of(listings["admm_tile16.hip"])
     exact = [l for n, l in t16.items() if "admm_tile16_kernelILi30ELb1E" in n]
     assert exact and all(sum(1 for i in l if i.startswith("v_pk_add_f32")) > 500 for l in exact)
-
-
-def iteration_loop(lines):
-    """(first, last) line of the ADMM iteration loop of a tile16 kernel: the innermost loop of the listing that contains the MFMAs of a whole
-    iteration (58 unrolled sweep steps); the tile-queue loop around it is longer."""
-    labels = {l[:-1]: i for i, l in enumerate(lines) if l.endswith(":")}
-    loops = []
-    for i, l in enumerate(lines):
-        m = re.search(r"s_cbranch_\w+\s+(\.LBB\d+_\d+)", l) or re.search(r"s_branch\s+(\.LBB\d+_\d+)", l)
-        if m and labels.get(m.group(1), 10 ** 9) < i:
-            loops.append((labels[m.group(1)], i))
-    with_mfma = [(a, b) for a, b in loops if sum(1 for l in lines[a:b] if l.startswith("v_mfma")) >= 200]
-    assert with_mfma
-    return min(with_mfma, key=lambda t: t[1] - t[0])
 
 
 def test_tile16_iteration_loop_is_free_of_scratch_traffic(listings):

@@ -6,8 +6,7 @@ from pathlib import Path
 import pytest
 
 import accelerated_tinympc_amd as T
-from test_isa import kernels_of
-from test_isa_sim64 import fingerprint, kernel_key
+from isa_tools import fingerprint, kernel_key, kernels_of
 
 CSRC = Path(T.build.CSRC)
 HOST_FILES = ("tinympc_batch.hip", "tinympc_batch64.hip")

@@ -7,7 +7,7 @@ import re
 import pytest
 
 import accelerated_tinympc_amd as T
-from test_isa import hazards, kernels_of, scratch_sizes
+from isa_tools import hazards, kernels_of, scratch_sizes
 
 # admm_rowlane_pm_kernel<NX, NU, N, EXACT, MPC, BPI>: bytes of scratch per lane; every instantiation not listed has none
 PM_SCRATCH = {(12, 4, 30, 1, 0, 0): 64, (12, 4, 30, 1, 1, 0): 84, (12, 4, 30, 1, 0, 1): 56,

@@ -2,13 +2,12 @@
 instantiations of admm_f64_rows_kernel and admm_f64_kernel in translation units of their own) beside their shared twins, read from the `hipcc -S`
 listings (build.device_asm).  CPU test: hipcc cross-compiles, no GPU needed.  The figures are pinned as built, with no threshold on the growth:
 rho and the record address are per-lane values where the twin has scalars ('Per-instance models and the batched Riccati', has the same table and what it shows)."""
-import re
 from pathlib import Path
 
 import pytest
 
 import accelerated_tinympc_amd as T
-from test_isa import kernels_of
+from isa_tools import figures, kernels_of
 
 # (NX, NU, N or capacity, RT): (VGPRs, AGPRs, bytes of scratch per lane) of the one-solve pm instantiation | of its shared twin in admm_f64_rows.hip
 SOLVE_PM = {(12, 4, 10, 0): (256, 0, 164), (12, 4, 30, 0): (256, 226, 0), (12, 4, 20, 0): (256, 208, 0), (4, 1, 10, 0): (251, 0, 0), (8, 4, 9, 0): (256, 0, 104),
@@ -30,18 +29,6 @@ LOOP = {(12, 4, 10, 0): (256, 0, 508), (12, 4, 30, 0): (256, 256, 708), (12, 4, 
 THREAD_PM = {(12, 4): (256, 256, 1052), (4, 1): (166, 0, 0), (8, 4): (256, 184, 0), (12, 2): (256, 256, 580), (4, 2): (225, 0, 0), (4, 4): (245, 0, 0), (16, 4): (256, 256, 3292)}
 THREAD = {(12, 4): (256, 256, 1528), (4, 1): (256, 22, 0), (8, 4): (256, 256, 1412), (12, 2): (256, 256, 1184), (4, 2): (256, 72, 0), (4, 4): (256, 112, 0), (16, 4): (256, 256, 2696)}
 PM_KERNELS = len(SOLVE_PM) + len(LOOP_PM) + len(THREAD_PM)  # 17 + 11 + 7 = 35
-
-
-def figures(listing, kernel, want):
-    """{template literals: (VGPRs, AGPRs, scratch, waves per SIMD)} of the instantiations of `kernel` whose mangled name satisfies want(name)"""
-    out = {}
-    for m in re.finditer(rf"^(_Z\w*\d+{kernel}I\w*):", listing, re.M):
-        if not want(m.group(1)):
-            continue
-        tail = listing[m.start():]
-        g = lambda k: int(re.search(rf"^; {k}: (\d+)", tail, re.M).group(1))
-        out[tuple(int(v) for v in re.findall(r"L[ib](\d+)E", m.group(1)))] = (g("NumVgprs"), g("NumAgprs"), g("ScratchSize"), g("Occupancy"))
-    return out
 
 
 @pytest.fixture(scope="module")
@@ -105,14 +92,3 @@ def test_design_records_the_figures_beside_the_twins():
     for key in THREAD_PM:
         row = f"| thread ({key[0]},{key[1]}) | {cell(THREAD_PM[key])} | {cell(THREAD[key])} |"
         assert row in sec, f"DESIGN has no row '{row}'"
-
-
-def test_pm_kernel_names_are_routed_to_the_new_units():
-    T.build.build()
-    sha, of = T.build.device_isa_sha, T.build.kernel_isa_sha
-    new = ("admm_f64_rows_pm.hip", "admm_f64_rowsim_pm.hip", "admm_f64_thread_pm.hip")
-    assert len({sha(u) for u in new + ("admm_f64_rows.hip", "admm_f64_rowsim.hip", "admm_f64_thread.hip")}) == 6
-    assert of("rows64<12,4,10,pm>") == of("rows64<12,2,n<=32,pm>") == of("rows64<12,4,n<=64,pm>") == sha("admm_f64_rows_pm.hip")
-    assert of("rows64<12,4,10,mpc,pm>") == of("rows64<12,4,10,sim,pm>") == sha("admm_f64_rowsim_pm.hip")
-    assert of("thread64<12,4,pm>") == of("thread64<16,4,pm>") == sha("admm_f64_thread_pm.hip")
-    assert of("rows64<12,4,10>") == sha("admm_f64_rows.hip") and of("rows64<12,4,10,sim>") == sha("admm_f64_rowsim.hip") and of("thread64<12,4>") == sha("admm_f64_thread.hip")

@@ -8,8 +8,7 @@ from pathlib import Path
 import pytest
 
 import accelerated_tinympc_amd as T
-from test_isa import kernels_of
-from test_isa_models64 import figures
+from isa_tools import figures, kernels_of
 
 # (NX, NU, EXACT): (VGPRs, AGPRs, bytes of scratch per lane) of admm_waveres_pm_kernel | of admm_waveres_kernel
 WAVERES_PM = {(16, 4, 0): (186, 0, 0), (16, 4, 1): (196, 0, 0), (16, 8, 0): (198, 0, 0), (16, 8, 1): (200, 0, 0), (20, 8, 0): (206, 0, 0), (20, 8, 1): (212, 0, 0),
@@ -96,12 +95,3 @@ def test_design_records_the_figures_beside_the_twins():
     for key in WAVESTREAM_PM:
         row = f"| wavestream ({key[0]},{key[1]},PF={key[2]},WPS={key[3]}) | {cell(WAVESTREAM_PM[key])} | {cell(WAVESTREAM[key])} |"
         assert row in sec, f"DESIGN has no row '{row}'"
-
-
-def test_pm_kernel_names_are_routed_to_the_new_units():
-    T.build.build()
-    sha, of = T.build.device_isa_sha, T.build.kernel_isa_sha
-    assert len({sha(u) for u in ("admm_waveres_pm.hip", "admm_wave_pm.hip", "admm_waveres.hip", "admm_wave.hip")}) == 4
-    assert of("waveres<32,16,exact,pm>") == of("waveres<16,4,fast,pm>") == sha("admm_waveres_pm.hip")
-    assert of("wavestream<32,16,exact,pm>") == sha("admm_wave_pm.hip")
-    assert of("waveres<32,16,exact>") == sha("admm_waveres.hip") and of("wavestream<16,4,exact>") == sha("admm_wave.hip")

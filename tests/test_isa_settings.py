@@ -6,7 +6,7 @@ import re
 import pytest
 
 import accelerated_tinympc_amd as T
-from test_isa import hazards, kernels_of, scratch_sizes
+from isa_tools import hazards, kernels_of, scratch_sizes
 
 ROWLANE = [(12, 4, 30), (12, 4, 25), (12, 4, 20), (12, 4, 10), (4, 1, 10), (8, 3, 7), (12, 4, 40), (12, 4, 50)]
 ROWDIMS = [(12, 4), (4, 1), (8, 3), (8, 4), (12, 2), (4, 2), (4, 4), (2, 2)]

@@ -1,7 +1,7 @@
 """Static figures of the fp64 per-instance-settings kernels (admm_f64_rows_ps.hip, admm_f64_rowloop_ps.hip, admm_f64_thread_ps.hip: the ",ps"
 instantiations of admm_f64_rows_kernel and admm_f64_kernel and the ps forms of two step functions, in translation units of their own) beside their
 shared twins, read from the `hipcc -S` listings (build.device_asm).  CPU test: hipcc cross-compiles, no GPU needed.  Kernel names, register and
-scratch figures, occupancy and unit hashes only.  The figures are pinned as built, with no threshold on the growth: the record's lane index and, for
+scratch figures and occupancy only (tests/test_device_code.py has the unit hashes and the routing of the names).  The figures are pinned as built, with no threshold on the growth: the record's lane index and, for
 the span of an iteration, its eight words are per-lane values where the twin has scalars ('Per-instance settings: the fp64 library', has
 the same table and what it shows)."""
 from pathlib import Path
@@ -9,8 +9,7 @@ from pathlib import Path
 import pytest
 
 import accelerated_tinympc_amd as T
-from test_isa import kernels_of
-from test_isa_models64 import figures
+from isa_tools import figures, kernels_of
 
 # (NX, NU, N or capacity, RT): (VGPRs, AGPRs, bytes of scratch per lane) of the one-solve ps instantiation | of its shared twin in admm_f64_rows.hip
 SOLVE_PS = {(12, 4, 10, 0): (256, 0, 176), (12, 4, 30, 0): (256, 232, 0), (12, 4, 20, 0): (256, 208, 0), (4, 1, 10, 0): (255, 0, 0), (8, 4, 9, 0): (256, 0, 100),
@@ -113,29 +112,3 @@ def test_design_records_the_figures_beside_the_twins():
     for key in STEP_PS:
         row = f"| {'update_slack' if key[2] == 1 else 'termination_condition'} ({key[0]},{key[1]}) | {cell(STEP_PS[key])} | {cell(STEP[key])} |"
         assert row in sec, f"DESIGN has no row '{row}'"
-
-
-def test_ps_kernel_names_are_routed_to_the_new_units():
-    T.build.build()
-    sha, of = T.build.device_isa_sha, T.build.kernel_isa_sha
-    assert len({sha(u) for u in NEW + ("admm_f64_rows.hip", "admm_f64_rowsim.hip", "admm_f64_thread.hip")}) == 6
-    assert of("rows64<12,4,10,ps>") == of("rows64<12,2,n<=32,ps>") == of("rows64<4,2,n<=64,ps>") == sha("admm_f64_rows_ps.hip")
-    assert of("rows64<12,4,10,mpc,ps>") == of("rows64<12,2,n<=32,mpc,ps>") == sha("admm_f64_rowloop_ps.hip")
-    assert of("thread64<12,4,ps>") == of("thread64<16,4,ps>") == sha("admm_f64_thread_ps.hip")
-    assert of("rows64<12,4,10>") == of("rows64<12,4,10,mpc>") == sha("admm_f64_rows.hip") and of("rows64<12,4,10,sim>") == sha("admm_f64_rowsim.hip")
-    assert of("thread64<12,4>") == sha("admm_f64_thread.hip") and of("rows64<12,4,10,pm>") == sha("admm_f64_rows_pm.hip") and of("thread64<12,4,pm>") == sha("admm_f64_thread_pm.hip")
-
-
-def test_the_profile_shows_every_existing_unit_s_hash_unmoved():
-    """profiles/settings64_isa.txt: parent and new column of every unit of build.SOURCES; the new column is what the objects of this tree hash to"""
-    T.build.build()
-    lines = (Path(__file__).resolve().parents[1] / "profiles" / "settings64_isa.txt").read_text().splitlines()
-    rows = {ln.split()[0]: ln.split()[1:] for ln in lines if ln and not ln.startswith("#")}
-    assert set(rows) == set(T.build.SOURCES)
-    for u in T.build.SOURCES:
-        if rows[u][0] == "no":   # "no device code (host only), parent and new"
-            continue
-        if u in NEW:
-            assert rows[u][:2] == ["(new", "unit)"] and rows[u][2] == T.build.device_isa_sha(u), rows[u]
-        else:
-            assert rows[u][0] == rows[u][1] == T.build.device_isa_sha(u) and rows[u][2] == "same", (u, rows[u])

@@ -5,7 +5,7 @@ import re
 import pytest
 
 import accelerated_tinympc_amd as T
-from test_isa import hazards, kernels_of, scratch_sizes
+from isa_tools import hazards, kernels_of, scratch_sizes
 
 ROWLANE = [(12, 4, 30), (12, 4, 25), (12, 4, 20), (12, 4, 10), (4, 1, 10), (8, 3, 7), (12, 4, 40), (12, 4, 50)]
 # admm_rowsim_kernel / admm_rowsim_pm_kernel <NX, NU, N, EXACT>: bytes of scratch per lane as built; every instantiation not listed has none.  The MPC

@@ -1,14 +1,13 @@
 """Static figures of the fp64 simulated closed loop's kernels (admm_f64_rowsim.hip: the SIM instantiations of admm_f64_rows_kernel in a
 translation unit of their own) beside their MPC twins in admm_f64_rows.hip, read from the `hipcc -S` listings (build.device_asm), and the
 instruction streams of every kernel of the fp64 library, pinned across its units.  CPU test: hipcc cross-compiles, no GPU needed."""
-import hashlib
 import re
 from pathlib import Path
 
 import pytest
 
 import accelerated_tinympc_amd as T
-from test_isa import kernels_of
+from isa_tools import fingerprint, kernel_key, kernels_of, loop_figures
 
 # the fp64 library's translation units with device code: the four kernel units and the unit of the three helper kernels (the host file has none)
 F64_UNITS = ("admm_f64_thread.hip", "admm_f64_rows.hip", "admm_f64_rowsim.hip", "admm_f64_plant.hip", "batch64_helpers.hip")
@@ -22,40 +21,6 @@ SIM = {(12, 4, 10, 0): (256, 0, 508), (12, 4, 30, 0): (256, 256, 708), (12, 4, 2
 MPC = {(12, 4, 10, 0): (256, 0, 440), (12, 4, 30, 0): (256, 256, 644), (12, 4, 20, 0): (256, 256, 332), (4, 1, 10, 0): (256, 0, 24), (8, 4, 9, 0): (256, 0, 136),
        (12, 4, 32, 1): (256, 256, 264), (4, 1, 32, 1): (256, 212, 0), (8, 4, 32, 1): (256, 256, 48), (12, 2, 32, 1): (256, 256, 164), (4, 2, 32, 1): (256, 216, 0),
        (4, 4, 32, 1): (256, 228, 0)}
-
-
-def figures(listing, want_sim):
-    """{(NX, NU, N, RT): (VGPRs, AGPRs, scratch, waves per SIMD)} of the closed-loop instantiations of admm_f64_rows_kernel in a listing"""
-    out = {}
-    for m in re.finditer(r"^(_Z\w*admm_f64_rows_kernelILi(\d+)ELi(\d+)ELi(\d+)ELb([01])ELb1E\w*):", listing, re.M):
-        if ("Sim64" in m.group(1)) != want_sim:
-            continue
-        tail = listing[m.start():]
-        g = lambda k: int(re.search(rf"^; {k}: (\d+)", tail, re.M).group(1))
-        out[tuple(int(v) for v in m.groups()[1:])] = (g("NumVgprs"), g("NumAgprs"), g("ScratchSize"), g("Occupancy"))
-    return out
-
-
-def kernel_key(name):
-    """mangled kernel name -> what it instantiates: (kernel, template literals, closed loop, simulated)"""
-    base = re.search(r"\d+([a-z_0-9]+?_kernel)", name).group(1)
-    lits = tuple(int(v) for v in re.findall(r"L[ib](\d+)E", name))
-    return (base, lits, "Mpc64" in name, "Sim64" in name)
-
-
-def fingerprint(listings):
-    """(kernels, instruction lines, sha256[:16]) over the instruction streams of every kernel of the listings, whichever unit holds it and whatever
-    it is called there: keyed by kernel_key, block labels unnumbered, the kernel's own name replaced"""
-    ks = {}
-    for text in listings:
-        for name, lines in kernels_of(text).items():
-            k = kernel_key(name)
-            assert k not in ks, k
-            ks[k] = [re.sub(r"\.LBB\d+_", ".LBB_", l).replace(name, "K") for l in lines]
-    h = hashlib.sha256()
-    for k in sorted(ks):
-        h.update((repr(k) + "\n" + "\n".join(ks[k]) + "\n").encode())
-    return len(ks), sum(map(len, ks.values())), h.hexdigest()[:16]
 
 
 @pytest.fixture(scope="module")
@@ -81,14 +46,14 @@ def test_the_plant_unit_holds_the_three_plant_kernels_of_every_class():
 
 
 def test_every_mpc_instantiation_has_a_sim_twin_at_its_occupancy(sim_listing, main_listing):
-    sim, mpc = figures(sim_listing, True), figures(main_listing, False)
+    sim, mpc = loop_figures(sim_listing, True), loop_figures(main_listing, False)
     assert set(sim) == set(mpc) == set(SIM) == set(MPC)
     for key in sim:
         assert sim[key][3] == mpc[key][3] == (2 if key[2] <= 12 else 1), (key, sim[key], mpc[key])
 
 
 def test_register_and_scratch_figures_are_pinned(sim_listing, main_listing):
-    sim, mpc = figures(sim_listing, True), figures(main_listing, False)
+    sim, mpc = loop_figures(sim_listing, True), loop_figures(main_listing, False)
     for key, pin in SIM.items():
         assert sim[key][:3] == pin, f"SIM {key}: (VGPRs, AGPRs, scratch) = {sim[key][:3]}, pinned at {pin}"
     for key, pin in MPC.items():
@@ -111,12 +76,3 @@ def test_the_fp64_kernels_keep_their_instruction_streams(sim_listing, main_listi
                        for u in F64_UNITS])
     print(f"fingerprint of the fp64 units = {got}, pinned at {F64_FINGERPRINT}")
     assert got == F64_FINGERPRINT
-
-
-def test_kernel_names_are_routed_to_their_units():
-    T.build.build()
-    sha = T.build.device_isa_sha
-    assert len({sha(u) for u in F64_UNITS}) == len(F64_UNITS)
-    assert T.build.kernel_isa_sha("rows64<12,4,10,sim>") == sha("admm_f64_rowsim.hip")
-    assert T.build.kernel_isa_sha("rows64<12,4,10,mpc>") == T.build.kernel_isa_sha("rows64<12,4,10>") == sha("admm_f64_rows.hip")
-    assert T.build.kernel_isa_sha("thread64<12,4>") == sha("admm_f64_thread.hip")

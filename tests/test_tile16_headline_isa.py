@@ -1,5 +1,5 @@
 """Static checks of the headline instantiations admm_tile16_kernel<N, exact, cold> on the listing the compiler emitted (CPU test, like
-tests/test_isa.py, whose listing helpers it uses).
+tests/test_isa.py; the listing helpers are those of tests/isa_tools.py).
 
 These instantiations run each sweep of an ADMM iteration under ONE narrowed EXEC (admm_tile16.hip: exec_narrow / exec_restore) instead of
 narrowing it around each of the sixty state updates.  hipcc is not told about the narrowed EXEC, so what it emitted is checked here, inside
@@ -24,7 +24,7 @@ import re
 import pytest
 
 import accelerated_tinympc_amd as T
-from test_isa import iteration_loop, kernels_of, scratch_sizes
+from isa_tools import iteration_loop, kernels_of, scratch_sizes
 
 HEAD = "admm_tile16_kernelILi{N}ELb1ELb1ELb0ELb0ELb0EEE"
 # loop size of the N = 30 kernel, instructions per ADMM iteration (labels not counted): the parent of this change 4 794 (60 EXEC regions, the

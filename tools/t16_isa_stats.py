@@ -5,7 +5,7 @@ from pathlib import Path
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
 import accelerated_tinympc_amd as T
-spec = importlib.util.spec_from_file_location('ti', ROOT / 'tests/test_isa.py'); ti = importlib.util.module_from_spec(spec); spec.loader.exec_module(ti)
+spec = importlib.util.spec_from_file_location('ti', ROOT / 'tests/isa_tools.py'); ti = importlib.util.module_from_spec(spec); spec.loader.exec_module(ti)
 for src in ("admm_tile16.hip", "admm_tile16_pi.hip"):
     txt = T.build.device_asm(src).read_text()
     sizes = ti.scratch_sizes(txt)
