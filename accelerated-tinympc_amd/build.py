@@ -12,6 +12,7 @@ import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
+from types import SimpleNamespace
 from typing import NamedTuple
 
 PKG = Path(__file__).resolve().parent
@@ -28,7 +29,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
 
 
 class Unit(NamedTuple):
-    """One translation unit of libtinympc_hip.so.  Everything build() and the tools know about a unit is its row of UNITS."""
+    """One translation unit of libtinympc_hip.so.  Everything build() and the tools know about a unit is its row of UNITS (or of ADDED_UNITS)."""
     source: str
     parent: str | None = None      # the kernel source it #includes (a variant unit: the parent's text compiled again): rebuilt with it
     flags: tuple = ()              # extra hipcc flags
@@ -80,23 +81,34 @@ UNITS = (
     Unit("riccati.cpp"),
     Unit("riccati_batch.hip"),
 )
-# the views of the table that build(), bench.py, the tests and the tools read
-SOURCES = [u.source for u in UNITS]
-INCLUDED_SOURCES = {u.source: [u.parent] for u in UNITS if u.parent}
-EXTRA_FLAGS = {u.source: [*u.flags, *os.environ.get(u.flags_env or "", "").split()] for u in UNITS if u.flags or u.flags_env}
-KERNEL_SOURCES = {u.family: u.source for u in UNITS if u.family and not u.tails}  # family -> its default unit
+# Units added since tests/golden/device_code.json was written.  That record is one of the suite's fixed files and has exactly the rows of UNITS, so a unit that
+# arrives with a feature is listed here: compiled, linked (after UNITS, in this order) and routed like any other, and recorded by the same readers in the record
+# beside it, tests/golden/device_code_added.json (tests/test_device_code_added.py; `python tools/device_code.py --write --added`).  A later feature adds its
+# rows to this table and that record.  Here: the wave kernels' text compiled once more with per-instance settings, each a variant of its pm sibling's parent.
+ADDED_UNITS = (
+    Unit("admm_wave_ps.hip", "admm_wave.hip", family="wavestream", tails=(",ps>",)),
+    Unit("admm_waveres_ps.hip", "admm_waveres.hip", flags_env="TINYMPC_WAVERES_FLAGS", family="waveres", tails=(",ps>",)),
+)
+ALL_UNITS = UNITS + ADDED_UNITS
+# the views of the tables that build(), bench.py, the tests and the tools read
+SOURCES = [u.source for u in UNITS]             # the units of the standing record
+ADDED_SOURCES = [u.source for u in ADDED_UNITS]
+LINKED_SOURCES = SOURCES + ADDED_SOURCES         # everything build() compiles and links: the rows of the two records together
+INCLUDED_SOURCES = {u.source: [u.parent] for u in ALL_UNITS if u.parent}
+EXTRA_FLAGS = {u.source: [*u.flags, *os.environ.get(u.flags_env or "", "").split()] for u in ALL_UNITS if u.flags or u.flags_env}
+KERNEL_SOURCES = {u.family: u.source for u in ALL_UNITS if u.family and not u.tails}  # family -> its default unit
 
 
 def unit_of(kernel_name: str) -> str | None:
     """The translation unit that holds the device code behind a kernel name such as 'tile16<12,4,30,exact,pi>': of the family's units the one
     with the longest matching tail, else the family's default unit; None for an unknown family."""
     family = kernel_name.split("<", 1)[0]
-    tails = [(t, u.source) for u in UNITS if u.family == family for t in u.tails if kernel_name.endswith(t)]
+    tails = [(t, u.source) for u in ALL_UNITS if u.family == family for t in u.tails if kernel_name.endswith(t)]
     return max(tails, key=lambda t: len(t[0]))[1] if tails else KERNEL_SOURCES.get(family)
 
 
 def _objs():
-    return [(CSRC / s, PKG / "lib" / (Path(s).stem + ".o")) for s in SOURCES if (CSRC / s).exists()]
+    return [(CSRC / s, PKG / "lib" / (Path(s).stem + ".o")) for s in LINKED_SOURCES if (CSRC / s).exists()]
 
 
 def needs_build() -> bool:
@@ -215,6 +227,10 @@ def kernel_isa_sha(kernel_name: str) -> str | None:
         return device_isa_sha(src) if src else None
     except (OSError, AssertionError, KeyError):
         return None
+
+
+# the added units as isa_tools.device_code() reads a build: its SOURCES and the two readers
+ADDED = SimpleNamespace(SOURCES=ADDED_SOURCES, device_isa_sha=device_isa_sha, device_asm=device_asm)
 
 
 if __name__ == "__main__":

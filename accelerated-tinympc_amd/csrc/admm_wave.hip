@@ -22,12 +22,21 @@ namespace tinympc
 // Under TINY_WAVE_PM_UNIT (admm_wave_pm.hip) it is admm_wavestream_pm_kernel(P, M) with per-instance models: the instance is the wave, so its own gain
 // table is a wave-uniform base address and its rho a wave-uniform value.  M is the trailing argument there and an unused local here; it is read under
 // `if constexpr (PM)` only, and nothing else of the body differs.
-#ifdef TINY_WAVE_PM_UNIT
+// Under TINY_WAVE_PS_UNIT (admm_wave_ps.hip) it is admm_wavestream_ps_kernel(P, SP) with per-instance settings: `my`, the settings view of the solve frame
+// (rowlane_math.h), is the instance's own record, read once at entry into scalar registers, where it is the launch's RowParams here.  The iteration loop runs
+// to my.max_iter: the wave is the instance, so no other instance's budget concerns it.
+#if defined(TINY_WAVE_PM_UNIT)
 #define TINY_WAVESTREAM_KERNEL admm_wavestream_pm_kernel
 #define TINY_WAVESTREAM_ARGS const RowParams P, const ModelParams M
+#define TINY_WAVE_SETTINGS_VIEW const RowParams &my = P
+#elif defined(TINY_WAVE_PS_UNIT)
+#define TINY_WAVESTREAM_KERNEL admm_wavestream_ps_kernel
+#define TINY_WAVESTREAM_ARGS const RowParams P, const SettingsParams SP
+#define TINY_WAVE_SETTINGS_VIEW const InstSettings my = wave_settings(SP, inst)
 #else
 #define TINY_WAVESTREAM_KERNEL admm_wavestream_kernel
 #define TINY_WAVESTREAM_ARGS const RowParams P
+#define TINY_WAVE_SETTINGS_VIEW const RowParams &my = P
 #endif
 template <int NX, int NU, int PF, int WPS>
 __global__ __launch_bounds__(WAVE, WPS) void TINY_WAVESTREAM_KERNEL(TINY_WAVESTREAM_ARGS)
@@ -42,6 +51,7 @@ __global__ __launch_bounds__(WAVE, WPS) void TINY_WAVESTREAM_KERNEL(TINY_WAVESTR
     __shared__ __attribute__((aligned(16))) float vec[WAVE]; // broadcast buffer of lane_products
     const int lane = threadIdx.x;
     const int inst = blockIdx.x;
+    TINY_WAVE_SETTINGS_VIEW;
     const bool is_x = lane < NX, is_u = (lane >= NX) && (lane < NX + NU);
     const int N = P.N;
     const int rowbase = (inst * N) * WAVE + lane;
@@ -63,9 +73,9 @@ __global__ __launch_bounds__(WAVE, WPS) void TINY_WAVESTREAM_KERNEL(TINY_WAVESTR
         pterm = -wreduce<PL::TERM>(t);
     }
     SolveFrame F(P, inst, true);
-    for (int it = 0; it < P.max_iter; ++it)
+    for (int it = 0; it < my.max_iter; ++it)
     {
-        const bool last_iter = (it == P.max_iter - 1);
+        const bool last_iter = (it == my.max_iter - 1);
         const bool zero_state = (it == 0) && (P.cold_start != 0);
         const bool zero_duals = (it == 0) && ((P.cold_start | P.duals_zero) != 0);
         float s = x0, pri = 0.f, dua = 0.f, t1 = 0.f;
@@ -112,7 +122,7 @@ __global__ __launch_bounds__(WAVE, WPS) void TINY_WAVESTREAM_KERNEL(TINY_WAVESTR
         }
         const float pN = pterm - rho * t1; // admm.cpp:83-84
         P.pd[rowbase + (N - 1) * WAVE] = is_x ? pN : 0.f;
-        if (F.judge(P, it, wave_residuals(pri, dua, is_x, is_u, rho))) break; // admm.cpp:91-109; wave-uniform: the instance is the wave
+        if (F.judge(my, it, wave_residuals(pri, dua, is_x, is_u, rho))) break; // admm.cpp:91-109; wave-uniform: the instance is the wave
         float p = pN;
         P.vz[rowbase + (N - 1) * WAVE] = P.vzn[rowbase + (N - 1) * WAVE]; // admm.cpp:141-142
         struct Bwd { float sn, g, xr; };
@@ -146,7 +156,7 @@ __global__ __launch_bounds__(WAVE, WPS) void TINY_WAVESTREAM_KERNEL(TINY_WAVESTR
             }
         }
     }
-    if (F.no_iterations(P, inst, lane == 0)) return;
+    if (F.no_iterations(my, P, inst, lane == 0)) return;
     {
         // live-out: q, r (admm.cpp:80-82) and, for a converged instance, x,u regenerated from the d it converged with
         const bool solved = F.solved();
@@ -175,7 +185,23 @@ __global__ __launch_bounds__(WAVE, WPS) void TINY_WAVESTREAM_KERNEL(TINY_WAVESTR
     }
 }
 
-#ifdef TINY_WAVE_PM_UNIT
+#if defined(TINY_WAVE_PS_UNIT)
+// Per-instance settings (tiny_batch_set_instance_settings with tiny_batch_set_row_kernel(tb, 6)): the launcher of the PS instantiations, compiled as
+// admm_wave_ps.hip (a translation unit of its own, so that admm_wave.hip keeps its code).
+hipError_t launch_admm_wavestream_ps(int nx, int nu, const RowParams &P, const SettingsParams &SP, hipStream_t stream)
+{
+    if (!SP.rec) return hipErrorInvalidValue;
+#define TINY_WAVE_PS_DISPATCH(NX, NU)                                                                          \
+    if (nx == NX && nu == NU)                                                                                  \
+    {                                                                                                          \
+        if (P.batch <= 2048) hipLaunchKernelGGL((admm_wavestream_ps_kernel<NX, NU, 4, 2>), dim3(P.batch), dim3(WAVE), 0, stream, P, SP); \
+        else hipLaunchKernelGGL((admm_wavestream_ps_kernel<NX, NU, 1, 3>), dim3(P.batch), dim3(WAVE), 0, stream, P, SP);                 \
+        return hipGetLastError();                                                                              \
+    }
+    TINY_FOR_EACH_WAVEDIMS(TINY_WAVE_PS_DISPATCH)
+    return hipErrorInvalidValue;
+}
+#elif defined(TINY_WAVE_PM_UNIT)
 // Per-instance models (tiny_batch_set_models with tiny_batch_set_row_kernel(tb, 6)): the launcher of the PM instantiations, compiled as admm_wave_pm.hip
 // (a translation unit of its own, so that admm_wave.hip keeps its code).  The gain table is the one admm_waveres_pm.hip packs.
 hipError_t launch_admm_wavestream_pm(int nx, int nu, const RowParams &P, const ModelParams &M, hipStream_t stream)
@@ -212,6 +238,6 @@ hipError_t launch_admm_wavestream(int nx, int nu, const RowParams &P, hipStream_
     TINY_FOR_EACH_WAVEDIMS(TINY_WAVE_DISPATCH)
     return hipErrorInvalidValue;
 }
-#endif // TINY_WAVE_PM_UNIT
+#endif // TINY_WAVE_PS_UNIT, TINY_WAVE_PM_UNIT
 
 } // namespace tinympc

@@ -47,12 +47,21 @@ struct StepRegs
 // Under TINY_WAVERES_PM_UNIT (admm_waveres_pm.hip) it is admm_waveres_pm_kernel(P, M) with per-instance models: the instance is the wave, so its own
 // gain table is a wave-uniform base address and its rho a wave-uniform value.  M is the trailing argument there and an unused local here; it is read
 // under `if constexpr (PM)` only, and nothing else of the body differs.
-#ifdef TINY_WAVERES_PM_UNIT
+// Under TINY_WAVERES_PS_UNIT (admm_waveres_ps.hip) it is admm_waveres_ps_kernel(P, SP) with per-instance settings: `my`, the settings view of the solve frame
+// (rowlane_math.h), is the instance's own record, read once at entry into scalar registers, where it is the launch's RowParams here.  The iteration loop runs
+// to my.max_iter: the wave is the instance, so no other instance's budget concerns it.
+#if defined(TINY_WAVERES_PM_UNIT)
 #define TINY_WAVERES_KERNEL admm_waveres_pm_kernel
 #define TINY_WAVERES_ARGS const RowParams P, const ModelParams M
+#define TINY_WAVE_SETTINGS_VIEW const RowParams &my = P
+#elif defined(TINY_WAVERES_PS_UNIT)
+#define TINY_WAVERES_KERNEL admm_waveres_ps_kernel
+#define TINY_WAVERES_ARGS const RowParams P, const SettingsParams SP
+#define TINY_WAVE_SETTINGS_VIEW const InstSettings my = wave_settings(SP, inst)
 #else
 #define TINY_WAVERES_KERNEL admm_waveres_kernel
 #define TINY_WAVERES_ARGS const RowParams P
+#define TINY_WAVE_SETTINGS_VIEW const RowParams &my = P
 #endif
 template <int NX, int NU, bool EXACT>
 __global__ __launch_bounds__(WAVE, 2) void TINY_WAVERES_KERNEL(TINY_WAVERES_ARGS)
@@ -72,6 +81,7 @@ __global__ __launch_bounds__(WAVE, 2) void TINY_WAVERES_KERNEL(TINY_WAVERES_ARGS
     const int lane = threadIdx.x;
     float *b = lds + 4 * WAVE + lane;     // b[i * WAVE]: slack of step i, in place
     const int inst = blockIdx.x;
+    TINY_WAVE_SETTINGS_VIEW;
     const bool is_x = lane < NX, is_u = (lane >= NX) && (lane < NX + NU);
     const int N = P.N;
     const int rowbase = (inst * N) * WAVE + lane;
@@ -121,11 +131,11 @@ __global__ __launch_bounds__(WAVE, 2) void TINY_WAVERES_KERNEL(TINY_WAVERES_ARGS
     float pN = 0.f;
     bool ran_bwd = false;
 
-    for (int it = 0; it < P.max_iter; ++it)
+    for (int it = 0; it < my.max_iter; ++it)
     {
         // the last permitted iteration must not overwrite d in c: x,u of an instance that exhausts max_iter come from the d
         // its last forward sweep used (regenerated in the epilogue); the final d itself is in the pd array
-        const bool keep_d = (it == P.max_iter - 1);
+        const bool keep_d = (it == my.max_iter - 1);
         float t1 = 0.f;
         float pri = 0.f, dua = 0.f;
         // ---------------- forward sweep: forward_pass + update_slack + update_dual + residual maxima ----------------
@@ -201,7 +211,7 @@ __global__ __launch_bounds__(WAVE, 2) void TINY_WAVERES_KERNEL(TINY_WAVERES_ARGS
             if (N > 49) a.t1 = fwd_step(49, a.t1, c.t1);
         }
         pN = EXACT ? pterm - rho * t1 : __builtin_fmaf(-rho, t1, pterm); // admm.cpp:83-84
-        if (F.judge(P, it, wave_residuals(pri, dua, is_x, is_u, rho))) break; // admm.cpp:91-109; wave-uniform: the instance is the wave
+        if (F.judge(my, it, wave_residuals(pri, dua, is_x, is_u, rho))) break; // admm.cpp:91-109; wave-uniform: the instance is the wave
         // ---------------- backward sweep: (v = vnew is the in-place slack) linear cost + backward_pass_grad ----------------
         ran_bwd = true;
         {
@@ -283,7 +293,7 @@ __global__ __launch_bounds__(WAVE, 2) void TINY_WAVERES_KERNEL(TINY_WAVERES_ARGS
             c.lo[0] = bwd_step(0, c.lo[0], 0.f, 0.f, false);
         }
     }
-    if (F.no_iterations(P, inst, lane == 0)) return;
+    if (F.no_iterations(my, P, inst, lane == 0)) return;
     {
         // ---------------- live-out ----------------
         const bool solved = F.solved();
@@ -317,7 +327,24 @@ __global__ __launch_bounds__(WAVE, 2) void TINY_WAVERES_KERNEL(TINY_WAVERES_ARGS
     }
 }
 
-#ifdef TINY_WAVERES_PM_UNIT
+#if defined(TINY_WAVERES_PS_UNIT)
+// Per-instance settings (tiny_batch_set_instance_settings with tiny_batch_set_row_kernel(tb, 7)): the launcher of the PS instantiations, compiled as
+// admm_waveres_ps.hip (a translation unit of its own, so that admm_waveres.hip keeps its code).
+hipError_t launch_admm_waveres_ps(int nx, int nu, bool exact, const RowParams &P, const SettingsParams &SP, hipStream_t stream)
+{
+    if (!SP.rec || P.N > WAVERES_MAX_N) return hipErrorInvalidValue;
+    const size_t ldsb = (size_t)(4 * WAVE + P.N * WAVE) * sizeof(float);
+#define TINY_WAVERES_PS_DISPATCH(NX, NU)                                                                                      \
+    if (nx == NX && nu == NU)                                                                                                 \
+    {                                                                                                                         \
+        if (exact) hipLaunchKernelGGL((admm_waveres_ps_kernel<NX, NU, true>), dim3(P.batch), dim3(WAVE), ldsb, stream, P, SP);  \
+        else hipLaunchKernelGGL((admm_waveres_ps_kernel<NX, NU, false>), dim3(P.batch), dim3(WAVE), ldsb, stream, P, SP);       \
+        return hipGetLastError();                                                                                             \
+    }
+    TINY_FOR_EACH_WAVEDIMS(TINY_WAVERES_PS_DISPATCH)
+    return hipErrorInvalidValue;
+}
+#elif defined(TINY_WAVERES_PM_UNIT)
 // Per-instance models (tiny_batch_set_models with tiny_batch_set_row_kernel(tb, 7)): the launcher of the PM instantiations and the kernel that packs the
 // gain tables of both wave kernels, compiled as admm_waveres_pm.hip (a translation unit of its own, so that admm_waveres.hip keeps its code).
 hipError_t launch_admm_waveres_pm(int nx, int nu, bool exact, const RowParams &P, const ModelParams &M, hipStream_t stream)
@@ -395,6 +422,6 @@ hipError_t launch_admm_waveres(int nx, int nu, bool exact, const RowParams &P, h
     TINY_FOR_EACH_WAVEDIMS(TINY_WAVERES_DISPATCH)
     return hipErrorInvalidValue;
 }
-#endif // TINY_WAVERES_PM_UNIT
+#endif // TINY_WAVERES_PS_UNIT, TINY_WAVERES_PM_UNIT
 
 } // namespace tinympc

@@ -833,7 +833,8 @@ struct KernelPlan
     Kernel kernel = Kernel::Rowlane;
     bool exact = true;   // arithmetic: the reference's summation order, or fma
     bool pm = false;     // per-instance models (the ",pm" instantiations of the 16-lane, the two wave and the run-time-dimension kernel)
-    bool ps = false;     // per-instance settings (the ",ps" instantiations of the 16-lane and the streaming row kernel: admm_rowlane_ps.hip, admm_steps_ps.hip)
+    bool ps = false;     // per-instance settings (the ",ps" instantiations of the 16-lane, the streaming row and the two wave kernels: admm_rowlane_ps.hip,
+                         // admm_steps_ps.hip, admm_wave_ps.hip, admm_waveres_ps.hip)
     bool pi = false;     // tile16 with per-instance bounds / reference (admm_tile16_pi.hip)
     Tile16Pi pi_tables{}; // ... and which of its tables go through the rings
     Loop loop = Loop::None;
@@ -921,12 +922,39 @@ int resolve_plan(const TinyBatch *tb, const Call &call, KernelPlan *out)
         if (tb->pm)
             return fail(TINY_BATCH_EUNSUPPORTED, "per-instance settings (tiny_batch_set_instance_settings) are not implemented together with per-instance models "
                                                  "(tiny_batch_clear_models() or tiny_batch_clear_instance_settings())");
-        if (!tb->rowmath_ok)
-            return fail(TINY_BATCH_EUNSUPPORTED, "per-instance settings are implemented by the 16-lane row kernels only (a compiled nx + nu <= 16): nx=%d nu=%d runs on a wave, "
-                                                 "tile48, generic or streaming MFMA kernel, which hold one set of settings per launch (tiny_batch_clear_instance_settings())", tb->nx, tb->nu);
+        // The two wave kernels (one wavefront = one workgroup = one instance: its record is a wave-uniform value and its budget the bound of its own loop)
+        // serve them too, on request: a forced family 6 or 7 (tiny_batch_set_row_kernel) resolves the automatic choice and the row variants to that family's
+        // ",ps" instantiations.  Without one the automatic choice may be tile48 — sixteen instances per workgroup on one set of settings — and stays refused.
+        // They have no on-chip loop: a run replays solve + plant kernel per step.  (tiny_batch_set_row_kernel accepts 7 only where N <= 50.)
+        const std::optional<Kernel> wave_forced = tb->row_family_forced == Kernel::Wavestream || tb->row_family_forced == Kernel::Waveres ? tb->row_family_forced : std::nullopt;
         if (v == VAR_STREAM || v == VAR_GENERIC)
             return fail(TINY_BATCH_EUNSUPPORTED, "per-instance settings are implemented by the row variants only (tiny_batch_select_kernel 0, 2 or 3): variant %d holds one set "
                                                  "of settings per launch", v);
+        if (wave_forced)
+        {
+            if (tb->en_uref || tb->en_d2p) // as without settings: no wave kernel reads them
+                return fail(TINY_BATCH_EUNSUPPORTED, "the optional Uref / coeff_d2p terms (tiny_batch_set_optional_terms) are implemented by the row "
+                                                     "kernels for nx + nu <= 16 only (nx=%d nu=%d, variant %d)", tb->nx, tb->nu, v);
+            if (v == VAR_ROW_FAST && wave_forced != Kernel::Waveres)
+                return fail(TINY_BATCH_EUNSUPPORTED, "fma arithmetic for 16 < nx + nu <= 64 needs the state-on-chip wave kernel (N <= 50); beyond that it is the streaming MFMA kernel (variant 1)");
+            out->kernel = *wave_forced;
+            out->exact = v != VAR_ROW_FAST;
+            out->pm = out->pi = false;
+            out->ps = true;
+            out->sim = call.sim;
+            out->loop = call.run() ? Loop::Replay : Loop::None;
+            return 0;
+        }
+        if (tb->row_family_forced == Kernel::Tile48)
+            return fail(TINY_BATCH_EUNSUPPORTED, "the forced row kernel tile48 (tiny_batch_set_row_kernel) has no per-instance-settings form: its sixteen instances per workgroup run on "
+                                                 "one set of settings; the two wave kernels (6 or 7) serve tiny_batch_set_instance_settings for this class");
+        if (!tb->rowmath_ok && tb->wave_ok)
+            return fail(TINY_BATCH_EUNSUPPORTED, "per-instance settings are implemented by the 16-lane row kernels (a compiled nx + nu <= 16) and, on request, by the two wave kernels: "
+                                                 "the automatic choice for nx=%d nu=%d may be tile48, which holds one set of settings per launch, so it is not made under them; "
+                                                 "tiny_batch_set_row_kernel(tb, 6 or 7) serves this class (or tiny_batch_clear_instance_settings())", tb->nx, tb->nu);
+        if (!tb->rowmath_ok)
+            return fail(TINY_BATCH_EUNSUPPORTED, "per-instance settings are implemented by the 16-lane row kernels only (a compiled nx + nu <= 16): nx=%d nu=%d runs on the "
+                                                 "generic or streaming MFMA kernel, which hold one set of settings per launch (tiny_batch_clear_instance_settings())", tb->nx, tb->nu);
         const std::optional<Kernel> forced = tb->row_family_forced;
         if (forced && forced != Kernel::Rowlane && forced != Kernel::Rowstream)
             return fail(TINY_BATCH_EUNSUPPORTED, "the forced row kernel %s (tiny_batch_set_row_kernel) has no per-instance-settings form: only the 16-lane kernel (1), the "
@@ -1376,7 +1404,8 @@ hipError_t launch_kernel(const TinyBatch *tb, const KernelPlan &pl, RowParams &P
 {
     const int nx = tb->nx, nu = tb->nu, N = tb->N;
     if (S && (pl.kernel != Kernel::Rowlane || pl.ps)) return hipErrorInvalidValue;
-    if (pl.ps && pl.kernel != Kernel::Rowlane && pl.kernel != Kernel::Rowstream) return hipErrorInvalidValue; // a missing ps kernel is an error, never another kernel
+    if (pl.ps && pl.kernel != Kernel::Rowlane && pl.kernel != Kernel::Rowstream && pl.kernel != Kernel::Wavestream && pl.kernel != Kernel::Waveres)
+        return hipErrorInvalidValue; // a missing ps kernel is an error, never another kernel
     switch (pl.kernel)
     {
     case Kernel::Rowlane:
@@ -1391,9 +1420,13 @@ hipError_t launch_kernel(const TinyBatch *tb, const KernelPlan &pl, RowParams &P
     case Kernel::Rowstream:
         if (pl.ps) return launch_admm_rowstream_ps(nx, nu, pl.exact, tb->h16, P, SettingsParams{tb->ps_dev}, tb->stream);
         return launch_admm_rowstream(nx, nu, pl.exact, tb->h16, P, tb->stream);
-    case Kernel::Wavestream: return pl.pm ? launch_admm_wavestream_pm(nx, nu, P, model_params(tb, pl), tb->stream) : launch_admm_wavestream(nx, nu, P, tb->stream);
+    case Kernel::Wavestream:
+        if (pl.ps) return launch_admm_wavestream_ps(nx, nu, P, SettingsParams{tb->ps_dev}, tb->stream);
+        return pl.pm ? launch_admm_wavestream_pm(nx, nu, P, model_params(tb, pl), tb->stream) : launch_admm_wavestream(nx, nu, P, tb->stream);
     case Kernel::Quadlane: return launch_admm_quadlane(N, pl.exact, tb->h16, P, tb->stream);
-    case Kernel::Waveres: return pl.pm ? launch_admm_waveres_pm(nx, nu, pl.exact, P, model_params(tb, pl), tb->stream) : launch_admm_waveres(nx, nu, pl.exact, P, tb->stream);
+    case Kernel::Waveres:
+        if (pl.ps) return launch_admm_waveres_ps(nx, nu, pl.exact, P, SettingsParams{tb->ps_dev}, tb->stream);
+        return pl.pm ? launch_admm_waveres_pm(nx, nu, pl.exact, P, model_params(tb, pl), tb->stream) : launch_admm_waveres(nx, nu, pl.exact, P, tb->stream);
     case Kernel::Tile48: return launch_admm_tile48(N, pl.exact, P, tb->stream);
     case Kernel::Tile16:
     {

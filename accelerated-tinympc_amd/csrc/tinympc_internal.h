@@ -191,10 +191,12 @@ struct SimParams
     const float *w = nullptr;
     float *x_traj = nullptr;
 };
-// Per-instance settings (tiny_batch_set_instance_settings): a kernel argument of its own of the ",ps" instantiations (admm_rowlane_ps.hip, admm_steps_ps.hip),
-// beside RowParams, whose layout stays as it is.  One 16-byte record per instance, [batch padded to 4], loaded once per instance at kernel entry: the four
-// TinySettings members a solve reads (types.hpp:39-47).  The two bound flags never reach a kernel: the host folds them into the {lo, hi} table.  RowParams'
-// own four values are not read by a ps kernel, except P.max_iter, which carries the batch's LARGEST budget: the wave-uniform bound of the iteration loop.
+// Per-instance settings (tiny_batch_set_instance_settings): a kernel argument of its own of the ",ps" instantiations (admm_rowlane_ps.hip, admm_steps_ps.hip,
+// admm_wave_ps.hip, admm_waveres_ps.hip), beside RowParams, whose layout stays as it is.  One 16-byte record per instance, [batch padded to 4], loaded once
+// per instance at kernel entry: the four TinySettings members a solve reads (types.hpp:39-47).  The two bound flags never reach a kernel: the host folds them
+// into the {lo, hi} table.  RowParams' own four values are not read by a ps kernel, except P.max_iter, which carries the batch's LARGEST budget: the
+// wave-uniform bound of the iteration loop where four instances share a wave.  (The wave kernels do not read it either: the instance is the wave and its own
+// budget bounds its loop.)
 struct InstSettings // (the members' names are RowParams': either is a settings view of the solve frame, rowlane_math.h)
 {
     float abs_pri_tol, abs_dua_tol;
@@ -289,6 +291,10 @@ hipError_t launch_admm_waveres_pm(int nx, int nu, bool exact, const RowParams &P
 // ... and their tables from the handle's model records ([batch][pm_gen_floats] -> [batch][pm_wave_floats]; fast = 1: the fma form, which holds -K):
 // 14.6 KB per (16,4) instance, 33 KB per (32,16) instance and arithmetic form — 541 MB at 16 384 instances of the latter (admm_waveres_pm.hip)
 hipError_t launch_models_pack_wave(const float *recs, float *dst, int batch, int nx, int nu, int fast, hipStream_t stream);
+// both wave kernels with per-instance settings (admm_wave_ps.hip, admm_waveres_ps.hip): the instance is the wave, so its record is a wave-uniform value and
+// the iteration loop runs to the instance's OWN budget (P.max_iter is not read); the batch-shared model, shared or per-instance bounds, one solve per launch
+hipError_t launch_admm_wavestream_ps(int nx, int nu, const RowParams &P, const SettingsParams &SP, hipStream_t stream);
+hipError_t launch_admm_waveres_ps(int nx, int nu, bool exact, const RowParams &P, const SettingsParams &SP, hipStream_t stream);
 // nx = 32, nu = 16, N <= 50 with sixteen instances per workgroup on the matrix cores (admm_tile48.hip): exact and fma arithmetic
 bool tile48_supported(int nx, int nu, int N);
 hipError_t launch_admm_tile48(int N, bool exact, const RowParams &P, hipStream_t stream);

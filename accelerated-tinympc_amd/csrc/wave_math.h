@@ -68,6 +68,19 @@ __device__ __forceinline__ float wave_rho(const RowParams &P, [[maybe_unused]] c
     if constexpr (PM) return M.rho[inst];
     else return P.rho;
 }
+// The settings record of the instance a wave solves (admm_wave_ps.hip, admm_waveres_ps.hip), read once at kernel entry.  inst = blockIdx.x, so the record
+// is one 16-byte scalar load; the four values are pinned to scalar registers, whatever the compiler proves about the address: the wave kernels sit at their
+// register budgets, and the loop bound, the check_termination test and the two tolerances are scalar operands everywhere they are read
+__device__ __forceinline__ InstSettings wave_settings(const SettingsParams &SP, int inst)
+{
+    const InstSettings r = SP.rec[inst];
+    InstSettings my;
+    my.abs_pri_tol = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, r.abs_pri_tol)));
+    my.abs_dua_tol = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, r.abs_dua_tol)));
+    my.max_iter = __builtin_amdgcn_readfirstlane(r.max_iter);
+    my.check_termination = __builtin_amdgcn_readfirstlane(r.check_termination);
+    return my;
+}
 
 template <int NX, int NU>
 struct WavePlans

@@ -364,7 +364,11 @@ class TinyBatchSolver:
     # -- per-instance settings (tiny_batch_set_instance_settings) ----------------------------------
     def set_instance_settings(self, abs_pri_tol=None, abs_dua_tol=None, max_iter=None, check_termination=None, en_state_bound=None, en_input_bound=None):
         """Every instance its own TinySettings: each argument is an array [B], a scalar (broadcast over the batch) or None (the field keeps the value of
-        set_settings).  Served by rowlane<...,ps> / rowstream<...,ps> (nx + nu <= 16); replaces any earlier per-instance settings."""
+        set_settings).  Served by rowlane<...,ps> / rowstream<...,ps> (nx + nu <= 16) and, for 16 < nx + nu <= 64, on request by the two wave kernels:
+        after set_row_kernel(7) waveres<nx,nu,exact|fast,ps> (N <= 50), after set_row_kernel(6) wavestream<nx,nu,exact,ps> (any N), where every instance
+        iterates to its own budget.  Refused (TINY_BATCH_EUNSUPPORTED at the solve, kernel_name() "unsupported") for such a class without a forced wave
+        family, with forced tile48, under variants 1 and 4 and together with per-instance models; a closed-loop run refuses a budget of 0.
+        Replaces any earlier per-instance settings."""
         def arr(v, dt):
             return None if v is None else np.ascontiguousarray(np.broadcast_to(np.asarray(v, dt), (self.B,)))
         f = [arr(v, np.float32) for v in (abs_pri_tol, abs_dua_tol)]

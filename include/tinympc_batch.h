@@ -285,6 +285,9 @@ extern "C"
      * With per-instance models (tiny_batch_set_models) 6 and 7 are a request, not only a preference: variants 0 and 2 then run that family's ",pm"
      * instantiations in exact arithmetic and variant 3 with family 7 runs "waveres<...,fast,pm>" (variant 3 with family 6 is refused, as without
      * models); with 0 such a handle stays on "generic<...,pm>", and 8 changes nothing there.
+     * With per-instance settings (tiny_batch_set_instance_settings) 6 and 7 are a request in the same way: variants 0 and 2 run that family's ",ps"
+     * instantiations in exact arithmetic, variant 3 with family 7 runs "waveres<...,fast,ps>" (with family 6 it is refused); with 0 or 8 a solve of
+     * such a class is refused (TINY_BATCH_EUNSUPPORTED), as are variants 1 and 4 and models together with settings.
      * Zero bounds: the two matrix-core kernels (5, 8) project with v_med3_f32, which breaks a tie between zeros of opposite sign the other way than the
      * reference's u_max.cwiseMin(u_min.cwiseMax(t)) does (t = +0 on a lower bound of -0, t = -0 on an upper bound of +0).  In exact arithmetic a handle
      * whose stored bounds hold such a pair — a lower bound of -0 under a positive upper bound, an upper bound of +0 over a lower bound that is negative
@@ -420,7 +423,12 @@ extern "C"
      * tiny_batch_solve returns 1 if any instance used up its own budget.  Bound flags that differ between instances make the {lo, hi} table per instance.
      * Kernels: "rowlane<nx,nu,N,arith,ps>" where (nx, nu, N) has an unrolled instantiation (fp32 storage, no optional terms; shared or per-instance
      * bounds; the on-chip closed loop with shared bounds and no plant), "rowstream<nx,nu,arith[,h16],ps>" for every other compiled nx + nu <= 16.
-     * TINY_BATCH_EUNSUPPORTED with a message: nx + nu > 16, per-instance models, a forced row kernel without a ps form (rowloop, quadlane, tile16),
+     * For 16 < nx + nu <= 64 the two wave kernels serve them on request, under variants 0, 2 and 3: after tiny_batch_set_row_kernel(tb, 7)
+     * "waveres<nx,nu,exact,ps>" / "waveres<nx,nu,fast,ps>" (N <= 50), after (tb, 6) "wavestream<nx,nu,exact,ps>" (any N; variant 3 refused as without
+     * settings).  There the instance is the wavefront: it iterates to its OWN budget and leaves, where four instances of a 16-lane wave run to the
+     * largest of theirs.  A closed-loop run replays solve + plant kernel per step through the one captured graph.
+     * TINY_BATCH_EUNSUPPORTED with a message: nx + nu > 16 without a forced wave family (the automatic choice may be tile48, sixteen instances per
+     * workgroup on one set of settings) or with forced tile48, the optional terms on a wave family (as without settings), per-instance models, a forced row kernel without a ps form (rowloop, quadlane, tile16),
      * the streaming MFMA and run-time-dimension variants.  The longest-first predictor assumes batch-wide settings: a cold start keeps index order. */
     int tiny_batch_set_instance_settings(TinyBatch *tb, const float *abs_pri_tol, const float *abs_dua_tol, const int *max_iter,
                                          const int *check_termination, const int *en_state_bound, const int *en_input_bound);

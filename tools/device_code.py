@@ -4,6 +4,8 @@ cross-compiles, nothing here opens a GPU.
 
     python tools/device_code.py --write           regenerate the record from this tree (a change that means to move a unit)
     python tools/device_code.py --check           compare the record with this tree, print the rows that differ
+    python tools/device_code.py --write --added   the same two for the units of build.ADDED_UNITS, which arrived after the standing record was written
+    python tools/device_code.py --check --added   and are recorded beside it in tests/golden/device_code_added.json
     python tools/device_code.py --against LIB     LIB = accelerated-tinympc_amd/lib of another checkout (built): the parent / new table of
                                                   profiles/*_isa.txt, and for every moved unit the kernels that differ
 """
@@ -20,6 +22,7 @@ import accelerated_tinympc_amd as T  # noqa: E402
 from isa_tools import device_code, kernels_of, moved_units  # noqa: E402
 
 RECORD = ROOT / "tests" / "golden" / "device_code.json"
+ADDED_RECORD = RECORD.with_name("device_code_added.json")   # the units of build.ADDED_UNITS
 
 
 def registers(listing: str) -> dict:
@@ -44,9 +47,10 @@ def against(lib: Path) -> None:
             return build.device_isa_sha(unit)
         except KeyError:
             return None
-    for unit in dict.fromkeys([*parent.SOURCES, *T.build.SOURCES]):
-        old = sha(parent, unit) if unit in parent.SOURCES else "(new unit)"
-        new = sha(T.build, unit) if unit in T.build.SOURCES else "(removed)"
+    linked = lambda b: getattr(b, 'LINKED_SOURCES', b.SOURCES)
+    for unit in dict.fromkeys([*linked(parent), *linked(T.build)]):
+        old = sha(parent, unit) if unit in linked(parent) else "(new unit)"
+        new = sha(T.build, unit) if unit in linked(T.build) else "(removed)"
         if old is None and new is None:
             print(f"{unit:28s} no device code (host only), parent and new")
             continue
@@ -73,24 +77,26 @@ def main() -> int:
     mode.add_argument("--write", action="store_true")
     mode.add_argument("--check", action="store_true")
     mode.add_argument("--against", type=Path, metavar="LIB")
+    ap.add_argument("--added", action="store_true", help="the units of build.ADDED_UNITS and their record, tests/golden/device_code_added.json")
     args = ap.parse_args()
     if args.against:
         against(args.against)
         return 0
     T.build.build()
-    now = device_code(T.build)
+    path, units = (ADDED_RECORD, T.build.ADDED) if args.added else (RECORD, T.build)
+    now = device_code(units)
     if args.write:
         rows = ",\n".join(f"  {json.dumps(u)}: {json.dumps(r)}" for u, r in now["units"].items())   # a row a line: a moved unit is one line of the diff
-        RECORD.write_text(f'{{\n "hipcc": {json.dumps(now["hipcc"])},\n "units": {{\n{rows}\n }}\n}}\n')
-        print(f"wrote {RECORD.relative_to(ROOT)}: {len(now['units'])} units, {sum(r['kernels'] for r in now['units'].values())} kernels")
+        path.write_text(f'{{\n "hipcc": {json.dumps(now["hipcc"])},\n "units": {{\n{rows}\n }}\n}}\n')
+        print(f"wrote {path.relative_to(ROOT)}: {len(now['units'])} units, {sum(r['kernels'] for r in now['units'].values())} kernels")
         return 0
-    record = json.loads(RECORD.read_text())
+    record = json.loads(path.read_text())
     diff = moved_units(record, now)
     for u in diff:
         print(f"{u}: recorded {record['units'].get(u)}, built {now['units'].get(u)}")
     if diff and record["hipcc"] != now["hipcc"]:
         print(f"(recorded under '{record['hipcc']}', this is '{now['hipcc']}')")
-    print(f"{len(diff)} of {len(now['units'])} units differ from {RECORD.relative_to(ROOT)}")
+    print(f"{len(diff)} of {len(now['units'])} units differ from {path.relative_to(ROOT)}")
     return 1 if diff else 0
 
 
